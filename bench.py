@@ -13,7 +13,27 @@ the max-over-ranks time.  The one exchange is the final all-gather of the
 per-instance results over RCCL ("costs": cost, iters, ok, u0 by default;
 "full": xs, us, K, cost), inside every timed step.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+A plain run (`bench.py --gpus G --steps N --warmup W`) does only what the
+headline needs: set-up, W warm-up steps, the N timed steps, the output dump
+when --dump-outputs is given, and the result line (metric, value, unit,
+ms_per_step, ..., the whole-solve roofline priced from the device counters of
+the timed steps).  Everything that takes runs of its own (the single-stream
+per-kernel profile, the CPU baseline, the strong / random_regime / ff extras,
+host_io) runs only with --full, where the --no-* options still drop single
+legs.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's shard:
+xs, us, K, cost, iters, ok, fn_pred as solve_dev leaves them in the caller's
+tensors) as DIR/<name>.npy in float64, at most 64 MB in all: an array too
+large for its share is cut to a seeded sample of instances, whose indices are
+written beside it as DIR/<name>_rows.npy.  Non-finite entries (fn_pred is
+NaN where an instance is not in contact) are written as 0 and marked in
+DIR/<name>_nonfinite.npy (0 finite, 1 NaN, +-2 +-inf).  The inputs are
+seeded, so two builds run with the same arguments can be compared output for
+output.
+
+Prints ONE JSON line (rank 0).  Extra objects (kernels, cpu_baseline, strong,
+random_regime, ff and host_io only with --full):
   roofline      SURVEY §8(d): algorithmic HBM bytes of the whole solve (every
                 kernel, from the device-counted iterations / line-search
                 trials) / wall time of the timed region, vs 8 TB/s; plus the
@@ -296,6 +316,50 @@ def cpu_baseline(cfg, batch, maxiter: int, budget_s: float) -> dict:
     }
 
 
+DUMP_NAMES = ("xs", "us", "K", "cost", "iters", "ok", "fn_pred")
+DUMP_BUDGET = 60_000_000  # bytes over all files (the limit is 64 MB)
+
+
+def dump_outputs(T, out_dir, budget: int = DUMP_BUDGET) -> dict:
+    """Write the solve's outputs (the caller's tensors as the last timed step
+    left them) as <name>.npy in float64.  Smallest first, each array may take
+    an equal share of what is left of the budget; one that does not fit is cut
+    to a sorted, seeded sample of instances (<name>_rows.npy holds their
+    indices).  An array with non-finite entries (fn_pred is NaN where the
+    instance is not in contact) is written with 0 in their place, so that
+    element-wise differences of two dumps stay finite, and
+    <name>_nonfinite.npy marks them: 0 finite, 1 NaN, +-2 +-inf.
+    Returns {name: instances written}."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    arrs, marks = {}, {}
+    for k in DUMP_NAMES:
+        a = T[k].detach().cpu().numpy().astype(np.float64)
+        bad = ~np.isfinite(a)
+        if bad.any():
+            marks[k] = np.where(np.isnan(a), 1.0, np.where(bad, 2.0 * np.sign(a), 0.0))
+            a = np.where(bad, 0.0, a)
+        arrs[k] = a
+    size = {k: arrs[k].nbytes * (2 if k in marks else 1) for k in arrs}
+    left, written = budget, {}
+    for i, k in enumerate(sorted(arrs, key=size.get)):
+        a, m = arrs[k], marks.get(k)
+        share = left // (len(arrs) - i)
+        if size[k] > share:
+            row = size[k] // a.shape[0] + 8  # + its entry in <name>_rows.npy
+            rows = np.sort(np.random.default_rng(SEED).choice(a.shape[0], size=max(1, share // row), replace=False))
+            a, m = a[rows], None if m is None else m[rows]
+            np.save(out / f"{k}_rows.npy", rows.astype(np.float64))
+            left -= rows.size * 8
+        np.save(out / f"{k}.npy", a)
+        left -= a.nbytes
+        if m is not None:
+            np.save(out / f"{k}_nonfinite.npy", m)
+            left -= m.nbytes
+        written[k] = int(a.shape[0])
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -319,9 +383,21 @@ def main():
     ap.add_argument("--force-collective", action="store_true",
                     help="RCCL process group and all-gather even at one process (rehearses RCCL's stream beside "
                          "the solver's 4 slice streams; DESIGN.md §8)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the single-stream per-kernel profile, the CPU "
+                         "baseline, the strong-scaling / random-regime / ff extras and host_io (each can still be "
+                         "dropped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (rank 0's shard) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.profile_only and args.no_profile:
         ap.error("--profile-only runs only the profiling step: it cannot be combined with --no-profile")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, dump, print
+        args.no_cpu_baseline = args.no_host_io = args.no_extras = True
+        args.no_profile = not args.profile_only
 
     import torch
     import torch.distributed as dist
@@ -399,6 +475,8 @@ def main():
             step()
         sync()
         elapsed = shard.timed_steps(step, args.steps, sync)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(T, args.dump_outputs)
 
     stats = T["stats"].cpu().numpy()
     ok = T["ok"].cpu().numpy()

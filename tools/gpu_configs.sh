@@ -13,11 +13,11 @@ TAG=${1:-cfg}
 O=$R/gpurun_out/$TAG; mkdir -p $O
 cd $R
 run() { local name=$1; shift; timeout -k 10 400 python3 "$@" > $O/$name.log 2>&1 || { echo "FAILED: $name"; tail -20 $O/$name.log; exit 1; }; echo "$name done"; }
-run metric bench.py
-run c2_random bench.py --batch 1024 --regime random --no-extras
-run c2_tracking bench.py --batch 1024 --no-extras
-run c3_ff bench.py --variant ff --batch 1024 --no-extras
-run c5_n100_point3d bench.py --horizon 100 --contact point3d --batch 1024 --no-extras --cpu-budget 20
+run metric bench.py --full
+run c2_random bench.py --full --batch 1024 --regime random --no-extras
+run c2_tracking bench.py --full --batch 1024 --no-extras
+run c3_ff bench.py --full --variant ff --batch 1024 --no-extras
+run c5_n100_point3d bench.py --full --horizon 100 --contact point3d --batch 1024 --no-extras --cpu-budget 20
 run c4_sweep tools/sweep_c4.py --seeds 256 --time 4
 run c1_flat -u -c "import ffddp_path; from ffddp.closed_loop import main; main(['--scenario','flat','--time','20','--no-viewer','--results-dir','$O/results'])"
 python3 - "$O" <<'PY'

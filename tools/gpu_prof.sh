@@ -23,5 +23,5 @@ timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o 
 echo "write done"
 python3 $R/tools/pmc_traffic.py $O/fetch $O/write classical/normal_1d/B4096/N30 3 $O/traffic_latest.json > /dev/null
 cp $O/traffic_latest.json $R/profiles/traffic_latest.json
-timeout -k 10 400 python3 $R/bench.py > $O/bench_full.log 2>&1
+timeout -k 10 400 python3 $R/bench.py --full > $O/bench_full.log 2>&1
 echo "bench done"; tail -1 $O/bench_full.log

@@ -13,6 +13,6 @@ if [ "$MODE" = "tests" ]; then
   tail -2 $O/gpu_tests.log
 fi
 for B in 4096 1024 512; do
-  timeout -k 10 200 python3 bench.py --batch $B --no-cpu-baseline --no-extras --no-host-io "$@" > $O/bench_$B.log 2>&1
+  timeout -k 10 200 python3 bench.py --full --batch $B --no-cpu-baseline --no-extras --no-host-io "$@" > $O/bench_$B.log 2>&1
   python3 -c "import json,sys; d=json.loads(open('$O/bench_$B.log').read().strip().splitlines()[-1]); k=d['kernels']; print($B, round(d['value']), 'ms/step %.2f'%d['ms_per_step'], ' '.join('%s=%.0f'%(n,v['avg_launch_ms']*1e3) for n,v in k.items()))"
 done

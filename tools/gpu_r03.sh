@@ -12,7 +12,7 @@ if [ "$2" != "notests" ]; then
   tail -2 $O/gpu_tests.log
   timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 fi
-timeout -k 10 400 python3 bench.py > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
+timeout -k 10 400 python3 bench.py --full > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
 python3 - <<PY
 import json
 d = json.loads(open("$O/bench.log").read().strip().splitlines()[-1])

@@ -56,7 +56,7 @@ for st in $STEPS; do
         head -12 $O/sq4096/summary.txt; head -12 $O/sq512/summary.txt ;;
     prof) bash $R/tools/gpu_prof.sh $TAG/prof skip-tests > $O/prof.log 2>&1 || { tail -20 $O/prof.log; exit 1; }
         tail -3 $O/prof.log | cut -c1-300 ;;
-    bench) timeout -k 10 400 python3 bench.py > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
+    bench) timeout -k 10 400 python3 bench.py --full > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
         tail -1 $O/bench.log | cut -c1-300 ;;
     ab) STEPS=10 BATCHES="${ABB:-4096 1024 512}" bash tools/ab_libs.sh $TAG/ab ${LIBS:-base main} ;;
     abff) STEPS=10 BATCHES="${ABB:-4096 1024}" BENCH_ARGS="--variant ff" bash tools/ab_libs.sh $TAG/abff ${LIBS:-base main} ;;
@@ -73,13 +73,13 @@ for st in $STEPS; do
         done ;;
     small) for L in base main; do
           if [ $L = main ]; then LIB=$R/franka-force-feedback-mpc_amd/lib/libffddp.so; else LIB=$R/franka-force-feedback-mpc_amd/lib/$L/libffddp.so; fi
-          FFDDP_LIB=$LIB timeout -k 10 200 python3 bench.py --horizon 100 --contact point3d --batch 1024 --no-extras --no-cpu-baseline --no-host-io > $O/c5_$L.log 2>&1 || { tail -20 $O/c5_$L.log; exit 1; }
+          FFDDP_LIB=$LIB timeout -k 10 200 python3 bench.py --full --horizon 100 --contact point3d --batch 1024 --no-extras --no-cpu-baseline --no-host-io > $O/c5_$L.log 2>&1 || { tail -20 $O/c5_$L.log; exit 1; }
           python3 -c "import json; d=json.loads(open('$O/c5_$L.log').read().strip().splitlines()[-1]); k=d['kernels']; print('c5', '$L', round(d['value']), ' '.join('%s=%.0f'%(n,v['avg_launch_ms']*1e3) for n,v in k.items()))"
           FFDDP_LIB=$LIB timeout -k 10 200 python3 tools/c1_breakdown.py --time 4 > $O/c1_$L.log 2>&1 || { tail -20 $O/c1_$L.log; exit 1; }
           echo "c1 $L $(tail -1 $O/c1_$L.log | cut -c1-400)"
         done ;;
     quick) for B in 4096 1024 512; do
-        timeout -k 10 200 python3 bench.py --batch $B --no-cpu-baseline --no-extras --no-host-io > $O/q_$B.log 2>&1 || { tail -20 $O/q_$B.log; exit 1; }
+        timeout -k 10 200 python3 bench.py --full --batch $B --no-cpu-baseline --no-extras --no-host-io > $O/q_$B.log 2>&1 || { tail -20 $O/q_$B.log; exit 1; }
         python3 -c "import json; d=json.loads(open('$O/q_$B.log').read().strip().splitlines()[-1]); k=d['kernels']; print($B, round(d['value']), 'ms/step %.2f'%d['ms_per_step'], ' '.join('%s=%.0f'%(n,v['avg_launch_ms']*1e3) for n,v in k.items()))"
       done ;;
   esac

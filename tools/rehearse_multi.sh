@@ -10,6 +10,6 @@ cd $R
 for spec in "2 costs 29533" "4 full 29534"; do
   set -- $spec
   FFDDP_BENCH_ONE_GPU=1 timeout -k 10 240 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $1 \
-    --master-addr 127.0.0.1 --master-port $3 bench.py --gpus $1 --steps 5 --warmup 1 --gather $2 > $O/n$1.log 2>&1
+    --master-addr 127.0.0.1 --master-port $3 bench.py --full --gpus $1 --steps 5 --warmup 1 --gather $2 > $O/n$1.log 2>&1
   tail -1 $O/n$1.log | cut -c1-300
 done
