@@ -2463,6 +2463,80 @@ __global__ __launch_bounds__(64) void k_build(const ffddp_robot* __restrict__ rb
   }
 }
 
+// ---------------------------------------------------------------------------
+// Fleet tick glue (ffddp_fleet_warm_start_dev / ffddp_fleet_keep_dev): pure
+// data movement around the solve of a receding-horizon fleet.  An instance's
+// arrays are contiguous blocks, indexed flat, so lanes touch consecutive
+// doubles (8-byte accesses: with nx = 21 an instance's base is only 8-byte
+// aligned).  Grid (B, FLEET_CHUNKS): the blocks of one instance stride over
+// its flat index together, so valid[b] / fin are uniform in every wave.
+// ---------------------------------------------------------------------------
+constexpr int FLEET_BLOCK = 256;
+constexpr int FLEET_CHUNKS = 4;
+
+// _shift_guess (crocoddyl_classical.py:733-757): xs_init = [x0] + keep_xs[1:],
+// us_init = keep_us[1:] + [keep_us[-1]]; cold: [x0] * (N+1), [u_cold] * N
+__global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_warm_start(
+    int N, int nx, const double* __restrict__ x0, const double* __restrict__ u_cold,
+    const uint8_t* __restrict__ valid, const double* __restrict__ keep_xs, const double* __restrict__ keep_us,
+    double* __restrict__ xs_init, double* __restrict__ us_init) {
+  const long b = blockIdx.x;
+  const int t0 = blockIdx.y * FLEET_BLOCK + threadIdx.x, step = FLEET_CHUNKS * FLEET_BLOCK;
+  const bool warm = valid[b] != 0;
+  const int nxs = (N + 1) * nx, nus = N * NU;
+  const double* xb = x0 + b * nx;
+  const double* kx = keep_xs + b * nxs;
+  double* xo = xs_init + b * nxs;
+  for (int i = t0; i < nxs; i += step) xo[i] = (warm && i >= nx) ? kx[i] : xb[i % nx];
+  const double* ub = u_cold + b * NU;
+  const double* ku = keep_us + b * nus;
+  double* uo = us_init + b * nus;
+  // knot min(k+1, N-1) of keep_us, flat: i + 7 except in the last knot
+  for (int i = t0; i < nus; i += step) uo[i] = warm ? ku[i + NU < nus ? i + NU : i] : ub[i % NU];
+}
+
+// keep the new solution iff its us[0] is finite (crocoddyl_classical.py:378-384),
+// then pack the first-knot record from the kept arrays (layout: include/ffddp.h)
+__global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_keep(
+    int N, int nx, const double* __restrict__ xs, const double* __restrict__ us, const double* __restrict__ K,
+    const double* __restrict__ cost, const int32_t* __restrict__ iters, const uint8_t* __restrict__ ok,
+    const double* __restrict__ fn_pred, const int32_t* __restrict__ stats, double* __restrict__ keep_xs,
+    double* __restrict__ keep_us, double* __restrict__ keep_K, double* __restrict__ first) {
+  const long b = blockIdx.x;
+  const int t0 = blockIdx.y * FLEET_BLOCK + threadIdx.x, step = FLEET_CHUNKS * FLEET_BLOCK;
+  const long nxs = (long)(N + 1) * nx, nus = (long)N * NU, nK = (long)N * NU * nx;
+  const double *xn = xs + b * nxs, *un = us + b * nus, *Kn = K + b * nK;
+  double *xk = keep_xs + b * nxs, *uk = keep_us + b * nus, *Kk = keep_K + b * nK;
+  // fin: every wave tests the seven entries of us[b][0] itself (lanes 0-6, one ballot)
+  const int lane = threadIdx.x & 63;
+  const unsigned long long m = __ballot(lane < NU ? (isfinite(un[lane]) ? 1 : 0) : 1);
+  const bool fin = m == ~0ull;
+  if (fin) {
+    for (int i = t0; i < nxs; i += step) xk[i] = xn[i];
+    for (int i = t0; i < nus; i += step) uk[i] = un[i];
+    for (int i = t0; i < nK; i += step) Kk[i] = Kn[i];
+  }
+  if (blockIdx.y != 0) return;
+  // the record comes from the kept arrays; when fin those equal the new
+  // solution, which is read here instead (the copy above is other waves' work)
+  const double *xr = fin ? xn : xk, *ur = fin ? un : uk, *Kr = fin ? Kn : Kk;
+  const int W = FFDDP_FLEET_FIRST_W(nx), oK = 8 + 2 * nx, oS = 8 + 9 * nx;
+  double* f = first + b * W;
+  for (int j = threadIdx.x; j < W; j += FLEET_BLOCK) {
+    double val;
+    if (j == 0) val = fin ? 1.0 : 0.0;
+    else if (j < 8) val = ur[j - 1];
+    else if (j < oK) val = xr[j - 8];  // knots 0 and 1 are adjacent
+    else if (j < oS) val = Kr[j - oK];
+    else if (j == oS) val = cost[b];
+    else if (j == oS + 1) val = (double)iters[b];
+    else if (j == oS + 2) val = (double)ok[b];
+    else if (j == oS + 3) val = (double)stats[b * FFDDP_NSTATS + 9];
+    else val = fn_pred[b * 2 + (j - oS - 4)];
+    f[j] = val;
+  }
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -3932,6 +4006,37 @@ int ffddp_build_problem_dev(ffddp_handle* h, int B, const ffddp_task* task, cons
   HIPCHK(h, hipSetDevice(h->device));
   hipLaunchKernelGGL(k_build, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, h->drb, T, *task, B, N,
                      h->hc.nx, h->hc.dt, t0, x0, node_ref, inst_ref, surface);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int ffddp_fleet_warm_start_dev(ffddp_handle* h, int B, const double* x0, const double* u_cold, const uint8_t* valid,
+                               const double* keep_xs, const double* keep_us, double* xs_init, double* us_init,
+                               void* stream) {
+  if (!h) return FFDDP_E_INVALID;
+  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_warm_start_dev: B must be positive");
+  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  if (!x0 || !u_cold || !valid || !keep_xs || !keep_us || !xs_init || !us_init)
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_warm_start_dev: null pointer");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_fleet_warm_start, dim3(B, FLEET_CHUNKS), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->hc.N,
+                     h->hc.nx, x0, u_cold, valid, keep_xs, keep_us, xs_init, us_init);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int ffddp_fleet_keep_dev(ffddp_handle* h, int B, const double* xs, const double* us, const double* K,
+                         const double* cost, const int32_t* iters, const uint8_t* ok, const double* fn_pred,
+                         const int32_t* stats, double* keep_xs, double* keep_us, double* keep_K, double* first,
+                         void* stream) {
+  if (!h) return FFDDP_E_INVALID;
+  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_keep_dev: B must be positive");
+  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  if (!xs || !us || !K || !cost || !iters || !ok || !fn_pred || !stats || !keep_xs || !keep_us || !keep_K || !first)
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_keep_dev: null pointer");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_fleet_keep, dim3(B, FLEET_CHUNKS), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->hc.N, h->hc.nx,
+                     xs, us, K, cost, iters, ok, fn_pred, stats, keep_xs, keep_us, keep_K, first);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

@@ -46,6 +46,8 @@ SYMBOLS = (
     "ffddp_plan_create",
     "ffddp_plan_run",
     "ffddp_plan_destroy",
+    "ffddp_fleet_warm_start_dev",
+    "ffddp_fleet_keep_dev",
 )
 PLANT_OBS = 69
 NSTATS = 10
@@ -54,6 +56,11 @@ TRACE_FIELDS = ("iter", "cost", "stop", "grad", "preg", "dreg", "step", "ffeas",
 NEGSTEP_CROCODDYL = 0
 NEGSTEP_BOUNDED_RISE = 1
 KERNEL_CLASSES = ("init", "node", "backward", "forward", "accept", "commit", "finalize", "forward2")
+
+
+def fleet_first_w(nx: int) -> int:
+    """FFDDP_FLEET_FIRST_W(nx): doubles per instance of ffddp_fleet_keep_dev's record."""
+    return 14 + 9 * int(nx)
 
 
 class Robot(C.Structure):
@@ -331,6 +338,10 @@ def load() -> C.CDLL:
     lib.ffddp_plan_run.restype = C.c_int
     lib.ffddp_plan_destroy.argtypes = [C.c_void_p]
     lib.ffddp_plan_destroy.restype = None
+    lib.ffddp_fleet_warm_start_dev.argtypes = [C.c_void_p, C.c_int] + [vp] * 7 + [vp]
+    lib.ffddp_fleet_warm_start_dev.restype = C.c_int
+    lib.ffddp_fleet_keep_dev.argtypes = [C.c_void_p, C.c_int] + [vp] * 12 + [vp]
+    lib.ffddp_fleet_keep_dev.restype = C.c_int
     _lib = lib
     return lib
 

@@ -515,6 +515,15 @@ class ClassicalCrocoddylMPC(_MPCBase):
         return tau_cmd
 
 
+def ff_filter_alpha(cfg, dt: float) -> float:
+    """The torque filter's discrete pole at step dt (crocoddyl_force_feedback.py:
+    493-505: _ff_alpha_ocp with dt_ocp, _ff_alpha_ctrl with the control period)."""
+    if cfg.ff_alpha_override is not None:
+        return float(np.clip(float(cfg.ff_alpha_override), 0.0, 0.999999))
+    wc = 2.0 * np.pi * float(max(cfg.ff_cutoff_hz, 0.0))
+    return float(np.clip(np.exp(-wc * dt), 0.0, 0.999999))
+
+
 class ForceFeedbackCrocoddylMPC(_MPCBase):
     """Force-feedback EE MPC (crocoddyl_force_feedback.py:293-1093): OCP state
     y=(q,v,tau_filtered), control w; torque policy of Eq. 14-18."""
@@ -522,12 +531,13 @@ class ForceFeedbackCrocoddylMPC(_MPCBase):
     variant = "ff"
 
     def __init__(self, sim, traj_fn: Traj, config: Optional[ForceFeedbackMPCConfig] = None, device: int = 0,
-                 use_plan: bool = True):
+                 use_plan: bool = True, calibration_obs=None):
         self.nx_aug = 21
         self._fn_pred_hist_raw: list = []
         self._fn_pred_hist_meas: list = []
         self._fn_pred_corr = np.nan
-        super().__init__(sim, traj_fn, config if config is not None else ForceFeedbackMPCConfig(), device, use_plan)
+        super().__init__(sim, traj_fn, config if config is not None else ForceFeedbackMPCConfig(), device, use_plan,
+                         calibration_obs)
 
     def _initial_tau(self, obs0):
         return obs0.tau_cmd
@@ -545,17 +555,10 @@ class ForceFeedbackCrocoddylMPC(_MPCBase):
 
     # -- filter constants (crocoddyl_force_feedback.py:493-510) ----------------------
     def _ff_alpha_ocp(self) -> float:
-        if self.cfg.ff_alpha_override is not None:
-            return float(np.clip(float(self.cfg.ff_alpha_override), 0.0, 0.999999))
-        wc = 2.0 * np.pi * float(max(self.cfg.ff_cutoff_hz, 0.0))
-        return float(np.clip(np.exp(-wc * self._dt_ocp), 0.0, 0.999999))
+        return ff_filter_alpha(self.cfg, self._dt_ocp)
 
     def _ff_alpha_ctrl(self) -> float:
-        if self.cfg.ff_alpha_override is not None:
-            return float(np.clip(float(self.cfg.ff_alpha_override), 0.0, 0.999999))
-        dt_mpc = float(getattr(self.sim, "dt", self.cfg.dt))
-        wc = 2.0 * np.pi * float(max(self.cfg.ff_cutoff_hz, 0.0))
-        return float(np.clip(np.exp(-wc * dt_mpc), 0.0, 0.999999))
+        return ff_filter_alpha(self.cfg, float(getattr(self.sim, "dt", self.cfg.dt)))
 
     def _policy_epsilon(self) -> float:
         dt_mpc = float(getattr(self.sim, "dt", self.cfg.dt))

@@ -10,6 +10,14 @@ references and results stay in HBM; only x0, the shared node references and
 the first knot of the solution cross PCIe).  Supported configuration: the
 benchmark one (solve every tick, ``mpc_update_steps = 1``; no command filter).
 
+``FleetForceFeedbackMPC`` is the same for ``ForceFeedbackCrocoddylMPC``
+(state y = (q, v, tau_hat), nx = 21; torque policy of Eq. 14-18 on the host).
+Its tick's glue around the solve -- the warm-start shift, keeping the
+solutions whose first control is finite, packing the first knot for the host
+-- runs in two kernels of the library (include/ffddp.h:
+ffddp_fleet_warm_start_dev, ffddp_fleet_keep_dev); the classical fleet uses
+them with ``device_tick=True`` and torch operations by default.
+
 ``run_sweep`` closes B loops around ``BatchedPlant`` (one launch per tick for
 all plants): per instance a scenario (table tilt / actuation mismatch /
 uncertainty injector, run_classical.py:53-91 and uncertainty_profiles.py) and
@@ -30,7 +38,8 @@ import numpy as np
 from . import _abi
 from . import robot as R
 from .config import OcpConfig
-from .controller import _OCP_FIELDS, _quat_wxyz_to_R, classical_benchmark_config
+from .controller import (_OCP_FIELDS, _quat_wxyz_to_R, classical_benchmark_config, ff_benchmark_config,
+                         ff_filter_alpha)
 from .plant import BatchedPlant, PandaTablePlant
 from .runlog import summary_metrics
 from .solver import BatchedBoxFDDP
@@ -40,14 +49,13 @@ from .uncertainty import BatchedUncertaintyInjector, config_for_scenario
 Traj = Callable[[float], Tuple[np.ndarray, np.ndarray, bool]]
 
 
-class FleetClassicalMPC:
-    """B classical controllers, one batched solve per tick.
+class _FleetBase:
+    """What the fleet controllers share: the solver and its device arrays, the
+    kept solution and its ``valid`` mask, the surface latch, the problem
+    references, and the device-side tick (``_tick_device``)."""
 
-    q_nom (B, 7): each instance's initial posture (the scalar controller's
-    ``q_nom = obs0.q``); tau0 (B, 7): its initial command (``obs0.tau_bias``);
-    R_site_from_pin_ee / p_site_minus_frame_pin: the site calibration
-    (crocoddyl_classical.py:199-226; one robot model, so shared).
-    """
+    variant = "classical"
+    nx = 14
 
     def __init__(self, B: int, traj_fn: Traj, config, q_nom, tau0, R_site_from_pin_ee, p_site_minus_frame_pin,
                  device: int = 0):
@@ -55,7 +63,8 @@ class FleetClassicalMPC:
 
         cfg = config
         if int(cfg.mpc_update_steps) != 1 or bool(cfg.apply_command_filter):
-            raise NotImplementedError("FleetClassicalMPC supports the benchmark setup: mpc_update_steps=1, no filter")
+            raise NotImplementedError(
+                f"{type(self).__name__} supports the benchmark setup: mpc_update_steps=1, no filter")
         self.torch = torch
         self.B, self.cfg, self.traj_fn = int(B), cfg, traj_fn
         self.N = int(cfg.horizon)
@@ -67,36 +76,113 @@ class FleetClassicalMPC:
         self.q_nom = np.asarray(q_nom, float).reshape(self.B, 7).copy()
         self.tau_prev = np.asarray(tau0, float).reshape(self.B, 7).copy()
         self.dt_ocp = float(cfg.dt_ocp) if cfg.dt_ocp is not None else float(cfg.dt)
-        ocp = OcpConfig(variant="classical", horizon=self.N, dt=self.dt_ocp, R_des=self.R_des)
-        for f in _OCP_FIELDS:
-            setattr(ocp, f, getattr(cfg, f))
-        ocp.tau_limits = np.asarray(cfg.tau_limits, float).copy()
-        self.solver = BatchedBoxFDDP(ocp, max_batch=self.B, device=device)
+        self.solver = BatchedBoxFDDP(self._ocp_config(), max_batch=self.B, device=device)
         self.solver.neg_step_rule = int(getattr(cfg, "neg_step_rule", 0))
         f64 = dict(dtype=torch.float64, device=self.dev)
-        B, N = self.B, self.N
+        B, N, nx = self.B, self.N, self.nx
         self.T = dict(
-            x0=torch.zeros((B, 14), **f64), node_ref=torch.zeros((B, N + 1, 6), **f64),
+            x0=torch.zeros((B, nx), **f64), node_ref=torch.zeros((B, N + 1, 6), **f64),
             inst_ref=torch.zeros((B, 21), **f64), surface=torch.zeros(B, dtype=torch.uint8, device=self.dev),
-            xs_init=torch.zeros((B, N + 1, 14), **f64), us_init=torch.zeros((B, N, 7), **f64),
-            xs=torch.zeros((B, N + 1, 14), **f64), us=torch.zeros((B, N, 7), **f64),
-            K=torch.zeros((B, N, 7, 14), **f64), cost=torch.zeros(B, **f64),
+            xs_init=torch.zeros((B, N + 1, nx), **f64), us_init=torch.zeros((B, N, 7), **f64),
+            xs=torch.zeros((B, N + 1, nx), **f64), us=torch.zeros((B, N, 7), **f64),
+            K=torch.zeros((B, N, 7, nx), **f64), cost=torch.zeros(B, **f64),
             iters=torch.zeros(B, dtype=torch.int32, device=self.dev), ok=torch.zeros(B, dtype=torch.uint8, device=self.dev),
             fn_pred=torch.zeros((B, 2), **f64), stats=torch.zeros((B, _abi.NSTATS), dtype=torch.int32, device=self.dev),
         )
         # the kept solution (solver.xs/us/K of the last solve whose us[0] was finite)
-        self.keep_xs = torch.zeros((B, N + 1, 14), **f64)
+        self.keep_xs = torch.zeros((B, N + 1, nx), **f64)
         self.keep_us = torch.zeros((B, N, 7), **f64)
-        self.keep_K = torch.zeros((B, N, 7, 14), **f64)
+        self.keep_K = torch.zeros((B, N, 7, nx), **f64)
         self.valid = np.zeros(B, bool)
         self.latched = np.zeros(B, bool)
         self.loss_count = np.zeros(B, np.int64)
         self.prev_mode = np.full(B, -1, np.int8)
         self._stream = torch.cuda.current_stream(self.dev).cuda_stream
+        self._tk = None  # the device tick's arrays, made on its first use
         self.last_info = {}
+
+    def _ocp_config(self) -> OcpConfig:
+        cfg = self.cfg
+        ocp = OcpConfig(variant=self.variant, horizon=self.N, dt=self.dt_ocp, R_des=self.R_des)
+        for f in _OCP_FIELDS:
+            setattr(ocp, f, getattr(cfg, f))
+        ocp.tau_limits = np.asarray(cfg.tau_limits, float).copy()
+        return ocp
 
     def close(self):
         self.solver.close()
+
+    def _phase(self, fn_meas, ee_z, t: float) -> np.ndarray:
+        """_surface_mode + _track_mode: this tick's surface flags; a mode
+        switch drops the instance's warm start."""
+        _, _, hint = self.traj_fn(t)
+        surface_now = self._surface(np.asarray(fn_meas, float), np.asarray(ee_z, float), hint)
+        changed = (self.prev_mode >= 0) & (surface_now != (self.prev_mode == 1))
+        self.valid &= ~changed
+        self.prev_mode = surface_now.astype(np.int8)
+        return surface_now
+
+    def _tau_ref(self, q) -> np.ndarray:
+        """_compute_tau_reference (crocoddyl_classical.py:453-460), vectorised."""
+        tmode = str(self.cfg.torque_ref_mode).strip().lower()
+        if tmode == "zero":
+            return np.zeros((self.B, 7))
+        if tmode == "gravity_qnom":
+            return _abi.gravity_torque(self.q_nom)
+        return _abi.gravity_torque(q)
+
+    # -- the tick on the device (include/ffddp.h: ffddp_fleet_warm_start_dev / _keep_dev) ----
+    def _tick_arrays(self):
+        """One page of host memory laid out as the tick's inputs, its device
+        twin, and views of both: float64 blocks x0, inst_ref, u_cold, the
+        shared node references, then the uint8 flags surface and valid (each
+        block on a 256-byte boundary)."""
+        torch = self.torch
+        B, N, nx = self.B, self.N, self.nx
+        specs = (("x0", (B, nx), np.float64), ("inst_ref", (B, 21), np.float64), ("u_cold", (B, 7), np.float64),
+                 ("node1", (1, N + 1, 6), np.float64), ("surface", (B,), np.uint8), ("valid", (B,), np.uint8))
+        offs, tot = {}, 0
+        for k, shape, dt in specs:
+            offs[k] = tot
+            tot += (int(np.prod(shape)) * np.dtype(dt).itemsize + 255) // 256 * 256
+        host = np.zeros(tot, np.uint8)
+        dev = torch.zeros(tot, dtype=torch.uint8, device=self.dev)
+        hv, t = {}, dict(self.T)
+        for k, shape, dt in specs:
+            n = int(np.prod(shape)) * np.dtype(dt).itemsize
+            hv[k] = host[offs[k]: offs[k] + n].view(dt).reshape(shape)
+            d = dev[offs[k]: offs[k] + n]
+            t[k] = (d.view(torch.float64) if dt is np.float64 else d).view(shape)
+        t.update(keep_xs=self.keep_xs, keep_us=self.keep_us, keep_K=self.keep_K,
+                 first=torch.zeros((B, _abi.fleet_first_w(nx)), dtype=torch.float64, device=self.dev))
+        return dict(host=host, dev=dev, hv=hv, t=t)
+
+    def _tick_device(self, x0, inst_ref, u_cold, surface_now, t: float) -> dict:
+        """One tick through the library's glue kernels: one packed copy up,
+        warm start, solve, keep, one copy of the packed first-knot records
+        down.  Updates ``valid`` with the solves kept; returns the records'
+        fields (of the kept solutions: us0, xs0, xs1, K0; of this solve: fin,
+        cost, iters, ok, neg_acc, fn0, fn1)."""
+        if self._tk is None:
+            self._tk = self._tick_arrays()
+        torch, B, N, nx = self.torch, self.B, self.N, self.nx
+        hv, T = self._tk["hv"], self._tk["t"]
+        hv["x0"][:], hv["inst_ref"][:], hv["u_cold"][:] = x0, inst_ref, u_cold
+        hv["node1"][0] = self._node_ref(t)
+        hv["surface"][:], hv["valid"][:] = surface_now, self.valid
+        self._tk["dev"].copy_(torch.from_numpy(self._tk["host"]))
+        T["node_ref"].copy_(T["node1"].expand(B, N + 1, 6))
+        self.solver.fleet_warm_start_dev(T, stream=self._stream)
+        self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream)
+        self.solver.fleet_keep_dev(T, stream=self._stream)
+        down = T["first"].cpu().numpy()
+        o = 8 + 9 * nx
+        r = dict(fin=down[:, 0] != 0, us0=down[:, 1:8], xs0=down[:, 8:8 + nx], xs1=down[:, 8 + nx:8 + 2 * nx],
+                 K0=down[:, 8 + 2 * nx:o].reshape(B, 7, nx), cost=down[:, o].copy(),
+                 iters=down[:, o + 1].astype(np.int32), ok=down[:, o + 2] != 0, neg_acc=down[:, o + 3].astype(np.int32),
+                 fn0=down[:, o + 4], fn1=down[:, o + 5])
+        self.valid |= r["fin"]
+        return r
 
     # -- per-tick pieces (crocoddyl_classical.py line refs as in controller.py) -------
     def _surface(self, fn_meas, ee_z, hint: bool) -> np.ndarray:
@@ -126,28 +212,46 @@ class FleetClassicalMPC:
             out[k, 3:] = self.R_mj_from_pin.T @ np.asarray(v, float)
         return out
 
-    def compute_control(self, q, v, tau_bias, fn_meas, ee_z, t: float) -> np.ndarray:
+    def _command(self, tau_raw, cost, v, tau_bias):
+        """The unstable fallback (crocoddyl_classical.py:392-404) and _safe_tau
+        (:260-284) without the command filter -> tau_cmd, |tau_raw|inf, unstable."""
+        cfg, B = self.cfg, self.B
+        tau_raw_inf = np.max(np.abs(tau_raw), 1)
+        unstable = (~np.isfinite(cost)) | (cost > float(cfg.max_solver_cost)) | (tau_raw_inf > float(cfg.max_tau_raw_inf))
+        fallback = np.asarray(tau_bias, float).reshape(B, 7) - float(cfg.fallback_dq_damping) * v
+        tau_raw = np.where(unstable[:, None], fallback, tau_raw)
+        self.valid &= ~unstable
+        lim = np.asarray(cfg.tau_limits, float)
+        bad = ~np.all(np.isfinite(tau_raw), 1)
+        tau_cmd = np.clip(np.where(bad[:, None], self.tau_prev, tau_raw), -lim, lim)
+        self.tau_prev = tau_cmd.copy()
+        return tau_cmd, tau_raw_inf, unstable
+
+
+class FleetClassicalMPC(_FleetBase):
+    """B classical controllers, one batched solve per tick.
+
+    q_nom (B, 7): each instance's initial posture (the scalar controller's
+    ``q_nom = obs0.q``); tau0 (B, 7): its initial command (``obs0.tau_bias``);
+    R_site_from_pin_ee / p_site_minus_frame_pin: the site calibration
+    (crocoddyl_classical.py:199-226; one robot model, so shared).
+    device_tick: run the tick's glue (warm start, keep, packing) through the
+    library's two fleet kernels instead of torch operations; same results bit
+    for bit (tests/test_gpu_fleet_ff.py).  Off by default.
+    """
+
+    variant = "classical"
+    nx = 14
+
+    def __init__(self, B: int, traj_fn: Traj, config, q_nom, tau0, R_site_from_pin_ee, p_site_minus_frame_pin,
+                 device: int = 0, device_tick: bool = False):
+        super().__init__(B, traj_fn, config, q_nom, tau0, R_site_from_pin_ee, p_site_minus_frame_pin, device)
+        self.device_tick = bool(device_tick)
+
+    def _tick_torch(self, x0, xreg, tref, surface_now, t: float):
+        """The tick's glue as torch operations -> us0, xs0, K0, cost, iters, ok, neg_acc, fn0."""
         torch = self.torch
         cfg, B, N, T = self.cfg, self.B, self.N, self.T
-        q = np.asarray(q, float).reshape(B, 7)
-        v = np.asarray(v, float).reshape(B, 7)
-        x0 = np.concatenate([q, v], 1)
-        _, _, hint = self.traj_fn(t)
-        surface_now = self._surface(np.asarray(fn_meas, float), np.asarray(ee_z, float), hint)
-        # _track_mode: a mode switch drops the warm start
-        changed = (self.prev_mode >= 0) & (surface_now != (self.prev_mode == 1))
-        self.valid &= ~changed
-        self.prev_mode = surface_now.astype(np.int8)
-        # problem references (_problem_arrays, crocoddyl_classical.py:521-556)
-        mode = str(cfg.posture_ref_mode).strip().lower()
-        xreg = np.concatenate([self.q_nom, np.zeros((B, 7))], 1) if mode == "q_nom" else x0.copy()
-        tmode = str(cfg.torque_ref_mode).strip().lower()
-        if tmode == "zero":
-            tref = np.zeros((B, 7))
-        elif tmode == "gravity_qnom":
-            tref = _abi.gravity_torque(self.q_nom)
-        else:
-            tref = _abi.gravity_torque(q)
         # the tick's inputs go up as ONE copy (packed float64: x0, inst_ref,
         # tau_prev, surface, warm-start mask per instance, then the shared
         # node references), its outputs come down as one (below)
@@ -185,7 +289,25 @@ class FleetClassicalMPC:
         iters = down[:, 121].astype(np.int32)
         ok = down[:, 122] != 0
         neg_acc = down[:, 123].astype(np.int32)  # ascent-direction acceptances of this solve
-        fn_pred = np.where(surface_now, down[:, 124], np.nan)
+        return us0, xs0, K0, cost, iters, ok, neg_acc, down[:, 124]
+
+    def compute_control(self, q, v, tau_bias, fn_meas, ee_z, t: float) -> np.ndarray:
+        cfg, B = self.cfg, self.B
+        q = np.asarray(q, float).reshape(B, 7)
+        v = np.asarray(v, float).reshape(B, 7)
+        x0 = np.concatenate([q, v], 1)
+        surface_now = self._phase(fn_meas, ee_z, t)
+        # problem references (_problem_arrays, crocoddyl_classical.py:521-556)
+        mode = str(cfg.posture_ref_mode).strip().lower()
+        xreg = np.concatenate([self.q_nom, np.zeros((B, 7))], 1) if mode == "q_nom" else x0.copy()
+        tref = self._tau_ref(q)
+        if self.device_tick:
+            r = self._tick_device(x0, np.concatenate([xreg, tref], 1), self.tau_prev, surface_now, t)
+            us0, xs0, K0, cost, iters, ok, neg_acc, fn0 = (r[k] for k in ("us0", "xs0", "K0", "cost", "iters", "ok",
+                                                                         "neg_acc", "fn0"))
+        else:
+            us0, xs0, K0, cost, iters, ok, neg_acc, fn0 = self._tick_torch(x0, xreg, tref, surface_now, t)
+        fn_pred = np.where(surface_now, fn0, np.nan)
         # _policy_control (:759-779): u = us[0] + s K[0] (x - xs[0])
         tau_raw = np.where(self.valid[:, None], us0, self.tau_prev)
         if cfg.use_feedback_policy:
@@ -195,20 +317,105 @@ class FleetClassicalMPC:
             fb = float(cfg.feedback_gain_scale) * np.matmul(K0, (x0 - xs0)[:, :, None])[:, :, 0]
             tau_raw = np.where(self.valid[:, None], tau_raw + fb, tau_raw)
         policy_idx = np.where(self.valid, 0, -1)
-        tau_raw_inf = np.max(np.abs(tau_raw), 1)
-        unstable = (~np.isfinite(cost)) | (cost > float(cfg.max_solver_cost)) | (tau_raw_inf > float(cfg.max_tau_raw_inf))
-        fallback = np.asarray(tau_bias, float).reshape(B, 7) - float(cfg.fallback_dq_damping) * v
-        tau_raw = np.where(unstable[:, None], fallback, tau_raw)
-        self.valid &= ~unstable
-        # _safe_tau (:260-284) without the command filter
-        lim = np.asarray(cfg.tau_limits, float)
-        bad = ~np.all(np.isfinite(tau_raw), 1)
-        tau_cmd = np.clip(np.where(bad[:, None], self.tau_prev, tau_raw), -lim, lim)
-        self.tau_prev = tau_cmd.copy()
+        tau_cmd, tau_raw_inf, unstable = self._command(tau_raw, cost, v, tau_bias)
         self.last_info = dict(ok=ok, cost=cost, iters=iters, tau_raw_inf=tau_raw_inf,
                               tau_cmd_inf=np.max(np.abs(tau_cmd), 1), surface_mode=surface_now, unstable=unstable,
                               fn_pred=fn_pred, solved_now=np.ones(B, bool), policy_idx=policy_idx,
                               neg_accepted=neg_acc)
+        return tau_cmd
+
+
+class FleetForceFeedbackMPC(_FleetBase):
+    """B force-feedback controllers, one batched solve per tick: per instance
+    exactly the logic of ``ForceFeedbackCrocoddylMPC.compute_control``
+    (crocoddyl_force_feedback.py:542-695, our B = 1 mirror in controller.py).
+
+    The constructor is ``FleetClassicalMPC``'s; tau0 (B, 7) is each
+    instance's initial command (``obs0.tau_cmd``).  The tick runs on the
+    library's fleet kernels: one packed upload, warm start, solve, keep, one
+    download of the first-knot records.  The torque policy (Eq. 14-18,
+    crocoddyl_force_feedback.py:1041-1093) is evaluated on the host from those
+    records so that it rounds like the scalar controller.
+
+    ``last_info`` has the classical fleet's keys plus ``tau_des_inf`` and
+    ``fn_pred_raw`` (_predicted_normal_force_next_step, NaN where the instance
+    is free).  The scalar controller's windowed regression of the logged
+    prediction (_align_logged_force_prediction: a least-squares fit per
+    instance and lag, a logged quantity only) is not computed by the fleet:
+    ``fn_pred`` equals ``fn_pred_raw``.
+    """
+
+    variant = "ff"
+    nx = 21
+
+    def _ocp_config(self) -> OcpConfig:
+        """ForceFeedbackCrocoddylMPC._ocp_config."""
+        cfg = self.cfg
+        c = super()._ocp_config()
+        c.ff_alpha = ff_filter_alpha(cfg, self.dt_ocp)
+        c.w_w = float(cfg.w_w)
+        c.w_w_soft_limits = float(cfg.w_w_soft_limits)
+        c.w_y = float(cfg.w_y)
+        c.y_weights = np.concatenate([cfg.y_q_weights, cfg.y_v_weights, cfg.y_tau_weights]).astype(float)
+        c.use_inner_state_reg = bool(cfg.use_inner_state_reg)
+        c.use_inner_tau_reg = bool(cfg.use_inner_tau_reg)
+        return c
+
+    def compute_control(self, q, v, tau_hat, tau_bias, fn_meas, ee_z, t: float) -> np.ndarray:
+        """tau_hat (B, 7): the measured torque state, what the scalar
+        controller's _tau_state_from_obs takes from its observation."""
+        cfg, B = self.cfg, self.B
+        q = np.asarray(q, float).reshape(B, 7)
+        v = np.asarray(v, float).reshape(B, 7)
+        tau_hat = np.asarray(tau_hat, float).reshape(B, 7)
+        y0 = np.concatenate([q, v, tau_hat], 1)
+        surface_now = self._phase(fn_meas, ee_z, t)
+        # problem references (crocoddyl_force_feedback.py:717-721: "x0" -> y0[:14], else q_nom)
+        if str(cfg.posture_ref_mode).strip().lower() == "x0":
+            xreg = y0[:, :14].copy()
+        else:
+            xreg = np.concatenate([self.q_nom, np.zeros((B, 7))], 1)
+        # cold start: w = y0[14:21] (_cold_control)
+        r = self._tick_device(y0, np.concatenate([xreg, self._tau_ref(q)], 1), tau_hat, surface_now, t)
+        cost, xs0, xs1, K0 = r["cost"], r["xs0"], r["xs1"], r["K0"]
+        dt_mpc = float(cfg.dt)
+        alpha = ff_filter_alpha(cfg, self.dt_ocp)
+        eps_pol = float(np.clip(dt_mpc / self.dt_ocp, 0.0, 1.0))  # _policy_epsilon
+        # _predicted_normal_force_next_step (:1219-1243)
+        f0, f1 = np.abs(r["fn0"]), np.abs(r["fn1"])
+        if self.N == 1 or dt_mpc >= self.dt_ocp - 1.0e-9:
+            f01 = f0
+        else:
+            f01 = (1.0 - eps_pol) * f0 + eps_pol * f1
+        fn_next = f0 if self.N == 1 else np.where(~np.isfinite(f0), f1, np.where(~np.isfinite(f1), f0, f01))
+        fn_pred_raw = np.where(surface_now & np.isfinite(fn_next), fn_next, np.nan)
+        # _policy_control, Eq. 14-18 (:1041-1093); instances without a kept solution command tau_hat
+        eps = eps_pol if bool(cfg.ff_use_tau_interpolation) else 0.0
+        with np.errstate(invalid="ignore", over="ignore"):
+            tau0, tau1 = xs0[:, 14:21], xs1[:, 14:21]
+            tau_pol = tau0 + eps * (tau1 - tau0)
+            if cfg.use_feedback_policy:
+                # stacked matmul: per instance the scalar controller's gemv, bit for bit
+                Kx, Ktau = K0[:, :, :14], K0[:, :, 14:21]
+                x_err = xs0[:, :14] - y0[:, :14]
+                tau_err = tau0 - y0[:, 14:21]
+                I7 = np.eye(7)
+                K_tilde_x = eps * (1.0 - alpha) * Kx
+                K_tilde_tau = I7 + eps * (1.0 - alpha) * (Ktau - I7)
+                tau_pol = tau_pol + float(cfg.feedback_gain_scale) * (
+                    np.matmul(K_tilde_x, x_err[:, :, None])[:, :, 0] + np.matmul(K_tilde_tau, tau_err[:, :, None])[:, :, 0])
+        tau_des = np.where(self.valid[:, None], tau_pol, tau_hat)
+        policy_idx = np.where(self.valid, 0, -1)
+        tau_raw = tau_des.copy()
+        if bool(cfg.ff_inverse_actuation_model):
+            a_c = ff_filter_alpha(cfg, dt_mpc)  # _ff_alpha_ctrl
+            tau_raw = (tau_raw - a_c * tau_hat) / max(1.0e-6, 1.0 - a_c)
+        tau_des_inf = np.max(np.abs(tau_des), 1)
+        tau_cmd, tau_raw_inf, unstable = self._command(tau_raw, cost, v, tau_bias)
+        self.last_info = dict(ok=r["ok"], cost=cost, iters=r["iters"], tau_des_inf=tau_des_inf, tau_raw_inf=tau_raw_inf,
+                              tau_cmd_inf=np.max(np.abs(tau_cmd), 1), surface_mode=surface_now, unstable=unstable,
+                              fn_pred=fn_pred_raw.copy(), fn_pred_raw=fn_pred_raw, solved_now=np.ones(B, bool),
+                              policy_idx=policy_idx, neg_accepted=r["neg_acc"])
         return tau_cmd
 
 
@@ -238,7 +445,7 @@ def _sweep_instances(scenarios: Sequence[str], seeds: int):
 def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilted_15", "actuation_uncertainty"),
               seeds: int = 256, total_time: float = 4.0, rank: int = 0, world: int = 1, device: int = 0,
               q_sigma: float = 0.02, verbose: bool = True, record: Sequence[int] = (),
-              neg_step_rule: int = 0) -> dict:
+              neg_step_rule: int = 0, variant: str = "classical", device_tick: bool = False) -> dict:
     """Closed-loop sweep of len(scenarios) * seeds instances; this rank runs
     its contiguous shard.  Returns per-instance summary arrays (this shard).
     record: shard-local instance indices whose controller inputs (the plant
@@ -246,7 +453,19 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     commanded torques are kept per tick, with what a scalar controller needs
     to replay them (the task, the config, the start states).
     neg_step_rule: the solver's ascent-direction comparator (include/ffddp.h
-    FFDDP_NEGSTEP_*; 0 = Crocoddyl's, the reference's behaviour)."""
+    FFDDP_NEGSTEP_*; 0 = Crocoddyl's, the reference's behaviour).
+    variant: "classical" (classical_benchmark_config, FleetClassicalMPC) or
+    "ff" (ff_benchmark_config, FleetForceFeedbackMPC).  The force-feedback
+    controllers' measured torque state tau_hat is, for instances with an
+    uncertainty injector, the injector's filtered torque measurement, and for
+    the others the plant's low-pass of the applied command (PandaTablePlant's
+    tau_meas_act_filt: alpha 0.2, zero at reset, one update per observation);
+    record then also keeps tau_hat per tick.
+    device_tick: FleetClassicalMPC(device_tick=...); the ff fleet always
+    ticks on the device."""
+    variant = str(variant).strip().lower()
+    if variant not in ("classical", "ff"):
+        raise ValueError(f"run_sweep: unknown variant {variant!r}")
     names, tilt, scale, seed = _sweep_instances(scenarios, seeds)
     n_all = len(names)
     per = (n_all + world - 1) // world
@@ -274,9 +493,14 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     plant.set_tilt(0.0)
     plant.step(np.zeros((B, 7)), integrate=False)  # mj_forward at the start state
     tau0 = plant.obs[:, 14:21].copy()
-    cfg = classical_benchmark_config(plant.dt, z_contact, neg_step_rule=neg_step_rule)
-    mpc = FleetClassicalMPC(B, traj, cfg, q_nom=q0, tau0=tau0, R_site_from_pin_ee=R_site_from_pin_ee,
-                            p_site_minus_frame_pin=p_off, device=device)
+    if variant == "ff":
+        cfg = ff_benchmark_config(plant.dt, z_contact, neg_step_rule=neg_step_rule)
+        mpc = FleetForceFeedbackMPC(B, traj, cfg, q_nom=q0, tau0=np.zeros((B, 7)),
+                                    R_site_from_pin_ee=R_site_from_pin_ee, p_site_minus_frame_pin=p_off, device=device)
+    else:
+        cfg = classical_benchmark_config(plant.dt, z_contact, neg_step_rule=neg_step_rule)
+        mpc = FleetClassicalMPC(B, traj, cfg, q_nom=q0, tau0=tau0, R_site_from_pin_ee=R_site_from_pin_ee,
+                                p_site_minus_frame_pin=p_off, device=device, device_tick=device_tick)
     plant.set_tilt(tilt)  # hidden from the controllers
     plant.step(tau0 * 0.0, integrate=False)
     # the scenarios' uncertainty injectors, batched (BatchedUncertaintyInjector:
@@ -296,7 +520,16 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     rec_idx = [int(i) for i in record]
     rec_obs = np.zeros((steps, len(rec_idx), plant.obs.shape[1]))
     rec_tau = np.zeros((steps, len(rec_idx), 7))
+    rec_tau_hat = np.zeros((steps, len(rec_idx), 7))
     rec_t = np.zeros(steps)
+    # the ff variant's torque measurement without an injector (plant.py
+    # PandaTablePlant.get_observation: _filt_act).  The plant filters the
+    # torque it was stepped with, so this filters tau_app (= tau * scale), not
+    # tau; the scenarios that scale the command all carry an injector, whose
+    # own measurement replaces this one, so for them the two are the same.
+    filt_act = np.zeros((B, 7))
+    tau_app = np.zeros((B, 7))
+    lpf = 0.2
     obs = plant.obs.copy()
     t = 0.0
     wall0 = time.perf_counter()
@@ -307,8 +540,16 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
         if inj is not None:
             q, v = q.copy(), v.copy()
             q[inj_idx], v[inj_idx] = inj.observation_for_controller(q[inj_idx], v[inj_idx])
-        tc = time.perf_counter()
-        tau = mpc.compute_control(q, v, bias, fn, ee[:, 2], t)
+        if variant == "ff":
+            filt_act = (1.0 - lpf) * filt_act + lpf * tau_app
+            tau_hat = filt_act.copy()
+            if inj is not None:
+                tau_hat[inj_idx] = inj.tau_hat_filt
+            tc = time.perf_counter()
+            tau = mpc.compute_control(q, v, tau_hat, bias, fn, ee[:, 2], t)
+        else:
+            tc = time.perf_counter()
+            tau = mpc.compute_control(q, v, bias, fn, ee[:, 2], t)
         ctrl_s += time.perf_counter() - tc
         unstable_ticks += mpc.last_info["unstable"]
         neg_ticks += mpc.last_info["neg_accepted"] > 0
@@ -318,6 +559,8 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
             rec_obs[k] = obs[rec_idx]
             rec_obs[k][:, 0:7], rec_obs[k][:, 7:14] = q[rec_idx], v[rec_idx]
             rec_tau[k] = tau[rec_idx]
+            if variant == "ff":
+                rec_tau_hat[k] = tau_hat[rec_idx]
         tau_app = tau * scale
         if inj is not None:
             tau_app[inj_idx] = inj.command_for_plant(tau[inj_idx])
@@ -348,10 +591,12 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     per_inst["neg_accepted_ticks"] = neg_ticks
     per_inst["solve_not_ok_ticks"] = not_ok_ticks
     out = dict(names=names, seed=seed, per_instance=per_inst, ticks=steps, wall_s=wall, controller_s=ctrl_s,
-               instances=B, shard=(lo, hi), n_all=n_all)
+               instances=B, shard=(lo, hi), n_all=n_all, variant=variant)
     if rec_idx:
         out["record"] = dict(index=np.array(rec_idx), t=rec_t, obs=rec_obs, tau=rec_tau, q0=q0[rec_idx], traj=traj,
                              config=cfg, dt=plant.dt, calibration_obs=obs0)
+        if variant == "ff":
+            out["record"]["tau_hat"] = rec_tau_hat
     return out
 
 

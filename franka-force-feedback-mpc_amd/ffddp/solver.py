@@ -297,6 +297,32 @@ class BatchedBoxFDDP:
         )
         self._check(rc, "ffddp_solve_batch_dev")
 
+    # -- fleet tick glue (include/ffddp.h: ffddp_fleet_warm_start_dev / ffddp_fleet_keep_dev) --
+    def fleet_warm_start_dev(self, t, stream=None):
+        """t["xs_init"], t["us_init"] from t["x0"], t["u_cold"] (B, 7), t["valid"]
+        (uint8) and the kept solution t["keep_xs"], t["keep_us"]: the controllers'
+        _shift_guess for B instances in one launch.  Asynchronous on `stream`."""
+        B = int(t["x0"].shape[0])
+        p = lambda k: C.c_void_p(int(t[k].data_ptr()))
+        rc = self._lib.ffddp_fleet_warm_start_dev(
+            self._h, B, p("x0"), p("u_cold"), p("valid"), p("keep_xs"), p("keep_us"), p("xs_init"), p("us_init"),
+            C.c_void_p(stream if stream else 0),
+        )
+        self._check(rc, "ffddp_fleet_warm_start_dev")
+
+    def fleet_keep_dev(self, t, stream=None):
+        """After solve_dev(t): instances whose us[0] is finite replace the kept
+        solution t["keep_xs"], t["keep_us"], t["keep_K"]; t["first"]
+        (B, _abi.fleet_first_w(nx)) takes the packed first-knot record.
+        Asynchronous on `stream`."""
+        B = int(t["x0"].shape[0])
+        p = lambda k: C.c_void_p(int(t[k].data_ptr()))
+        rc = self._lib.ffddp_fleet_keep_dev(
+            self._h, B, p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"), p("fn_pred"), p("stats"),
+            p("keep_xs"), p("keep_us"), p("keep_K"), p("first"), C.c_void_p(stream if stream else 0),
+        )
+        self._check(rc, "ffddp_fleet_keep_dev")
+
     # -- device-side problem builder ----------------------------------------------
     def build_problem_dev(self, task, t, stream=None):
         """Fill t["node_ref"], t["inst_ref"], t["surface"] on the device from

@@ -118,9 +118,12 @@ class BatchedUncertaintyInjector:
     measurement) and 7 for the command -- pre-drawn a chunk of ticks at a time
     (a Generator's normals are one stream however many a call asks for), and
     the delay lines are ring buffers over the batch.  Only the fields the
-    fleet reads are produced: the delayed noisy (q, dq) and the applied
-    command.  Bit-identical to per-instance ScenarioUncertaintyInjector calls
-    (tests/test_closed_loop.py)."""
+    fleets read are produced: the delayed noisy (q, dq), the applied command
+    and, as attributes refreshed by observation_for_controller, the torque
+    measurement ``tau_hat`` (the scalar tau_meas_act) and its first-order
+    filter ``tau_hat_filt`` (tau_meas_act_filt), both (B, nu).  Bit-identical
+    to per-instance ScenarioUncertaintyInjector calls
+    (tests/test_closed_loop.py, tests/test_fleet_ff_cpu.py)."""
 
     CHUNK = 256  # ticks of normals drawn per Generator call
 
@@ -147,6 +150,9 @@ class BatchedUncertaintyInjector:
         self._ci = 0
         self._z = np.zeros((self.B, 0, 4 * self.nu))
         self._zi = 0
+        self._tau_lpf_alpha = float(np.clip(tau_lpf_alpha, 0.0, 1.0))
+        self.tau_hat = np.zeros((self.B, self.nu))
+        self.tau_hat_filt = np.zeros((self.B, self.nu))
 
     def _normals(self):
         """this tick's 28 normals per instance: q, dq, tau (observation), tau (command)"""
@@ -175,7 +181,10 @@ class BatchedUncertaintyInjector:
         self._z_tick = z = self._normals()
         qo = old[:, :nu] + (0.0 + self.sig[0] * z[:, :nu])
         dqo = old[:, nu:] + (0.0 + self.sig[1] * z[:, nu:2 * nu])
-        self._tau_hat(z[:, 2 * nu:3 * nu])  # the torque measurement's draw (the fleet does not read it)
+        # the torque measurement and its filter, as ScenarioUncertaintyInjector.observation_for_controller
+        self.tau_hat = self._tau_hat(z[:, 2 * nu:3 * nu])
+        a = self._tau_lpf_alpha
+        self.tau_hat_filt = (1.0 - a) * self.tau_hat_filt + a * self.tau_hat
         return qo, dqo
 
     def command_for_plant(self, tau_cmd):

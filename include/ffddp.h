@@ -313,6 +313,43 @@ int ffddp_gravity_torque_dev(ffddp_handle* h, int B, const double* q, double* ta
 int ffddp_build_problem_dev(ffddp_handle* h, int B, const ffddp_task* task, const double* t0, const double* x0,
                             double* node_ref, double* inst_ref, uint8_t* surface, void* stream);
 
+/* Per-tick glue of a receding-horizon fleet (B closed loops, one batched
+ * solve per control tick) around ffddp_solve_batch_dev.  Device pointers,
+ * asynchronous on `stream`; N and nx are the handle's.  Pure data movement
+ * plus a finiteness test, so the results are exact.  Outputs must not
+ * overlap inputs.  FFDDP_E_INVALID for a null handle or pointer or B <= 0,
+ * FFDDP_E_CAPACITY for B > max_batch.
+ *
+ * ffddp_fleet_warm_start_dev: the controllers' _shift_guess
+ * (crocoddyl_classical.py:733-757) from the kept solution:
+ *   xs_init[b][0] = x0[b];  k >= 1: valid[b] ? keep_xs[b][k] : x0[b]
+ *                           (the state index is not shifted, as in the reference)
+ *   us_init[b][k] = valid[b] ? keep_us[b][min(k+1, N-1)] : u_cold[b]
+ * x0 [B][nx], u_cold [B][7] (classical: the previous command; force feedback:
+ * y0[14:21]), valid [B] (1 = a kept solution exists), keep_xs [B][N+1][nx],
+ * keep_us [B][N][7] -> xs_init [B][N+1][nx], us_init [B][N][7].
+ *
+ * ffddp_fleet_keep_dev: after the solve.  Per instance fin = the seven
+ * entries of us[b][0] are finite (only knot 0 is tested,
+ * crocoddyl_classical.py:378-384); if fin the instance's whole xs, us, K are
+ * copied to keep_xs, keep_us, keep_K, else those are left untouched.  Then
+ * first[b] takes one packed record from the kept arrays,
+ * FFDDP_FLEET_FIRST_W(nx) = 14 + 9 nx doubles, in this order:
+ *   [0] fin (0 / 1), [1..7] keep_us[0], [8..] keep_xs[0] (nx), keep_xs[1] (nx),
+ *   keep_K[0] (7 nx, row-major [7][nx]), cost, iters, ok, stats[9],
+ *   fn_pred[0], fn_pred[1]
+ * (integers converted to double), which is all a controller reads of a tick's
+ * solve: one copy to the host per tick.  xs, us, K, cost, iters, ok, fn_pred,
+ * stats are ffddp_solve_batch_dev's outputs (stats is required here). */
+#define FFDDP_FLEET_FIRST_W(nx) (14 + 9 * (nx))
+int ffddp_fleet_warm_start_dev(ffddp_handle* h, int B, const double* x0, const double* u_cold, const uint8_t* valid,
+                               const double* keep_xs, const double* keep_us, double* xs_init, double* us_init,
+                               void* stream);
+int ffddp_fleet_keep_dev(ffddp_handle* h, int B, const double* xs, const double* us, const double* K,
+                         const double* cost, const int32_t* iters, const uint8_t* ok, const double* fn_pred,
+                         const int32_t* stats, double* keep_xs, double* keep_us, double* keep_K, double* first,
+                         void* stream);
+
 /* ---------------------------------------------------------------------------
  * Closed-loop plant stand-in: the MuJoCo plant of the
  * reference's closed loop, FrankaMujocoSim.step() in torque mode

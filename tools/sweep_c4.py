@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """BASELINE configs[3]: all 5 scenarios x 256 seeds = 1280 closed-loop runs,
 sharded over the ranks (one process per GPU, torchrun), each rank stepping its
-shard as one fleet (FleetClassicalMPC + BatchedPlant); RCCL all-gather of the
+shard as one fleet (FleetClassicalMPC, or FleetForceFeedbackMPC with
+--variant ff, + BatchedPlant); RCCL all-gather of the
 per-instance summaries; rank 0 prints one JSON line (per-scenario statistics,
 wall time, closed-loop ticks/s).
 
   python tools/sweep_c4.py [--seeds 256] [--time 4]            # 1 GPU
+  python tools/sweep_c4.py --variant ff                        # force-feedback fleet
+  python tools/sweep_c4.py --device-tick 1                     # classical, tick glue in HIP kernels
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/sweep_c4.py
 """
 import argparse
@@ -26,6 +29,11 @@ def main():
     ap.add_argument("--out", type=str, default="")
     ap.add_argument("--neg-step-rule", type=int, choices=(0, 1), default=0,
                     help="ascent-direction comparator: 0 Crocoddyl's (default), 1 bounded rise")
+    ap.add_argument("--variant", choices=("classical", "ff"), default="classical",
+                    help="controller: classical (default) or force feedback")
+    ap.add_argument("--device-tick", type=int, choices=(0, 1), default=0,
+                    help="classical only: 1 runs the tick's glue through the library's fleet kernels "
+                         "(the ff fleet always does)")
     a = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -38,7 +46,7 @@ def main():
         dist.barrier()
     t0 = time.perf_counter()
     res = fleet.run_sweep(seeds=a.seeds, total_time=a.time, rank=rank, world=world, device=local, verbose=(rank == 0),
-                           neg_step_rule=a.neg_step_rule)
+                           neg_step_rule=a.neg_step_rule, variant=a.variant, device_tick=bool(a.device_tick))
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -48,7 +56,8 @@ def main():
                                             a.seeds)
     if rank == 0:
         line = {"config": "5 scenarios x %d seeds closed loop, %.1f s each" % (a.seeds, a.time), "ranks": world,
-                "neg_step_rule": a.neg_step_rule,
+                "neg_step_rule": a.neg_step_rule, "variant": a.variant,
+                "device_tick": int(a.device_tick or a.variant == "ff"),
                 "instances": int(res["n_all"]), "ticks": res["ticks"], "wall_s": wall,
                 "closed_loop_ticks_per_s": res["n_all"] * res["ticks"] / wall,
                 "rank0_controller_s": res["controller_s"], "scenarios": fleet.scenario_table(names, m)}
