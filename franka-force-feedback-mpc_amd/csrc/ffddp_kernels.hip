@@ -2537,6 +2537,224 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_keep(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Fleet closed loop on the device (ffddp_fleet_pre_dev / ffddp_fleet_post_dev):
+// what FleetClassicalMPC / FleetForceFeedbackMPC.compute_control do on the host
+// around the solve, per instance, from the caller's device-resident state.
+// ---------------------------------------------------------------------------
+
+// Everything before the solve.  One block per instance: every wave derives the
+// instance's decisions (latch, mode change, warm / cold) from the old state
+// itself, so they are uniform; the state is rewritten by thread 0 after a
+// barrier, which is why the instance is not split over several blocks as in
+// k_fleet_warm_start (another block could read valid[b] after the rewrite).
+__global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_pre(
+    const ffddp_robot* __restrict__ rb, int N, int nx, ffddp_fleet_params P, ffddp_fleet_state S,
+    const double* __restrict__ q, const double* __restrict__ v, const double* __restrict__ fn_meas,
+    const double* __restrict__ contact, const double* __restrict__ ee_z, long ld, long ld1,
+    const double* __restrict__ tau_hat, long ld_th, const double* __restrict__ q_nom, const double* __restrict__ node1, int hint,
+    double* __restrict__ x0, uint8_t* __restrict__ surface, double* __restrict__ inst_ref,
+    double* __restrict__ node_ref, double* __restrict__ xs_init, double* __restrict__ us_init) {
+  const long b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const bool ff = nx == 21;
+  const bool latched0 = S.latched[b] != 0, valid0 = S.valid[b] != 0;
+  const int cnt0 = S.loss_count[b], pm = S.prev_mode[b];
+  // _surface (fleet.py; crocoddyl_classical.py:286-303)
+  bool latched = latched0, surf = hint != 0;
+  int cnt = cnt0;
+  if (P.phase_source == 1) {
+    double fn = fn_meas[b * ld1];
+    if (contact) fn = fn * (contact[b * ld1] > 0.5 ? 1.0 : 0.0);
+    const double ez = ee_z[b * ld1];
+    const bool near = isfinite(ez) && ez <= P.z_contact + P.z_contact_band;
+    const bool lost = fn < P.fn_contact_off;
+    const int c = latched0 ? (lost ? cnt0 + 1 : 0) : 0;
+    const bool release = latched0 && c >= P.contact_release_steps;
+    const bool engage = !latched0 && (fn > P.fn_contact_on || (hint != 0 && near));
+    latched = (latched0 && !release) || engage;
+    cnt = (release || engage) ? 0 : c;
+    surf = latched;
+  }
+  // _phase: a mode switch drops the warm start
+  const bool changed = pm >= 0 && (surf != (pm == 1));
+  const bool warm = valid0 && !changed;
+  __syncthreads();  // every wave holds the old state
+  if (tid == 0) {
+    S.valid[b] = warm ? 1 : 0;
+    S.latched[b] = latched ? 1 : 0;
+    S.loss_count[b] = cnt;
+    S.prev_mode[b] = surf ? 1 : 0;
+    surface[b] = surf ? 1 : 0;
+  }
+  const double *qb = q + b * ld, *vb = v + b * ld, *th = ff ? tau_hat + b * ld_th : nullptr, *qn = q_nom + b * NQ;
+  auto x0at = [&](int j) -> double { return j < 7 ? qb[j] : (j < 14 ? vb[j - 7] : th[j - 14]); };
+  if (tid < nx) x0[b * nx + tid] = x0at(tid);
+  // problem references (_problem_arrays, crocoddyl_classical.py:521-556; _tau_ref)
+  double* ir = inst_ref + b * 21;
+  if (tid < 14) ir[tid] = P.posture_mode ? (tid < 7 ? qn[tid] : 0.0) : x0at(tid);
+  if (P.torque_mode == 2) {
+    if (tid >= 64 && tid < 64 + NQ) ir[14 + tid - 64] = 0.0;
+  } else if (tid == 64) {  // wave 1, so wave 0's lanes go on with the copies
+    double qq[NQ], g[NQ];
+    for (int i = 0; i < NQ; ++i) qq[i] = P.torque_mode == 1 ? qn[i] : qb[i];
+    gravity_torque(*rb, qq, g);
+    for (int i = 0; i < NQ; ++i) ir[14 + i] = g[i];
+  }
+  const int nref = (N + 1) * 6, nxs = (N + 1) * nx, nus = N * NU;
+  double* nr = node_ref + b * nref;
+  for (int i = tid; i < nref; i += FLEET_BLOCK) nr[i] = node1[i];
+  // _shift_guess, as k_fleet_warm_start
+  const double* kx = S.keep_xs + b * nxs;
+  double* xo = xs_init + b * nxs;
+  for (int i = tid; i < nxs; i += FLEET_BLOCK) xo[i] = (warm && i >= nx) ? kx[i] : x0at(i % nx);
+  const double* ub = ff ? th : S.tau_prev + b * NU;
+  const double* ku = S.keep_us + b * nus;
+  double* uo = us_init + b * nus;
+  for (int i = tid; i < nus; i += FLEET_BLOCK) uo[i] = warm ? ku[i + NU < nus ? i + NU : i] : ub[i % NU];
+}
+
+// max |x| over lanes 0..6 of the wave; a NaN propagates, as in np.max(np.abs(.))
+__device__ __forceinline__ double fleet_absmax7(double x) {
+  double m = 0.0;
+  bool nan = false;
+  for (int i = 0; i < NU; ++i) {
+    const double y = fabs(__shfl(x, i));
+    nan |= y != y;
+    m = fmax(m, y);
+  }
+  return nan ? __builtin_nan("") : m;
+}
+
+// Row i of the torque policy from the kept first knot, in the fleets' order of
+// operations (no contraction: only the order inside the dot products differs
+// from numpy's).  Classical (_policy_control, crocoddyl_classical.py:759-779):
+// us0 + s K0 (x0 - xs0); force feedback (Eq. 14-18, crocoddyl_force_feedback.py:
+// 1041-1093) -> tau_des, then the inverse actuation map -> the return value.
+template <bool FF>
+__device__ __forceinline__ double fleet_policy_row(const ffddp_fleet_params& P, int i, bool valid, const double* ur,
+                                                   const double* xr, const double* Kr, const double* x0b,
+                                                   const double* tau_prev, double& tau_des) {
+#pragma clang fp contract(off)
+  if (!FF) {
+    double t = valid ? ur[i] : tau_prev[i];
+    if (P.use_feedback_policy && valid) {
+      double acc = 0.0;
+      for (int j = 0; j < 14; ++j) acc += Kr[i * 14 + j] * (x0b[j] - xr[j]);
+      t = t + P.feedback_gain_scale * acc;
+    }
+    tau_des = __builtin_nan("");
+    return t;
+  }
+  const double eps = P.ff_use_tau_interpolation ? P.eps_pol : 0.0;
+  const double tau0 = xr[14 + i], tau1 = xr[21 + 14 + i], th = x0b[14 + i];
+  double tp = tau0 + eps * (tau1 - tau0);
+  if (P.use_feedback_policy) {
+    const double c = eps * (1.0 - P.alpha_ocp);
+    double ax = 0.0, at = 0.0;
+    for (int j = 0; j < 14; ++j) ax += (c * Kr[i * 21 + j]) * (xr[j] - x0b[j]);
+    for (int j = 0; j < 7; ++j) {
+      const double I = i == j ? 1.0 : 0.0;
+      at += (I + c * (Kr[i * 21 + 14 + j] - I)) * (xr[14 + j] - x0b[14 + j]);
+    }
+    tp = tp + P.feedback_gain_scale * (ax + at);
+  }
+  tau_des = valid ? tp : th;
+  double t = tau_des;
+  if (P.ff_inverse_actuation_model) t = (t - P.alpha_ctrl * th) / fmax(1.0e-6, 1.0 - P.alpha_ctrl);
+  return t;
+}
+
+// Everything after the solve: k_fleet_keep's keep, then (wave 0 of the
+// instance's first block, lanes 0-6 = the seven joints) the policy, _command,
+// the info record, and the sweep's actuation and log columns when asked for.
+__global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_post(
+    int N, int nx, ffddp_fleet_params P, ffddp_fleet_state S, const double* __restrict__ xs,
+    const double* __restrict__ us, const double* __restrict__ K, const double* __restrict__ cost,
+    const int32_t* __restrict__ iters, const uint8_t* __restrict__ ok, const double* __restrict__ fn_pred,
+    const int32_t* __restrict__ stats, const double* __restrict__ x0, const uint8_t* __restrict__ surface,
+    const double* __restrict__ tau_bias, long ld_bias, double* __restrict__ tau_cmd, double* __restrict__ info,
+    const double* __restrict__ scale, double* __restrict__ tau_app, double* __restrict__ tau_filt, double lpf,
+    const double* __restrict__ obs, long ld_obs, double* __restrict__ log_obs) {
+  const long b = blockIdx.x;
+  const int t0 = blockIdx.y * FLEET_BLOCK + threadIdx.x, step = FLEET_CHUNKS * FLEET_BLOCK;
+  const long nxs = (long)(N + 1) * nx, nus = (long)N * NU, nK = (long)N * NU * nx;
+  const double *xn = xs + b * nxs, *un = us + b * nus, *Kn = K + b * nK;
+  double *xk = S.keep_xs + b * nxs, *uk = S.keep_us + b * nus, *Kk = S.keep_K + b * nK;
+  const int lane = threadIdx.x & 63;
+  const unsigned long long m = __ballot(lane < NU ? (isfinite(un[lane]) ? 1 : 0) : 1);
+  const bool fin = m == ~0ull;
+  if (fin) {
+    for (int i = t0; i < nxs; i += step) xk[i] = xn[i];
+    for (int i = t0; i < nus; i += step) uk[i] = un[i];
+    for (int i = t0; i < nK; i += step) Kk[i] = Kn[i];
+  }
+  if (blockIdx.y != 0 || threadIdx.x >= 64) return;
+  // the kept first knot (when fin the new solution, read in place: the copy above is other waves' work)
+  const double *xr = fin ? xn : xk, *ur = fin ? un : uk, *Kr = fin ? Kn : Kk;
+  const bool ff = nx == 21, on = lane < NU;
+  const int i = on ? lane : 0;  // lanes 7.. repeat joint 0 and write nothing
+  const bool valid = S.valid[b] != 0 || fin;
+  const double* x0b = x0 + b * nx;
+  double* tprev = S.tau_prev + b * NU;
+  const bool surf = surface[b] != 0;
+  double tau_des;
+  double traw = ff ? fleet_policy_row<true>(P, i, valid, ur, xr, Kr, x0b, tprev, tau_des)
+                   : fleet_policy_row<false>(P, i, valid, ur, xr, Kr, x0b, tprev, tau_des);
+  const double tau_des_inf = ff ? fleet_absmax7(tau_des) : __builtin_nan("");
+  // _command: unstable fallback (crocoddyl_classical.py:392-404), _safe_tau (:260-284)
+  const double tau_raw_inf = fleet_absmax7(traw), cb = cost[b];
+  const bool unstable = !isfinite(cb) || cb > P.max_solver_cost || tau_raw_inf > P.max_tau_raw_inf;
+  double tc;
+  {
+#pragma clang fp contract(off)
+    if (unstable) traw = tau_bias[b * ld_bias + i] - P.fallback_dq_damping * x0b[7 + i];
+    const bool bad = __ballot(on && !isfinite(traw)) != 0;
+    const double lim = P.tau_limits[i], x = bad ? tprev[i] : traw;
+    tc = x != x ? x : fmin(fmax(x, -lim), lim);
+  }
+  const double tau_cmd_inf = fleet_absmax7(tc);
+  if (on) {
+    tprev[i] = tc;
+    tau_cmd[b * NU + i] = tc;
+    if (tau_app) {
+#pragma clang fp contract(off)
+      const double ta = scale ? tc * scale[b * NU + i] : tc;
+      tau_app[b * NU + i] = ta;
+      if (tau_filt) tau_filt[b * NU + i] = (1.0 - lpf) * tau_filt[b * NU + i] + lpf * ta;
+    }
+  }
+  if (log_obs && lane < FFDDP_FLEET_LOG_W)  // site position, normal force, contact flag
+    log_obs[b * FFDDP_FLEET_LOG_W + lane] = obs[b * ld_obs + (lane < 3 ? 28 + lane : 43 + lane)];
+  if (lane != 0) return;
+  S.valid[b] = (valid && !unstable) ? 1 : 0;
+  double* f = info + b * FFDDP_FLEET_INFO_W;
+  f[0] = (double)ok[b];
+  f[1] = cb;
+  f[2] = (double)iters[b];
+  f[3] = fin ? 1.0 : 0.0;
+  f[4] = unstable ? 1.0 : 0.0;
+  f[5] = surf ? 1.0 : 0.0;
+  f[6] = valid ? 0.0 : -1.0;
+  f[7] = (double)stats[b * FFDDP_NSTATS + 9];
+  f[8] = tau_raw_inf;
+  f[9] = tau_cmd_inf;
+  f[10] = tau_des_inf;
+  // predicted normal force (classical: knot 0; force feedback: _predicted_normal_force_next_step, :1219-1243)
+  const double fn0 = fn_pred[b * 2], fn1 = fn_pred[b * 2 + 1];
+  double fp;
+  if (!ff) {
+    fp = surf ? fn0 : __builtin_nan("");
+  } else {
+#pragma clang fp contract(off)
+    const double f0 = fabs(fn0), f1 = fabs(fn1);
+    const double f01 = (N == 1 || !P.ff_dt_mpc_below_dt_ocp) ? f0 : (1.0 - P.eps_pol) * f0 + P.eps_pol * f1;
+    const double fnx = N == 1 ? f0 : (!isfinite(f0) ? f1 : (!isfinite(f1) ? f0 : f01));
+    fp = (surf && isfinite(fnx)) ? fnx : __builtin_nan("");
+  }
+  f[11] = fp;
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -4037,6 +4255,56 @@ int ffddp_fleet_keep_dev(ffddp_handle* h, int B, const double* xs, const double*
   HIPCHK(h, hipSetDevice(h->device));
   hipLaunchKernelGGL(k_fleet_keep, dim3(B, FLEET_CHUNKS), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->hc.N, h->hc.nx,
                      xs, us, K, cost, iters, ok, fn_pred, stats, keep_xs, keep_us, keep_K, first);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+static bool fleet_state_complete(const ffddp_fleet_state* s) {
+  return s->valid && s->latched && s->loss_count && s->prev_mode && s->tau_prev && s->keep_xs && s->keep_us && s->keep_K;
+}
+
+int ffddp_fleet_pre_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                        const double* q, const double* v, const double* fn_meas, const double* contact,
+                        const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
+                        const double* q_nom,
+                        const double* node_ref1, int contact_hint, double* x0, uint8_t* surface, double* inst_ref,
+                        double* node_ref, double* xs_init, double* us_init, void* stream) {
+  if (!h) return FFDDP_E_INVALID;
+  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_dev: B must be positive");
+  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  const bool ff = h->hc.nx == 21;
+  if (!p || !s || !fleet_state_complete(s) || !q || !v || !fn_meas || !ee_z || (ff && !tau_hat) || !q_nom ||
+      !node_ref1 || !x0 || !surface || !inst_ref || !node_ref || !xs_init || !us_init)
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_dev: null pointer");
+  if (ld_qv < NQ || ld_scalar < 1 || (ff && ld_tau_hat < NU) || p->phase_source < 0 || p->phase_source > 1 || p->torque_mode < 0 ||
+      p->torque_mode > 2 || p->posture_mode < 0 || p->posture_mode > 1)
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_dev: bad stride or mode");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_fleet_pre, dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx, *p, *s,
+                     q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar, tau_hat, (long)ld_tau_hat, q_nom, node_ref1,
+                     contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int ffddp_fleet_post_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                         const double* xs, const double* us, const double* K, const double* cost,
+                         const int32_t* iters, const uint8_t* ok, const double* fn_pred, const int32_t* stats,
+                         const double* x0, const uint8_t* surface, const double* tau_bias, int ld_tau_bias,
+                         double* tau_cmd, double* info, const double* scale, double* tau_app, double* tau_filt,
+                         double lpf, const double* obs, int ld_obs, double* log_obs, void* stream) {
+  if (!h) return FFDDP_E_INVALID;
+  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_post_dev: B must be positive");
+  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  if (!p || !s || !fleet_state_complete(s) || !xs || !us || !K || !cost || !iters || !ok || !fn_pred || !stats ||
+      !x0 || !surface || !tau_bias || !tau_cmd || !info)
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_post_dev: null pointer");
+  if (ld_tau_bias < NU || (log_obs && (!obs || ld_obs < FFDDP_PLANT_OBS)) || (tau_filt && !tau_app))
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_post_dev: bad stride or optional arguments");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_fleet_post, dim3(B, FLEET_CHUNKS), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->hc.N, h->hc.nx,
+                     *p, *s, xs, us, K, cost, iters, ok, fn_pred, stats, x0, surface, tau_bias, (long)ld_tau_bias,
+                     tau_cmd, info, scale, tau_app, tau_filt, lpf, obs, (long)ld_obs, log_obs);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

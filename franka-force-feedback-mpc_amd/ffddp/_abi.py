@@ -48,6 +48,8 @@ SYMBOLS = (
     "ffddp_plan_destroy",
     "ffddp_fleet_warm_start_dev",
     "ffddp_fleet_keep_dev",
+    "ffddp_fleet_pre_dev",
+    "ffddp_fleet_post_dev",
 )
 PLANT_OBS = 69
 NSTATS = 10
@@ -61,6 +63,46 @@ KERNEL_CLASSES = ("init", "node", "backward", "forward", "accept", "commit", "fi
 def fleet_first_w(nx: int) -> int:
     """FFDDP_FLEET_FIRST_W(nx): doubles per instance of ffddp_fleet_keep_dev's record."""
     return 14 + 9 * int(nx)
+
+
+FLEET_INFO_W = 12
+FLEET_INFO_FIELDS = ("ok", "cost", "iters", "fin", "unstable", "surface", "policy_idx", "neg_accepted", "tau_raw_inf",
+                     "tau_cmd_inf", "tau_des_inf", "fn_pred")
+FLEET_LOG_W = 5  # site position (3), normal force, contact flag
+
+
+class FleetState(C.Structure):
+    """ffddp_fleet_state: the per-instance controller state of the device fleet loop (device pointers)."""
+
+    _fields_ = [(n, C.c_void_p) for n in ("valid", "latched", "loss_count", "prev_mode", "tau_prev", "keep_xs",
+                                          "keep_us", "keep_K")]
+
+
+class FleetParams(C.Structure):
+    """ffddp_fleet_params: the controller configuration's scalars (fleet_params)."""
+
+    _fields_ = [
+        ("phase_source", C.c_int32),
+        ("contact_release_steps", C.c_int32),
+        ("posture_mode", C.c_int32),
+        ("torque_mode", C.c_int32),
+        ("use_feedback_policy", C.c_int32),
+        ("ff_use_tau_interpolation", C.c_int32),
+        ("ff_inverse_actuation_model", C.c_int32),
+        ("ff_dt_mpc_below_dt_ocp", C.c_int32),
+        ("z_contact", C.c_double),
+        ("z_contact_band", C.c_double),
+        ("fn_contact_on", C.c_double),
+        ("fn_contact_off", C.c_double),
+        ("feedback_gain_scale", C.c_double),
+        ("max_solver_cost", C.c_double),
+        ("max_tau_raw_inf", C.c_double),
+        ("fallback_dq_damping", C.c_double),
+        ("tau_limits", C.c_double * 7),
+        ("eps_pol", C.c_double),
+        ("alpha_ocp", C.c_double),
+        ("alpha_ctrl", C.c_double),
+    ]
 
 
 class Robot(C.Structure):
@@ -342,6 +384,13 @@ def load() -> C.CDLL:
     lib.ffddp_fleet_warm_start_dev.restype = C.c_int
     lib.ffddp_fleet_keep_dev.argtypes = [C.c_void_p, C.c_int] + [vp] * 12 + [vp]
     lib.ffddp_fleet_keep_dev.restype = C.c_int
+    fl = [C.c_void_p, C.c_int, C.POINTER(FleetParams), C.POINTER(FleetState)]
+    lib.ffddp_fleet_pre_dev.argtypes = (fl + [vp] * 5 + [C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int] + [vp] * 6
+                                        + [vp])
+    lib.ffddp_fleet_pre_dev.restype = C.c_int
+    lib.ffddp_fleet_post_dev.argtypes = (fl + [vp] * 8 + [vp, vp, vp, C.c_int, vp, vp] + [vp, vp, vp, C.c_double]
+                                         + [vp, C.c_int, vp] + [vp])
+    lib.ffddp_fleet_post_dev.restype = C.c_int
     _lib = lib
     return lib
 

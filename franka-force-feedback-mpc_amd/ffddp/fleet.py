@@ -26,7 +26,9 @@ seeded) and seeds the actuation-uncertainty injector; the reference runs one
 scenario from the keyframe with a fixed seed, so this is a sweep around its
 configuration rather than a replay of it.  Ranks (torch.distributed) take
 contiguous shards of the instances; the per-instance summary metrics are
-all-gathered at the end (RCCL on the GPU box).
+all-gathered at the end (RCCL on the GPU box).  ``run_sweep(device_loop=True)``
+runs the loop itself on the device (fleet_loop.DeviceFleetLoop) for the
+scenarios without an injector.
 """
 from __future__ import annotations
 
@@ -47,6 +49,42 @@ from .trajectory import TABLE_CENTER, TABLE_HALF_Z, TOOL_RADIUS, make_approach_t
 from .uncertainty import BatchedUncertaintyInjector, config_for_scenario
 
 Traj = Callable[[float], Tuple[np.ndarray, np.ndarray, bool]]
+
+
+def node_ref(traj_fn: Traj, t0: float, N: int, dt_ocp: float, R_mj_from_pin, p_site_minus_frame_pin) -> np.ndarray:
+    """A tick's node references (N+1, 6): the trajectory sampled at
+    t0 + k dt_ocp, mapped to the Pinocchio frame (crocoddyl_classical.py:
+    250-258, 526-546).  The fleets and the device loop's table share it."""
+    out = np.zeros((N + 1, 6))
+    sample = getattr(traj_fn, "sample", None)
+    if sample is not None:  # same bits as the loop below (R_MJ_FROM_PIN is a signed permutation)
+        P, V, _ = sample(np.array([t0 + k * dt_ocp for k in range(N + 1)]))
+        out[:, :3] = P @ R_mj_from_pin - p_site_minus_frame_pin
+        out[:, 3:] = V @ R_mj_from_pin
+        return out
+    for k in range(N + 1):
+        p, v, _ = traj_fn(t0 + k * dt_ocp)
+        out[k, :3] = R_mj_from_pin.T @ np.asarray(p, float) - p_site_minus_frame_pin
+        out[k, 3:] = R_mj_from_pin.T @ np.asarray(v, float)
+    return out
+
+
+def fleet_ocp_config(cfg, variant: str, N: int, dt_ocp: float, R_des) -> OcpConfig:
+    """The solver's OCP definition from a controller configuration
+    (_MPCBase._ocp_config; variant "ff": ForceFeedbackCrocoddylMPC._ocp_config)."""
+    ocp = OcpConfig(variant=variant, horizon=N, dt=dt_ocp, R_des=R_des)
+    for f in _OCP_FIELDS:
+        setattr(ocp, f, getattr(cfg, f))
+    ocp.tau_limits = np.asarray(cfg.tau_limits, float).copy()
+    if variant == "ff":
+        ocp.ff_alpha = ff_filter_alpha(cfg, dt_ocp)
+        ocp.w_w = float(cfg.w_w)
+        ocp.w_w_soft_limits = float(cfg.w_w_soft_limits)
+        ocp.w_y = float(cfg.w_y)
+        ocp.y_weights = np.concatenate([cfg.y_q_weights, cfg.y_v_weights, cfg.y_tau_weights]).astype(float)
+        ocp.use_inner_state_reg = bool(cfg.use_inner_state_reg)
+        ocp.use_inner_tau_reg = bool(cfg.use_inner_tau_reg)
+    return ocp
 
 
 class _FleetBase:
@@ -102,12 +140,7 @@ class _FleetBase:
         self.last_info = {}
 
     def _ocp_config(self) -> OcpConfig:
-        cfg = self.cfg
-        ocp = OcpConfig(variant=self.variant, horizon=self.N, dt=self.dt_ocp, R_des=self.R_des)
-        for f in _OCP_FIELDS:
-            setattr(ocp, f, getattr(cfg, f))
-        ocp.tau_limits = np.asarray(cfg.tau_limits, float).copy()
-        return ocp
+        return fleet_ocp_config(self.cfg, self.variant, self.N, self.dt_ocp, self.R_des)
 
     def close(self):
         self.solver.close()
@@ -199,18 +232,7 @@ class _FleetBase:
         return self.latched.copy()
 
     def _node_ref(self, t0: float) -> np.ndarray:
-        out = np.zeros((self.N + 1, 6))
-        sample = getattr(self.traj_fn, "sample", None)
-        if sample is not None:  # same bits as the loop below (R_MJ_FROM_PIN is a signed permutation)
-            P, V, _ = sample(np.array([t0 + k * self.dt_ocp for k in range(self.N + 1)]))
-            out[:, :3] = P @ self.R_mj_from_pin - self.p_site_minus_frame_pin
-            out[:, 3:] = V @ self.R_mj_from_pin
-            return out
-        for k in range(self.N + 1):
-            p, v, _ = self.traj_fn(t0 + k * self.dt_ocp)
-            out[k, :3] = self.R_mj_from_pin.T @ np.asarray(p, float) - self.p_site_minus_frame_pin
-            out[k, 3:] = self.R_mj_from_pin.T @ np.asarray(v, float)
-        return out
+        return node_ref(self.traj_fn, t0, self.N, self.dt_ocp, self.R_mj_from_pin, self.p_site_minus_frame_pin)
 
     def _command(self, tau_raw, cost, v, tau_bias):
         """The unstable fallback (crocoddyl_classical.py:392-404) and _safe_tau
@@ -348,19 +370,6 @@ class FleetForceFeedbackMPC(_FleetBase):
     variant = "ff"
     nx = 21
 
-    def _ocp_config(self) -> OcpConfig:
-        """ForceFeedbackCrocoddylMPC._ocp_config."""
-        cfg = self.cfg
-        c = super()._ocp_config()
-        c.ff_alpha = ff_filter_alpha(cfg, self.dt_ocp)
-        c.w_w = float(cfg.w_w)
-        c.w_w_soft_limits = float(cfg.w_w_soft_limits)
-        c.w_y = float(cfg.w_y)
-        c.y_weights = np.concatenate([cfg.y_q_weights, cfg.y_v_weights, cfg.y_tau_weights]).astype(float)
-        c.use_inner_state_reg = bool(cfg.use_inner_state_reg)
-        c.use_inner_tau_reg = bool(cfg.use_inner_tau_reg)
-        return c
-
     def compute_control(self, q, v, tau_hat, tau_bias, fn_meas, ee_z, t: float) -> np.ndarray:
         """tau_hat (B, 7): the measured torque state, what the scalar
         controller's _tau_state_from_obs takes from its observation."""
@@ -445,7 +454,8 @@ def _sweep_instances(scenarios: Sequence[str], seeds: int):
 def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilted_15", "actuation_uncertainty"),
               seeds: int = 256, total_time: float = 4.0, rank: int = 0, world: int = 1, device: int = 0,
               q_sigma: float = 0.02, verbose: bool = True, record: Sequence[int] = (),
-              neg_step_rule: int = 0, variant: str = "classical", device_tick: bool = False) -> dict:
+              neg_step_rule: int = 0, variant: str = "classical", device_tick: bool = False,
+              device_loop: bool = False) -> dict:
     """Closed-loop sweep of len(scenarios) * seeds instances; this rank runs
     its contiguous shard.  Returns per-instance summary arrays (this shard).
     record: shard-local instance indices whose controller inputs (the plant
@@ -462,10 +472,22 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     tau_meas_act_filt: alpha 0.2, zero at reset, one update per observation);
     record then also keeps tau_hat per tick.
     device_tick: FleetClassicalMPC(device_tick=...); the ff fleet always
-    ticks on the device."""
+    ticks on the device.
+    device_loop: run the whole closed loop on the device (fleet_loop.
+    DeviceFleetLoop: no host synchronisation per tick, the logs come down once
+    at the end) and build the same summary from them.  Not for scenarios with
+    an uncertainty injector nor with ``record`` (NotImplementedError);
+    ``controller_s`` is None, the ticks are not timed apart."""
     variant = str(variant).strip().lower()
     if variant not in ("classical", "ff"):
         raise ValueError(f"run_sweep: unknown variant {variant!r}")
+    if device_loop:
+        injected = [s for s in scenarios if config_for_scenario(str(s), seed=0) is not None]
+        if injected:
+            raise NotImplementedError(f"run_sweep(device_loop=True): the uncertainty injector of {injected} "
+                                      "does not run on the device")
+        if len(record):
+            raise NotImplementedError("run_sweep(device_loop=True): record is not supported")
     names, tilt, scale, seed = _sweep_instances(scenarios, seeds)
     n_all = len(names)
     per = (n_all + world - 1) // world
@@ -486,8 +508,13 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
 
     R_site_from_pin_ee, p_off = site_calibration(obs0)
     nominal.close()
-    plant = BatchedPlant(B, timestep=0.001, n_substeps=5, device=device)
     q0 = np.stack([R.Q_NEUTRAL + np.random.default_rng(int(s)).normal(0.0, q_sigma, 7) for s in seed])
+    if device_loop:
+        out = _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, (R_site_from_pin_ee, p_off), total_time,
+                                neg_step_rule, device, t_cp, verbose)
+        out.update(names=names, seed=seed, shard=(lo, hi), n_all=n_all)
+        return out
+    plant = BatchedPlant(B, timestep=0.001, n_substeps=5, device=device)
     plant.q = q0.copy()
     plant.v = np.zeros((B, 7))
     plant.set_tilt(0.0)
@@ -598,6 +625,53 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
         if variant == "ff":
             out["record"]["tau_hat"] = rec_tau_hat
     return out
+
+
+def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, total_time, neg_step_rule, device, t_cp,
+                      verbose) -> dict:
+    """run_sweep's loop on the device (fleet_loop.DeviceFleetLoop) and the
+    host path's summary from the downloaded logs."""
+    import torch
+
+    from .fleet_loop import DeviceFleetLoop
+
+    B = q0.shape[0]
+    timestep, n_substeps = 0.001, 5
+    dt = float(timestep * n_substeps)  # BatchedPlant.dt
+    make_cfg = ff_benchmark_config if variant == "ff" else classical_benchmark_config
+    cfg = make_cfg(dt, z_contact, neg_step_rule=neg_step_rule)
+    steps = int(total_time / dt)
+    loop = DeviceFleetLoop(variant, B, traj, cfg, q0, tilt_deg=tilt, torque_scale=scale, device=device, steps=steps,
+                           calibration=calibration, timestep=timestep, n_substeps=n_substeps)
+    wall0 = time.perf_counter()
+    loop.run(steps)
+    torch.cuda.synchronize(loop.dev)
+    wall = time.perf_counter() - wall0
+    r = loop.results()
+    loop.close()
+    if np.any(r["plant_fail"]):
+        raise RuntimeError("run_sweep(device_loop=True): a plant step failed (non-SPD mass matrix)")
+    # series[k]: the plant after tick k's command, at the time t_k + dt (the host loop's t += dt)
+    t_after = np.array([float(t) + dt for t in r["t"]])
+    obs = r["obs"][1:]
+    p_ref = np.stack([np.asarray(traj(float(t))[0], float) for t in t_after])
+    err = obs[:, :, 0:3] - p_ref[:, None, :]
+    fnm = obs[:, :, 3] * (obs[:, :, 4] > 0.5)
+    series = dict(t=np.repeat(t_after[:, None], B, 1), err_tan=np.linalg.norm(err[:, :, :2], axis=2),
+                  err_3d=np.linalg.norm(err, axis=2), fn_meas=fnm, contact=(fnm > 0.5).astype(float))
+    if verbose:
+        print(f"device loop: B={B} ticks={steps} | final median |p-p_ref|={np.median(series['err_3d'][-1]):.4f} m | "
+              f"median Fn={np.median(fnm[-1]):.2f} N | ok={np.mean(r['ok']):.3f}", flush=True)
+    per_inst = {k: np.zeros(B) for k in SUMMARY_KEYS}
+    for b in range(B):
+        s = summary_metrics(series["t"][:, b], series["err_tan"][:, b], series["err_3d"][:, b],
+                            series["fn_meas"][:, b], series["contact"][:, b], float(cfg.fn_des), t_cp)
+        for k_ in SUMMARY_KEYS[:-3]:
+            per_inst[k_][b] = s[k_]
+    per_inst["unstable_ticks"] = (r["unstable"] != 0).sum(0).astype(float)
+    per_inst["neg_accepted_ticks"] = (r["neg_accepted"] > 0).sum(0).astype(float)
+    per_inst["solve_not_ok_ticks"] = (r["ok"] == 0).sum(0).astype(float)
+    return dict(per_instance=per_inst, ticks=steps, wall_s=wall, controller_s=None, instances=B, variant=variant)
 
 
 SUMMARY_KEYS = ("rms_tangential_error", "rms_tangential_error_contact_phase", "rms_3d_error", "avg_abs_force_err",

@@ -1,0 +1,250 @@
+"""The fleet closed loop on the device: B plants and B MPC controllers stepped
+together with the host only enqueuing.
+
+``DeviceFleetLoop`` is ``run_sweep``'s loop (fleet.py) for the scenarios
+without an uncertainty injector, with everything a tick does kept in HBM: per
+tick it enqueues the plant step (ffddp_plant_step_dev), the controllers' work
+before the solve (ffddp_fleet_pre_dev: surface latch, mode-switch drop,
+references with the device gravity torque, warm start), the batched solve, and
+their work after it (ffddp_fleet_post_dev: keep, torque policy, unstable
+fallback, clip, the plant-side actuation and the tick's log rows).  No host
+synchronisation and no host<->device copy happens inside ``run``; the logs come
+down once in ``results``.
+
+The node references and the contact hint of every tick depend on the time
+only, so they are tabulated on the host before the run (``reference_table``,
+the fleets' ``node_ref``) and uploaded once: the solve's inputs are the host
+fleets' bit for bit.  Per instance the loop computes what ``FleetClassicalMPC``
+/ ``FleetForceFeedbackMPC.compute_control`` compute, up to the order of
+summation inside the policy's dot products and the device (rather than host)
+evaluation of the gravity torque reference.
+
+Not on the device, and so not supported here: the uncertainty injector
+(``actuation_uncertainty``), ``run_sweep``'s ``record``, and any per-tick host
+callback; ``tick()`` lets a caller look between ticks at the price of its own
+synchronisation.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import numpy as np
+
+from . import _abi
+from . import robot as R
+from .controller import ff_filter_alpha
+from .fleet import Traj, fleet_ocp_config, node_ref, site_calibration
+
+LPF_ALPHA = 0.2  # PandaTablePlant's tau_meas_lpf_alpha: the ff sweep's torque measurement filter
+
+
+def reference_table(traj_fn: Traj, steps: int, dt: float, N: int, dt_ocp: float, R_mj_from_pin,
+                    p_site_minus_frame_pin, t0: float = 0.0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Every tick's node references (steps, N+1, 6), contact hint (steps,) and
+    time (steps,), by the fleets' ``node_ref``; tick k runs at t0 advanced k
+    times by dt (the sweep's ``t += dt``).  Host only: needs no device."""
+    refs = np.zeros((steps, N + 1, 6))
+    hints = np.zeros(steps, bool)
+    times = np.zeros(steps)
+    t = float(t0)
+    for k in range(steps):
+        refs[k] = node_ref(traj_fn, t, N, dt_ocp, R_mj_from_pin, p_site_minus_frame_pin)
+        hints[k] = bool(traj_fn(t)[2])
+        times[k] = t
+        t += dt
+    return refs, hints, times
+
+
+def fleet_params(cfg, variant: str, dt_ocp: float) -> _abi.FleetParams:
+    """ffddp_fleet_params from a ClassicalMPCConfig / ForceFeedbackMPCConfig:
+    the scalars the fleets read in _surface, compute_control and _command."""
+    p = _abi.FleetParams()
+    p.phase_source = 1 if str(cfg.phase_source).strip().lower() == "force_latch" else 0
+    p.contact_release_steps = int(cfg.contact_release_steps)
+    mode = str(cfg.posture_ref_mode).strip().lower()
+    p.posture_mode = (0 if mode == "x0" else 1) if variant == "ff" else (1 if mode == "q_nom" else 0)
+    tmode = str(cfg.torque_ref_mode).strip().lower()
+    p.torque_mode = 2 if tmode == "zero" else (1 if tmode == "gravity_qnom" else 0)
+    p.use_feedback_policy = int(bool(cfg.use_feedback_policy))
+    p.z_contact, p.z_contact_band = float(cfg.z_contact), float(cfg.z_contact_band)
+    p.fn_contact_on, p.fn_contact_off = float(cfg.fn_contact_on), float(cfg.fn_contact_off)
+    p.feedback_gain_scale = float(cfg.feedback_gain_scale)
+    p.max_solver_cost, p.max_tau_raw_inf = float(cfg.max_solver_cost), float(cfg.max_tau_raw_inf)
+    p.fallback_dq_damping = float(cfg.fallback_dq_damping)
+    _abi._fill(p.tau_limits, np.asarray(cfg.tau_limits, float))
+    if variant == "ff":
+        dt_mpc = float(cfg.dt)
+        p.ff_use_tau_interpolation = int(bool(cfg.ff_use_tau_interpolation))
+        p.ff_inverse_actuation_model = int(bool(cfg.ff_inverse_actuation_model))
+        p.ff_dt_mpc_below_dt_ocp = int(dt_mpc < dt_ocp - 1.0e-9)
+        p.eps_pol = float(np.clip(dt_mpc / dt_ocp, 0.0, 1.0))
+        p.alpha_ocp = ff_filter_alpha(cfg, dt_ocp)
+        p.alpha_ctrl = ff_filter_alpha(cfg, dt_mpc)
+    return p
+
+
+STATE_KEYS = ("valid", "latched", "loss_count", "prev_mode", "tau_prev", "keep_xs", "keep_us", "keep_K")
+_PLANT_KEYS = ("q", "v", "obs", "tau_app", "tau_filt")
+
+
+class DeviceFleetLoop:
+    """B closed loops (plant + controller) resident on one device.
+
+    variant: "classical" or "ff"; traj_fn: the task; config: the controller
+    configuration (the fleets' supported one: mpc_update_steps = 1, no command
+    filter); q0 (B, 7): start postures (also each instance's q_nom); tilt_deg,
+    torque_scale: per-instance table tilt (hidden from the controllers) and
+    command scale, (B, 7) per joint (both broadcast); steps: the most ticks
+    the loop will run (sizes the reference table and the logs); calibration:
+    (R_site_from_pin_ee, p_site_minus_frame_pin), by default taken from the
+    nominal plant at the "neutral" keyframe as run_sweep does.
+
+    ``S``: the controller state, ``T``: the solve's arrays, ``P``: the plant's
+    (q, v, obs, tau_app, tau_filt, plane) -- all device tensors.
+    """
+
+    def __init__(self, variant: str, B: int, traj_fn: Traj, config, q0, tilt_deg=0.0, torque_scale=1.0,
+                 device: int = 0, steps: int = 800, calibration: Optional[tuple] = None, t0: float = 0.0,
+                 timestep: float = 0.001, n_substeps: int = 5):
+        variant = str(variant).strip().lower()
+        if variant not in ("classical", "ff"):
+            raise ValueError(f"DeviceFleetLoop: unknown variant {variant!r}")
+        cfg = config
+        if int(cfg.mpc_update_steps) != 1 or bool(cfg.apply_command_filter):
+            raise NotImplementedError("DeviceFleetLoop supports the benchmark setup: mpc_update_steps=1, no filter")
+        import torch
+
+        from .plant import BatchedPlant, PandaTablePlant, table_plane
+        from .solver import BatchedBoxFDDP
+
+        self.torch = torch
+        self.variant, self.B, self.cfg, self.traj_fn = variant, int(B), cfg, traj_fn
+        self.nx = 21 if variant == "ff" else 14
+        self.N = int(cfg.horizon)
+        self.steps = int(steps)
+        self.dt_ocp = float(cfg.dt_ocp) if cfg.dt_ocp is not None else float(cfg.dt)
+        self.dev = torch.device("cuda", device)
+        if calibration is None:
+            nominal = PandaTablePlant(n_substeps=n_substeps, timestep=timestep, device=device)
+            calibration = site_calibration(nominal.reset("neutral"))
+            nominal.close()
+        R_site, p_off = (np.asarray(a, float) for a in calibration)
+        self.R_des = R.R_MJ_FROM_PIN.T @ R.vertical_down_rotation_mj() @ R_site.T
+        self.plant = BatchedPlant(self.B, timestep=timestep, n_substeps=n_substeps, device=device)
+        self.dt = self.plant.dt
+        self.refs, self.hints, self.times = reference_table(traj_fn, self.steps, self.dt, self.N, self.dt_ocp,
+                                                            R.R_MJ_FROM_PIN, p_off, t0)
+        self.params = fleet_params(cfg, variant, self.dt_ocp)
+        self.solver = BatchedBoxFDDP(fleet_ocp_config(cfg, variant, self.N, self.dt_ocp, self.R_des),
+                                     max_batch=self.B, device=device)
+        self.solver.neg_step_rule = int(getattr(cfg, "neg_step_rule", 0))
+        self._stream = torch.cuda.current_stream(self.dev).cuda_stream
+        B, N, nx = self.B, self.N, self.nx
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        z = lambda *s, dtype=torch.float64: torch.zeros(s, dtype=dtype, device=self.dev)  # noqa: E731
+        up = lambda a: torch.from_numpy(np.array(a, dtype=np.float64)).to(self.dev)  # noqa: E731
+        self.S = dict(valid=z(B, dtype=torch.uint8), latched=z(B, dtype=torch.uint8), loss_count=z(B, dtype=torch.int32),
+                      prev_mode=torch.full((B,), -1, dtype=torch.int8, device=self.dev), tau_prev=z(B, 7),
+                      keep_xs=z(B, N + 1, nx), keep_us=z(B, N, 7), keep_K=z(B, N, 7, nx))
+        q0 = np.asarray(q0, float).reshape(B, 7)
+        tilt = np.broadcast_to(np.asarray(tilt_deg, float), (B,))
+        self.P = dict(q=up(q0), v=z(B, 7), obs=z(B, _abi.PLANT_OBS), tau_app=z(B, 7), tau_filt=z(B, 7),
+                      plane=up(np.stack([np.concatenate(table_plane(0.0))] * B)))
+        obs = self.P["obs"]
+        self.T = dict(
+            x0=z(B, nx), node_ref=z(B, N + 1, 6), inst_ref=z(B, 21), surface=z(B, dtype=torch.uint8),
+            xs_init=z(B, N + 1, nx), us_init=z(B, N, 7), xs=z(B, N + 1, nx), us=z(B, N, 7), K=z(B, N, 7, nx),
+            cost=z(B), iters=z(B, dtype=torch.int32), ok=z(B, dtype=torch.uint8), fn_pred=z(B, 2),
+            stats=z(B, _abi.NSTATS, dtype=torch.int32),
+            # the controllers' inputs: views of the plant's records
+            q=obs[:, 0:7], v=obs[:, 7:14], tau_bias=obs[:, 14:21], fn_meas=obs[:, 46], contact=obs[:, 47],
+            ee_z=obs[:, 30], obs=obs, q_nom=up(q0), tau_cmd=z(B, 7), tau_app=self.P["tau_app"],
+            scale=up(np.broadcast_to(np.asarray(torque_scale, float), (B, 7))), **self.S)
+        if variant == "ff":
+            self.T.update(tau_hat=self.P["tau_filt"], tau_filt=self.P["tau_filt"])
+        self.ref_table = up(self.refs)
+        self.log_info = torch.full((self.steps, B, _abi.FLEET_INFO_W), float("nan"), **f64)
+        self.log_obs = torch.full((self.steps + 1, B, _abi.FLEET_LOG_W), float("nan"), **f64)
+        self.log_fail = z(self.steps + 1, B, dtype=torch.int32)
+        # the start: the controllers' first command is the bias torque on a level
+        # table (run_sweep); then the tilted plant's first observation
+        self._plant_step(integrate=False)
+        if variant == "classical":
+            self.S["tau_prev"].copy_(obs[:, 14:21])
+        self.P["plane"].copy_(up(np.stack([np.concatenate(table_plane(t)) for t in tilt])))
+        self.k = 0
+        self._plant_step(integrate=False)
+        self._stepped = True  # obs already is tick k's observation
+        torch.cuda.synchronize(self.dev)
+
+    def close(self):
+        self.solver.close()
+        self.plant.close()
+
+    # -- the tick ---------------------------------------------------------------------
+    def _plant_step(self, integrate: bool = True):
+        P = self.P
+        self.plant.step_dev(P["q"], P["v"], P["tau_app"], P["plane"], P["obs"], fail=self.log_fail[self.k if integrate else 0],
+                            integrate=integrate, stream=self._stream)
+
+    def _enqueue_tick(self):
+        k, T = self.k, self.T
+        if k >= self.steps:
+            raise RuntimeError(f"DeviceFleetLoop: the loop was sized for {self.steps} ticks")
+        if not self._stepped:
+            self._plant_step()
+        T["node_ref1"], T["info"], T["log_obs"] = self.ref_table[k], self.log_info[k], self.log_obs[k]
+        self.solver.fleet_pre_dev(T, self.params, bool(self.hints[k]), stream=self._stream)
+        self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream)
+        self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream)
+        self._stepped = False
+        self.k = k + 1
+
+    def run(self, steps: int):
+        """Enqueue `steps` ticks: plant step, pre, solve, post.  Returns without waiting for the device."""
+        for _ in range(int(steps)):
+            self._enqueue_tick()
+
+    def tick(self):
+        """One tick, waited for, for callers that look at the tensors in between."""
+        self._enqueue_tick()
+        self.torch.cuda.synchronize(self.dev)
+
+    # -- state and logs -----------------------------------------------------------------
+    def state(self) -> dict:
+        """Host copies of the controller state (STATE_KEYS), the plant state and the tick counter."""
+        self.torch.cuda.synchronize(self.dev)
+        s = {k: self.S[k].cpu().numpy().copy() for k in STATE_KEYS}
+        s.update({k: self.P[k].cpu().numpy().copy() for k in _PLANT_KEYS})
+        s.update(k=self.k, stepped=self._stepped)
+        return s
+
+    def load_state(self, s: dict):
+        """Upload what ``state`` returned: the loop continues from that tick."""
+        torch = self.torch
+        for k in STATE_KEYS:
+            self.S[k].copy_(torch.from_numpy(np.ascontiguousarray(s[k])).to(self.dev))
+        for k in _PLANT_KEYS:
+            self.P[k].copy_(torch.from_numpy(np.ascontiguousarray(s[k])).to(self.dev))
+        self.k, self._stepped = int(s["k"]), bool(s["stepped"])
+        torch.cuda.synchronize(self.dev)
+
+    def results(self) -> dict:
+        """The logs of the k ticks run so far, downloaded once: ``info``
+        (k, B, FLEET_INFO_W) and each of its fields by name (k, B), ``obs``
+        (k + 1, B, FLEET_LOG_W): row j is the plant record (site position,
+        normal force, contact flag) tick j's controllers saw, the last row the
+        one after the last command (the plant is stepped for it, once), ``t``
+        (k,) the ticks' times, ``plant_fail`` (B,) plant steps that failed."""
+        torch, k = self.torch, self.k
+        if not self._stepped and k > 0:
+            self._plant_step()
+            self._stepped = True
+        self.log_obs[k].copy_(self.P["obs"][:, [28, 29, 30, 46, 47]])
+        torch.cuda.synchronize(self.dev)
+        info = self.log_info[:k].cpu().numpy()
+        out = dict(info=info, obs=self.log_obs[: k + 1].cpu().numpy(), t=self.times[:k].copy(),
+                   plant_fail=self.log_fail[: k + 1].sum(0).cpu().numpy())
+        for i, name in enumerate(_abi.FLEET_INFO_FIELDS):
+            out[name] = info[:, :, i]
+        return out

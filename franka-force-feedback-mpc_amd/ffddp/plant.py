@@ -171,6 +171,20 @@ class BatchedPlant:
             raise RuntimeError(f"ffddp_plant_step failed ({rc})")
         return self.obs
 
+    def step_dev(self, q, v, tau, plane, obs, fail=None, integrate: bool = True, stream=None):
+        """One control step on device-resident state (ffddp_plant_step_dev):
+        contiguous float64 torch tensors q, v (B, 7; advanced in place), tau
+        (B, 7), plane (B, 6) -> obs (B, PLANT_OBS); fail (B,) int32, optional,
+        takes the per-instance failure flags.  Asynchronous on `stream`; the
+        host arrays of ``step`` are not touched."""
+        for a in (q, v, tau, plane, obs):
+            assert a.is_contiguous() and a.shape[0] == self.B
+        p = lambda a: C.c_void_p(int(a.data_ptr()) if a is not None else 0)  # noqa: E731
+        rc = self.lib.ffddp_plant_step_dev(self._h, self.B, p(q), p(v), p(tau), p(plane), 1 if integrate else 0, p(obs),
+                                           p(fail), C.c_void_p(stream if stream else 0))
+        if rc:
+            raise RuntimeError(f"ffddp_plant_step_dev failed ({rc})")
+
     def close(self):
         if getattr(self, "_h", None):
             self.lib.ffddp_plant_destroy(self._h)

@@ -323,6 +323,59 @@ class BatchedBoxFDDP:
         )
         self._check(rc, "ffddp_fleet_keep_dev")
 
+    # -- fleet closed loop on the device (include/ffddp.h: ffddp_fleet_pre_dev / ffddp_fleet_post_dev) --
+    @staticmethod
+    def _fleet_state(t) -> _abi.FleetState:
+        s = _abi.FleetState()
+        for k, _ in _abi.FleetState._fields_:
+            setattr(s, k, int(t[k].data_ptr()))
+        return s
+
+    def fleet_pre_dev(self, t, params: _abi.FleetParams, hint: bool, stream=None):
+        """Everything a fleet tick does before the solve, for B instances in one
+        launch.  Inputs t["q"], t["v"] (B, 7), t["fn_meas"], t["ee_z"] (B,),
+        optionally t["contact"] (B,) and, for force feedback, t["tau_hat"]
+        (B, 7) -- all may be strided views of the plant's records --
+        t["q_nom"] (B, 7), t["node_ref1"] (N+1, 6) and the trajectory's contact
+        `hint`; the controller state t["valid"], t["latched"] (uint8),
+        t["loss_count"] (int32), t["prev_mode"] (int8), t["tau_prev"] and the
+        kept solution.  Writes the state and the solve's inputs t["x0"],
+        t["surface"], t["inst_ref"], t["node_ref"], t["xs_init"], t["us_init"].
+        Asynchronous on `stream`."""
+        B = int(t["x0"].shape[0])
+        p = lambda k: C.c_void_p(int(t[k].data_ptr()) if t.get(k) is not None else 0)
+        assert t["q"].stride(0) == t["v"].stride(0) and t["fn_meas"].stride(0) == t["ee_z"].stride(0)
+        assert t.get("contact") is None or t["contact"].stride(0) == t["fn_meas"].stride(0)
+        th = t.get("tau_hat")
+        st = self._fleet_state(t)
+        rc = self._lib.ffddp_fleet_pre_dev(
+            self._h, B, C.byref(params), C.byref(st), p("q"), p("v"), p("fn_meas"), p("contact"), p("ee_z"),
+            int(t["q"].stride(0)), int(t["fn_meas"].stride(0)), p("tau_hat"), int(th.stride(0)) if th is not None else 0,
+            p("q_nom"), p("node_ref1"), int(bool(hint)), p("x0"), p("surface"), p("inst_ref"), p("node_ref"),
+            p("xs_init"), p("us_init"), C.c_void_p(stream if stream else 0),
+        )
+        self._check(rc, "ffddp_fleet_pre_dev")
+
+    def fleet_post_dev(self, t, params: _abi.FleetParams, lpf: float = 0.0, stream=None):
+        """Everything a fleet tick does after solve_dev(t): keep, torque policy,
+        unstable fallback and _safe_tau -> t["tau_cmd"] (B, 7), t["info"]
+        (B, _abi.FLEET_INFO_W; fields _abi.FLEET_INFO_FIELDS) and the state.
+        t["tau_bias"] (B, 7) may be a strided view.  Optional: t["tau_app"]
+        (B, 7) = t["scale"] (B, 7) * tau_cmd, t["tau_filt"] (B, 7) low-passed by
+        `lpf`, t["log_obs"] (B, _abi.FLEET_LOG_W) from the plant records
+        t["obs"].  Asynchronous on `stream`."""
+        B = int(t["x0"].shape[0])
+        p = lambda k: C.c_void_p(int(t[k].data_ptr()) if t.get(k) is not None else 0)
+        st = self._fleet_state(t)
+        obs = t.get("obs")
+        rc = self._lib.ffddp_fleet_post_dev(
+            self._h, B, C.byref(params), C.byref(st), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
+            p("fn_pred"), p("stats"), p("x0"), p("surface"), p("tau_bias"), int(t["tau_bias"].stride(0)),
+            p("tau_cmd"), p("info"), p("scale"), p("tau_app"), p("tau_filt"), float(lpf), p("obs"),
+            int(obs.stride(0)) if obs is not None else 0, p("log_obs"), C.c_void_p(stream if stream else 0),
+        )
+        self._check(rc, "ffddp_fleet_post_dev")
+
     # -- device-side problem builder ----------------------------------------------
     def build_problem_dev(self, task, t, stream=None):
         """Fill t["node_ref"], t["inst_ref"], t["surface"] on the device from

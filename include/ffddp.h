@@ -350,6 +350,98 @@ int ffddp_fleet_keep_dev(ffddp_handle* h, int B, const double* xs, const double*
                          const int32_t* stats, double* keep_xs, double* keep_us, double* keep_K, double* first,
                          void* stream);
 
+/* The fleet's closed loop on the device: everything a fleet tick does around
+ * the solve besides the two kernels above, per instance exactly what
+ * FleetClassicalMPC / FleetForceFeedbackMPC.compute_control do on the host
+ * (ffddp/fleet.py), from controller state that stays in caller-owned device
+ * arrays.  A tick is ffddp_fleet_pre_dev, ffddp_solve_batch_dev,
+ * ffddp_fleet_post_dev on one stream; nothing crosses to the host.  Device
+ * pointers, asynchronous on `stream`; N, nx and the variant are the handle's.
+ * FFDDP_E_INVALID for a null handle, a null required pointer, a bad stride
+ * or mode, or B <= 0; FFDDP_E_CAPACITY for B > max_batch. */
+typedef struct ffddp_fleet_state {
+  uint8_t* valid;      /* [B] 1 = a kept solution exists (warm start, policy) */
+  uint8_t* latched;    /* [B] the surface latch (phase_source force_latch) */
+  int32_t* loss_count; /* [B] consecutive ticks below fn_contact_off while latched */
+  int8_t* prev_mode;   /* [B] last tick's surface flag, -1 before the first tick */
+  double* tau_prev;    /* [B][7] the previous command */
+  double* keep_xs;     /* [B][N+1][nx] the kept solution, as for ffddp_fleet_keep_dev */
+  double* keep_us;     /* [B][N][7] */
+  double* keep_K;      /* [B][N][7][nx] */
+} ffddp_fleet_state;
+
+/* The controller configuration's scalars (ClassicalMPCConfig /
+ * ForceFeedbackMPCConfig); the ff_* fields, eps_pol and the alphas are read
+ * by the force-feedback variant only. */
+typedef struct ffddp_fleet_params {
+  int32_t phase_source;          /* 0 "trajectory" (the contact hint), 1 "force_latch" */
+  int32_t contact_release_steps;
+  int32_t posture_mode;          /* 0: x_reg_ref = x0[:14]; 1: [q_nom, 0] */
+  int32_t torque_mode;           /* 0: gravity(q); 1: gravity(q_nom); 2: zero */
+  int32_t use_feedback_policy;
+  int32_t ff_use_tau_interpolation;
+  int32_t ff_inverse_actuation_model;
+  int32_t ff_dt_mpc_below_dt_ocp; /* dt_mpc < dt_ocp - 1e-9 */
+  double z_contact, z_contact_band, fn_contact_on, fn_contact_off;
+  double feedback_gain_scale, max_solver_cost, max_tau_raw_inf, fallback_dq_damping;
+  double tau_limits[7];
+  double eps_pol;    /* clip(dt_mpc / dt_ocp, 0, 1) */
+  double alpha_ocp;  /* the torque filter's pole at dt_ocp */
+  double alpha_ctrl; /* the torque filter's pole at the control period */
+} ffddp_fleet_params;
+
+/* ffddp_fleet_pre_dev: everything before the solve.
+ * Inputs: q, v (rows of 7, row stride ld_qv doubles), fn_meas, ee_z (one value
+ * per instance, stride ld_scalar), tau_hat (rows of 7, stride ld_tau_hat; force
+ * feedback only, else may be NULL) -- so they may be views into the plant's
+ * FFDDP_PLANT_OBS records (q = obs, v = obs + 7, fn_meas = obs + 46, ee_z =
+ * obs + 30, strides FFDDP_PLANT_OBS).  contact (stride ld_scalar, may be
+ * NULL): when given, the force used is fn_meas * (contact > 0.5), the plant
+ * record's obs[46] * (obs[47] > 0.5).  q_nom [B][7]; node_ref1 [N+1][6] this
+ * tick's node references, shared by the instances; contact_hint the
+ * trajectory's contact flag at this tick.
+ * Per instance: the surface latch (_surface; a non-finite ee_z is not near),
+ * the mode-switch drop of `valid` and prev_mode (_phase) -> state, surface[b];
+ * x0[b] = [q, v] (force feedback [q, v, tau_hat]); inst_ref[b] = posture
+ * reference per posture_mode, gravity torque per torque_mode (the device
+ * gravity_torque, as ffddp_gravity_torque_dev); node_ref[b] = node_ref1;
+ * xs_init / us_init by ffddp_fleet_warm_start_dev's rule with the updated
+ * valid and u_cold = tau_prev (classical) or tau_hat (force feedback).
+ *
+ * ffddp_fleet_post_dev: everything after the solve.  xs .. stats are the
+ * solve's outputs, x0 and surface what pre wrote, tau_bias rows of 7 with
+ * stride ld_tau_bias (the plant's obs + 14).  fin and keep as
+ * ffddp_fleet_keep_dev, valid |= fin; the torque policy from the kept first
+ * knot (classical us0 + s K0 (x0 - xs0); force feedback Eq. 14-18 and the
+ * inverse actuation map) in the fleets' order of operations, only the order
+ * of summation inside the dot products differs from numpy's; then _command:
+ * tau_raw_inf, unstable (fallback tau_bias - damping v, valid &= ~unstable),
+ * non-finite rows -> tau_prev, clip to tau_limits, tau_prev = tau_cmd.
+ * Outputs tau_cmd [B][7] and info [B][FFDDP_FLEET_INFO_W]:
+ *   [0] ok, [1] cost, [2] iters, [3] fin, [4] unstable, [5] surface,
+ *   [6] policy_idx (0 / -1), [7] neg_accepted (stats[9]), [8] tau_raw_inf,
+ *   [9] tau_cmd_inf, [10] tau_des_inf (NaN for classical), [11] fn_pred
+ *   (classical: knot 0; force feedback: the knot-0/1 interpolation; NaN when free).
+ * Optional (NULL = off), the closed-loop sweep's actuation and logging:
+ *   tau_app [B][7] = scale [B][7] * tau_cmd, per joint (scale NULL = 1);
+ *   tau_filt [B][7] (needs tau_app) <- (1 - lpf) tau_filt + lpf tau_app, the
+ *     next tick's tau_hat of the force-feedback sweep;
+ *   log_obs [B][FFDDP_FLEET_LOG_W] <- obs[b][28..30, 46, 47] (site position,
+ *     normal force, contact flag) of obs [B] rows with stride ld_obs. */
+#define FFDDP_FLEET_INFO_W 12
+#define FFDDP_FLEET_LOG_W 5
+int ffddp_fleet_pre_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                        const double* q, const double* v, const double* fn_meas, const double* contact,
+                        const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
+                        const double* q_nom, const double* node_ref1, int contact_hint, double* x0, uint8_t* surface,
+                        double* inst_ref, double* node_ref, double* xs_init, double* us_init, void* stream);
+int ffddp_fleet_post_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                         const double* xs, const double* us, const double* K, const double* cost,
+                         const int32_t* iters, const uint8_t* ok, const double* fn_pred, const int32_t* stats,
+                         const double* x0, const uint8_t* surface, const double* tau_bias, int ld_tau_bias,
+                         double* tau_cmd, double* info, const double* scale, double* tau_app, double* tau_filt,
+                         double lpf, const double* obs, int ld_obs, double* log_obs, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Closed-loop plant stand-in: the MuJoCo plant of the
  * reference's closed loop, FrankaMujocoSim.step() in torque mode

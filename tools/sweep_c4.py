@@ -9,6 +9,8 @@ wall time, closed-loop ticks/s).
   python tools/sweep_c4.py [--seeds 256] [--time 4]            # 1 GPU
   python tools/sweep_c4.py --variant ff                        # force-feedback fleet
   python tools/sweep_c4.py --device-tick 1                     # classical, tick glue in HIP kernels
+  python tools/sweep_c4.py --device-loop 1 --scenarios flat tilted_5 tilted_10 tilted_15
+                                                               # the whole closed loop on the device
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/sweep_c4.py
 """
 import argparse
@@ -20,6 +22,9 @@ from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import ffddp_path  # noqa: E402,F401
+
+
+ALL_SCENARIOS = ("flat", "tilted_5", "tilted_10", "tilted_15", "actuation_uncertainty")
 
 
 def main():
@@ -34,6 +39,10 @@ def main():
     ap.add_argument("--device-tick", type=int, choices=(0, 1), default=0,
                     help="classical only: 1 runs the tick's glue through the library's fleet kernels "
                          "(the ff fleet always does)")
+    ap.add_argument("--device-loop", type=int, choices=(0, 1), default=0,
+                    help="1 runs the whole closed loop on the device (DeviceFleetLoop); not for scenarios "
+                         "with an uncertainty injector (actuation_uncertainty)")
+    ap.add_argument("--scenarios", nargs="+", default=list(ALL_SCENARIOS), help="scenarios to sweep (default: all 5)")
     a = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -45,17 +54,18 @@ def main():
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
-    res = fleet.run_sweep(seeds=a.seeds, total_time=a.time, rank=rank, world=world, device=local, verbose=(rank == 0),
-                           neg_step_rule=a.neg_step_rule, variant=a.variant, device_tick=bool(a.device_tick))
+    res = fleet.run_sweep(scenarios=tuple(a.scenarios), seeds=a.seeds, total_time=a.time, rank=rank, world=world,
+                           device=local, verbose=(rank == 0), neg_step_rule=a.neg_step_rule, variant=a.variant, device_tick=bool(a.device_tick),
+                           device_loop=bool(a.device_loop))
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     wall = time.perf_counter() - t0
     m = fleet.gather_summaries(res, res["n_all"], device=torch.device("cuda", local))
-    names, _, _, _ = fleet._sweep_instances(("flat", "tilted_5", "tilted_10", "tilted_15", "actuation_uncertainty"),
-                                            a.seeds)
+    names, _, _, _ = fleet._sweep_instances(tuple(a.scenarios), a.seeds)
     if rank == 0:
-        line = {"config": "5 scenarios x %d seeds closed loop, %.1f s each" % (a.seeds, a.time), "ranks": world,
+        line = {"config": "%d scenarios x %d seeds closed loop, %.1f s each" % (len(a.scenarios), a.seeds, a.time),
+                "ranks": world, "device_loop": int(a.device_loop), "loop_wall_s": res["wall_s"],
                 "neg_step_rule": a.neg_step_rule, "variant": a.variant,
                 "device_tick": int(a.device_tick or a.variant == "ff"),
                 "instances": int(res["n_all"]), "ticks": res["ticks"], "wall_s": wall,
