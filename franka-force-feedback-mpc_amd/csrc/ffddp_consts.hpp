@@ -12,6 +12,10 @@
 
 namespace ffddp {
 
+// Key word 1 of the device injector's Philox4x64-10 stream (ffddp_inject.hpp;
+// "FFDDPINJ"), mirrored by ffddp/uncertainty.py PHILOX_TAG.
+constexpr uint64_t INJECT_PHILOX_TAG = 0x4646444450494e4aull;
+
 inline void fill_consts(const ffddp_robot& rb, const ffddp_ocp_config& c, DevConsts& k) {
   std::memset(&k, 0, sizeof(k));
   k.rb = rb;

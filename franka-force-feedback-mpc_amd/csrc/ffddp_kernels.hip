@@ -42,6 +42,7 @@
 
 #include "ffddp_consts.hpp"
 #include "ffddp_group.hpp"
+#include "ffddp_inject.hpp"
 #include "ffddp_plant.hpp"
 #include "ffddp_primal_g8.hpp"
 #include "ffddp_rollout.hpp"
@@ -4305,6 +4306,61 @@ int ffddp_fleet_post_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, co
   hipLaunchKernelGGL(k_fleet_post, dim3(B, FLEET_CHUNKS), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->hc.N, h->hc.nx,
                      *p, *s, xs, us, K, cost, iters, ok, fn_pred, stats, x0, surface, tau_bias, (long)ld_tau_bias,
                      tau_cmd, info, scale, tau_app, tau_filt, lpf, obs, (long)ld_obs, log_obs);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// the uncertainty injector around the tick (ffddp_inject.hpp)
+static int fleet_inject_check(ffddp_handle* h, int B, const ffddp_fleet_inject* inj, int k, const char* who) {
+  if (B <= 0 || k < 0) return fail(h, FFDDP_E_INVALID, std::string(who) + ": B must be positive and k >= 0");
+  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  if (!inj || !inj->row || !inj->a || !inj->b || !inj->obs_ring || !inj->cmd_ring || !inj->tau_hat_filt || !inj->z_cmd)
+    return fail(h, FFDDP_E_INVALID, std::string(who) + ": null pointer");
+  if (inj->d_obs < 0 || inj->d_cmd < 0 || inj->rows < 0)
+    return fail(h, FFDDP_E_INVALID, std::string(who) + ": a delay below 0");
+  if (inj->noise != FFDDP_INJECT_NOISE_TABLE && inj->noise != FFDDP_INJECT_NOISE_PHILOX)
+    return fail(h, FFDDP_E_INVALID, std::string(who) + ": unknown noise mode");
+  return 0;
+}
+
+int ffddp_fleet_inject_obs_dev(ffddp_handle* h, int B, const ffddp_fleet_inject* inj, int k, const double* z,
+                               const double* q, const double* v, int ld_qv, const double* tau_filt, double* qv_ctrl,
+                               double* tau_hat, double* tau_ctrl, void* stream) {
+  if (!h) return FFDDP_E_INVALID;
+  if (int rc = fleet_inject_check(h, B, inj, k, "ffddp_fleet_inject_obs_dev")) return rc;
+  if (!q || !v || !qv_ctrl || (inj->noise == FFDDP_INJECT_NOISE_TABLE ? (inj->rows > 0 && !z) : !inj->seed))
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_inject_obs_dev: null pointer");
+  if (ld_qv < NQ) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_inject_obs_dev: bad stride");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int nb = (int)(((long)B * NU + INJECT_BLOCK - 1) / INJECT_BLOCK);
+  hipLaunchKernelGGL(k_fleet_inject_obs, dim3(nb), dim3(INJECT_BLOCK), 0, (hipStream_t)stream, B, *inj, k, z, q, v,
+                     (long)ld_qv, tau_filt, qv_ctrl, tau_hat, tau_ctrl);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int ffddp_fleet_inject_cmd_dev(ffddp_handle* h, int B, const ffddp_fleet_inject* inj, int k, const double* tau_cmd,
+                               double* tau_app, void* stream) {
+  if (!h) return FFDDP_E_INVALID;
+  if (int rc = fleet_inject_check(h, B, inj, k, "ffddp_fleet_inject_cmd_dev")) return rc;
+  if (!tau_cmd || !tau_app) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_inject_cmd_dev: null pointer");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int nb = (int)(((long)B * NU + INJECT_BLOCK - 1) / INJECT_BLOCK);
+  hipLaunchKernelGGL(k_fleet_inject_cmd, dim3(nb), dim3(INJECT_BLOCK), 0, (hipStream_t)stream, B, *inj, k, tau_cmd,
+                     tau_app);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int ffddp_fleet_noise_dev(ffddp_handle* h, int B, const uint64_t* seed, int k, double* z, uint64_t* words,
+                          void* stream) {
+  if (!h) return FFDDP_E_INVALID;
+  if (B <= 0 || k < 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_noise_dev: B must be positive and k >= 0");
+  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  if (!seed || !z) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_noise_dev: null pointer");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int nb = (int)(((long)B * NU + INJECT_BLOCK - 1) / INJECT_BLOCK);
+  hipLaunchKernelGGL(k_fleet_noise, dim3(nb), dim3(INJECT_BLOCK), 0, (hipStream_t)stream, B, seed, k, z, words);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

@@ -50,6 +50,9 @@ SYMBOLS = (
     "ffddp_fleet_keep_dev",
     "ffddp_fleet_pre_dev",
     "ffddp_fleet_post_dev",
+    "ffddp_fleet_inject_obs_dev",
+    "ffddp_fleet_inject_cmd_dev",
+    "ffddp_fleet_noise_dev",
 )
 PLANT_OBS = 69
 NSTATS = 10
@@ -76,6 +79,27 @@ class FleetState(C.Structure):
 
     _fields_ = [(n, C.c_void_p) for n in ("valid", "latched", "loss_count", "prev_mode", "tau_prev", "keep_xs",
                                           "keep_us", "keep_K")]
+
+
+INJECT_NOISE_TABLE = 0
+INJECT_NOISE_PHILOX = 1
+INJECT_NOISE_MODES = {"numpy": INJECT_NOISE_TABLE, "philox": INJECT_NOISE_PHILOX}
+INJECT_NZ = 28  # normals per instance and tick: q, dq, tau (observation), tau (command)
+
+
+class FleetInject(C.Structure):
+    """ffddp_fleet_inject: the device uncertainty injector's scalars and device pointers."""
+
+    _fields_ = [
+        ("d_obs", C.c_int32),
+        ("d_cmd", C.c_int32),
+        ("noise", C.c_int32),
+        ("rows", C.c_int32),
+        ("sigma_q", C.c_double),
+        ("sigma_dq", C.c_double),
+        ("sigma_tau", C.c_double),
+        ("lpf", C.c_double),
+    ] + [(n, C.c_void_p) for n in ("row", "a", "b", "seed", "obs_ring", "cmd_ring", "tau_hat_filt", "z_cmd")]
 
 
 class FleetParams(C.Structure):
@@ -391,6 +415,13 @@ def load() -> C.CDLL:
     lib.ffddp_fleet_post_dev.argtypes = (fl + [vp] * 8 + [vp, vp, vp, C.c_int, vp, vp] + [vp, vp, vp, C.c_double]
                                          + [vp, C.c_int, vp] + [vp])
     lib.ffddp_fleet_post_dev.restype = C.c_int
+    fi = [C.c_void_p, C.c_int, C.POINTER(FleetInject), C.c_int]
+    lib.ffddp_fleet_inject_obs_dev.argtypes = fi + [vp, vp, vp, C.c_int, vp, vp, vp, vp] + [vp]
+    lib.ffddp_fleet_inject_obs_dev.restype = C.c_int
+    lib.ffddp_fleet_inject_cmd_dev.argtypes = fi + [vp, vp] + [vp]
+    lib.ffddp_fleet_inject_cmd_dev.restype = C.c_int
+    lib.ffddp_fleet_noise_dev.argtypes = [C.c_void_p, C.c_int, vp, C.c_int, vp, vp] + [vp]
+    lib.ffddp_fleet_noise_dev.restype = C.c_int
     _lib = lib
     return lib
 

@@ -27,8 +27,8 @@ scenario from the keyframe with a fixed seed, so this is a sweep around its
 configuration rather than a replay of it.  Ranks (torch.distributed) take
 contiguous shards of the instances; the per-instance summary metrics are
 all-gathered at the end (RCCL on the GPU box).  ``run_sweep(device_loop=True)``
-runs the loop itself on the device (fleet_loop.DeviceFleetLoop) for the
-scenarios without an injector.
+runs the loop itself on the device (fleet_loop.DeviceFleetLoop); the injector
+runs there too once ``device_noise`` names the source of its normals.
 """
 from __future__ import annotations
 
@@ -455,7 +455,7 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
               seeds: int = 256, total_time: float = 4.0, rank: int = 0, world: int = 1, device: int = 0,
               q_sigma: float = 0.02, verbose: bool = True, record: Sequence[int] = (),
               neg_step_rule: int = 0, variant: str = "classical", device_tick: bool = False,
-              device_loop: bool = False) -> dict:
+              device_loop: bool = False, device_noise: Optional[str] = None) -> dict:
     """Closed-loop sweep of len(scenarios) * seeds instances; this rank runs
     its contiguous shard.  Returns per-instance summary arrays (this shard).
     record: shard-local instance indices whose controller inputs (the plant
@@ -475,17 +475,28 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     ticks on the device.
     device_loop: run the whole closed loop on the device (fleet_loop.
     DeviceFleetLoop: no host synchronisation per tick, the logs come down once
-    at the end) and build the same summary from them.  Not for scenarios with
-    an uncertainty injector nor with ``record`` (NotImplementedError);
-    ``controller_s`` is None, the ticks are not timed apart."""
+    at the end) and build the same summary from them.  Not with ``record``
+    (NotImplementedError); ``controller_s`` is None, the ticks are not timed
+    apart.
+    device_noise (with device_loop): where the device injector's normals come
+    from -- "numpy": a table drawn ahead from the instances' Generators, the
+    host path's perturbations exactly; "philox": generated on the device, no
+    table (another stream).  The summary then also carries ``inject_a`` /
+    ``inject_b`` (the injectors' gain and bias, NaN without one).  None: a
+    scenario with an injector is refused (NotImplementedError)."""
     variant = str(variant).strip().lower()
     if variant not in ("classical", "ff"):
         raise ValueError(f"run_sweep: unknown variant {variant!r}")
+    if device_noise is not None:
+        if device_noise not in ("numpy", "philox"):
+            raise ValueError(f"run_sweep: unknown device_noise {device_noise!r} (numpy or philox)")
+        if not device_loop:
+            raise ValueError("run_sweep: device_noise needs device_loop=True")
     if device_loop:
         injected = [s for s in scenarios if config_for_scenario(str(s), seed=0) is not None]
-        if injected:
+        if injected and device_noise is None:
             raise NotImplementedError(f"run_sweep(device_loop=True): the uncertainty injector of {injected} "
-                                      "does not run on the device")
+                                      "runs on the device only with device_noise=\"numpy\" or \"philox\"")
         if len(record):
             raise NotImplementedError("run_sweep(device_loop=True): record is not supported")
     names, tilt, scale, seed = _sweep_instances(scenarios, seeds)
@@ -510,8 +521,11 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     nominal.close()
     q0 = np.stack([R.Q_NEUTRAL + np.random.default_rng(int(s)).normal(0.0, q_sigma, 7) for s in seed])
     if device_loop:
+        ucfgs = None
+        if device_noise is not None:  # per instance, as the host path below
+            ucfgs = [config_for_scenario(str(names[b]), seed=int(seed[b])) for b in range(B)]
         out = _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, (R_site_from_pin_ee, p_off), total_time,
-                                neg_step_rule, device, t_cp, verbose)
+                                neg_step_rule, device, t_cp, verbose, ucfgs, device_noise)
         out.update(names=names, seed=seed, shard=(lo, hi), n_all=n_all)
         return out
     plant = BatchedPlant(B, timestep=0.001, n_substeps=5, device=device)
@@ -628,7 +642,7 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
 
 
 def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, total_time, neg_step_rule, device, t_cp,
-                      verbose) -> dict:
+                      verbose, ucfgs=None, noise=None) -> dict:
     """run_sweep's loop on the device (fleet_loop.DeviceFleetLoop) and the
     host path's summary from the downloaded logs."""
     import torch
@@ -642,7 +656,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     cfg = make_cfg(dt, z_contact, neg_step_rule=neg_step_rule)
     steps = int(total_time / dt)
     loop = DeviceFleetLoop(variant, B, traj, cfg, q0, tilt_deg=tilt, torque_scale=scale, device=device, steps=steps,
-                           calibration=calibration, timestep=timestep, n_substeps=n_substeps)
+                           calibration=calibration, timestep=timestep, n_substeps=n_substeps, uncertainty=ucfgs,
+                           noise=noise or "numpy")
     wall0 = time.perf_counter()
     loop.run(steps)
     torch.cuda.synchronize(loop.dev)
@@ -671,7 +686,10 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     per_inst["unstable_ticks"] = (r["unstable"] != 0).sum(0).astype(float)
     per_inst["neg_accepted_ticks"] = (r["neg_accepted"] > 0).sum(0).astype(float)
     per_inst["solve_not_ok_ticks"] = (r["ok"] == 0).sum(0).astype(float)
-    return dict(per_instance=per_inst, ticks=steps, wall_s=wall, controller_s=None, instances=B, variant=variant)
+    out = dict(per_instance=per_inst, ticks=steps, wall_s=wall, controller_s=None, instances=B, variant=variant)
+    if ucfgs is not None:
+        out.update(inject_a=r["inject_a"], inject_b=r["inject_b"])
+    return out
 
 
 SUMMARY_KEYS = ("rms_tangential_error", "rms_tangential_error_contact_phase", "rms_3d_error", "avg_abs_force_err",

@@ -1,15 +1,26 @@
 """The fleet closed loop on the device: B plants and B MPC controllers stepped
 together with the host only enqueuing.
 
-``DeviceFleetLoop`` is ``run_sweep``'s loop (fleet.py) for the scenarios
-without an uncertainty injector, with everything a tick does kept in HBM: per
-tick it enqueues the plant step (ffddp_plant_step_dev), the controllers' work
-before the solve (ffddp_fleet_pre_dev: surface latch, mode-switch drop,
-references with the device gravity torque, warm start), the batched solve, and
-their work after it (ffddp_fleet_post_dev: keep, torque policy, unstable
-fallback, clip, the plant-side actuation and the tick's log rows).  No host
-synchronisation and no host<->device copy happens inside ``run``; the logs come
-down once in ``results``.
+``DeviceFleetLoop`` is ``run_sweep``'s loop (fleet.py) with everything a tick
+does kept in HBM: per tick it enqueues the plant step (ffddp_plant_step_dev),
+the controllers' work before the solve (ffddp_fleet_pre_dev: surface latch,
+mode-switch drop, references with the device gravity torque, warm start), the
+batched solve, and their work after it (ffddp_fleet_post_dev: keep, torque
+policy, unstable fallback, clip, the plant-side actuation and the tick's log
+rows).  No host synchronisation and no host<->device copy happens inside
+``run``; the logs come down once in ``results``.
+
+With ``uncertainty`` the ``actuation_uncertainty`` scenario's injector runs in
+the loop as two more launches per tick: ffddp_fleet_inject_obs_dev after the
+plant step (delayed, noisy observations and the noisy torque measurement into
+controller-side buffers that pre then reads instead of the plant's records)
+and ffddp_fleet_inject_cmd_dev after post (the applied torque becomes a *
+(delayed command) + b + noise).  Instances with and without an injector share
+one fleet.  The arithmetic is BatchedUncertaintyInjector's bit for bit; the
+normals come either from a table drawn ahead from the instances' numpy
+Generators (``noise="numpy"``: the host sweep's perturbations exactly,
+224 bytes per instance and tick) or from Philox4x64-10 on the device
+(``noise="philox"``: no table, another stream; uncertainty.philox_normals).
 
 The node references and the contact hint of every tick depend on the time
 only, so they are tabulated on the host before the run (``reference_table``,
@@ -19,14 +30,14 @@ fleets' bit for bit.  Per instance the loop computes what ``FleetClassicalMPC``
 summation inside the policy's dot products and the device (rather than host)
 evaluation of the gravity torque reference.
 
-Not on the device, and so not supported here: the uncertainty injector
-(``actuation_uncertainty``), ``run_sweep``'s ``record``, and any per-tick host
-callback; ``tick()`` lets a caller look between ticks at the price of its own
+Not on the device, and so not supported here: ``run_sweep``'s ``record`` and
+any per-tick host callback; ``tick()`` lets a caller look between ticks at the price of its own
 synchronisation.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+import dataclasses
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -34,6 +45,7 @@ from . import _abi
 from . import robot as R
 from .controller import ff_filter_alpha
 from .fleet import Traj, fleet_ocp_config, node_ref, site_calibration
+from .uncertainty import UncertaintyProfileConfig, delay_steps, draw_gain_bias, predraw
 
 LPF_ALPHA = 0.2  # PandaTablePlant's tau_meas_lpf_alpha: the ff sweep's torque measurement filter
 
@@ -85,6 +97,7 @@ def fleet_params(cfg, variant: str, dt_ocp: float) -> _abi.FleetParams:
 
 STATE_KEYS = ("valid", "latched", "loss_count", "prev_mode", "tau_prev", "keep_xs", "keep_us", "keep_K")
 _PLANT_KEYS = ("q", "v", "obs", "tau_app", "tau_filt")
+_INJECT_KEYS = ("obs_ring", "cmd_ring", "tau_hat_filt", "z_cmd")  # the injector's state (ffddp_fleet_inject)
 
 
 class DeviceFleetLoop:
@@ -98,17 +111,35 @@ class DeviceFleetLoop:
     the loop will run (sizes the reference table and the logs); calibration:
     (R_site_from_pin_ee, p_site_minus_frame_pin), by default taken from the
     nominal plant at the "neutral" keyframe as run_sweep does.
+    uncertainty: None, or one Optional[UncertaintyProfileConfig] per instance
+    (None: no injector); the configs may differ by seed only.  noise: where
+    the injector's normals come from, "numpy" (uncertainty.predraw's table of
+    `steps` ticks, uploaded once; at most max_table_bytes) or "philox".
 
     ``S``: the controller state, ``T``: the solve's arrays, ``P``: the plant's
-    (q, v, obs, tau_app, tau_filt, plane) -- all device tensors.
+    (q, v, obs, tau_app, tau_filt, plane), ``J``: the injector's (row, a, b,
+    seed, the rings, the filter, qv_ctrl, tau_hat, tau_ctrl; with
+    ``uncertainty`` only) -- all device tensors.
     """
 
     def __init__(self, variant: str, B: int, traj_fn: Traj, config, q0, tilt_deg=0.0, torque_scale=1.0,
                  device: int = 0, steps: int = 800, calibration: Optional[tuple] = None, t0: float = 0.0,
-                 timestep: float = 0.001, n_substeps: int = 5):
+                 timestep: float = 0.001, n_substeps: int = 5,
+                 uncertainty: Optional[Sequence[Optional[UncertaintyProfileConfig]]] = None, noise: str = "numpy",
+                 max_table_bytes: int = 1 << 30):
         variant = str(variant).strip().lower()
         if variant not in ("classical", "ff"):
             raise ValueError(f"DeviceFleetLoop: unknown variant {variant!r}")
+        if noise not in _abi.INJECT_NOISE_MODES:
+            raise ValueError(f"DeviceFleetLoop: unknown noise source {noise!r} (numpy or philox)")
+        ucfgs = None
+        if uncertainty is not None:
+            ucfgs = list(uncertainty)
+            if len(ucfgs) != int(B):
+                raise ValueError("DeviceFleetLoop: uncertainty takes one entry (a config or None) per instance")
+            given = [c for c in ucfgs if c is not None]
+            if any(dataclasses.replace(c, seed=0) != dataclasses.replace(given[0], seed=0) for c in given):
+                raise ValueError("DeviceFleetLoop: the uncertainty configs may differ by seed only")
         cfg = config
         if int(cfg.mpc_update_steps) != 1 or bool(cfg.apply_command_filter):
             raise NotImplementedError("DeviceFleetLoop supports the benchmark setup: mpc_update_steps=1, no filter")
@@ -162,6 +193,11 @@ class DeviceFleetLoop:
             scale=up(np.broadcast_to(np.asarray(torque_scale, float), (B, 7))), **self.S)
         if variant == "ff":
             self.T.update(tau_hat=self.P["tau_filt"], tau_filt=self.P["tau_filt"])
+        self.J = self.inject = self.inject_a = self.inject_b = None
+        if ucfgs is not None:
+            self.inject_a, self.inject_b = np.full(B, np.nan), np.full(B, np.nan)
+            if any(c is not None for c in ucfgs):  # else the plain loop
+                self._init_inject(ucfgs, noise, max_table_bytes)
         self.ref_table = up(self.refs)
         self.log_info = torch.full((self.steps, B, _abi.FLEET_INFO_W), float("nan"), **f64)
         self.log_obs = torch.full((self.steps + 1, B, _abi.FLEET_LOG_W), float("nan"), **f64)
@@ -176,6 +212,39 @@ class DeviceFleetLoop:
         self._plant_step(integrate=False)
         self._stepped = True  # obs already is tick k's observation
         torch.cuda.synchronize(self.dev)
+
+    def _init_inject(self, ucfgs, noise: str, max_table_bytes: int):
+        """The injector's arrays (``J``) and ffddp_fleet_inject; the controllers'
+        inputs q, v (and the ff tau_hat) become views of its outputs."""
+        torch, B = self.torch, self.B
+        z = lambda *s: torch.zeros(s, dtype=torch.float64, device=self.dev)  # noqa: E731
+        idx = [b for b, c in enumerate(ucfgs) if c is not None]
+        given = [ucfgs[b] for b in idx]
+        row = np.full(B, -1, np.int32)
+        row[idx] = np.arange(len(idx), dtype=np.int32)
+        c0 = given[0]
+        d_obs, d_cmd = delay_steps(c0, self.dt)
+        self.noise, self.z_table = noise, None
+        if noise == "numpy":
+            a, b, zt = predraw(given, self.steps, max_table_bytes=max_table_bytes)
+            self.z_table = torch.from_numpy(zt).to(self.dev)
+        else:
+            a, b, _ = draw_gain_bias(given)
+        self.inject_a[idx], self.inject_b[idx] = a, b
+        seed = np.array([int(c.seed) % (1 << 64) for c in given], dtype=np.uint64)
+        self.J = dict(row=torch.from_numpy(row).to(self.dev), a=torch.from_numpy(a).to(self.dev),
+                      b=torch.from_numpy(b).to(self.dev), seed=torch.from_numpy(seed.view(np.int64)).to(self.dev),
+                      obs_ring=z(d_obs + 1, B, 14), cmd_ring=z(d_cmd + 1, B, 7), tau_hat_filt=z(B, 7), z_cmd=z(B, 7),
+                      qv_ctrl=z(B, 14), tau_hat=z(B, 7), tau_ctrl=z(B, 7),
+                      q=self.P["obs"][:, 0:7], v=self.P["obs"][:, 7:14], tau_cmd=self.T["tau_cmd"],
+                      tau_app=self.P["tau_app"])
+        if self.variant == "ff":
+            self.J["tau_filt"] = self.P["tau_filt"]
+        self.inject = self.solver.fleet_inject(self.J, d_obs, d_cmd, (c0.sigma_q, c0.sigma_dq, c0.sigma_tau),
+                                               float(np.clip(LPF_ALPHA, 0.0, 1.0)), noise)
+        self.T.update(q=self.J["qv_ctrl"][:, 0:7], v=self.J["qv_ctrl"][:, 7:14])
+        if self.variant == "ff":
+            self.T["tau_hat"] = self.J["tau_ctrl"]
 
     def close(self):
         self.solver.close()
@@ -194,14 +263,20 @@ class DeviceFleetLoop:
         if not self._stepped:
             self._plant_step()
         T["node_ref1"], T["info"], T["log_obs"] = self.ref_table[k], self.log_info[k], self.log_obs[k]
+        if self.inject is not None:
+            self.solver.fleet_inject_obs_dev(self.J, self.inject, k, z=None if self.z_table is None else self.z_table[k],
+                                             stream=self._stream)
         self.solver.fleet_pre_dev(T, self.params, bool(self.hints[k]), stream=self._stream)
         self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream)
         self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream)
+        if self.inject is not None:
+            self.solver.fleet_inject_cmd_dev(self.J, self.inject, k, stream=self._stream)
         self._stepped = False
         self.k = k + 1
 
     def run(self, steps: int):
-        """Enqueue `steps` ticks: plant step, pre, solve, post.  Returns without waiting for the device."""
+        """Enqueue `steps` ticks: plant step, (inject_obs,) pre, solve, post(, inject_cmd).
+        Returns without waiting for the device."""
         for _ in range(int(steps)):
             self._enqueue_tick()
 
@@ -212,10 +287,13 @@ class DeviceFleetLoop:
 
     # -- state and logs -----------------------------------------------------------------
     def state(self) -> dict:
-        """Host copies of the controller state (STATE_KEYS), the plant state and the tick counter."""
+        """Host copies of the controller state (STATE_KEYS), the plant state, the
+        injector state (_INJECT_KEYS, with ``uncertainty``) and the tick counter."""
         self.torch.cuda.synchronize(self.dev)
         s = {k: self.S[k].cpu().numpy().copy() for k in STATE_KEYS}
         s.update({k: self.P[k].cpu().numpy().copy() for k in _PLANT_KEYS})
+        if self.J is not None:
+            s.update({k: self.J[k].cpu().numpy().copy() for k in _INJECT_KEYS})
         s.update(k=self.k, stepped=self._stepped)
         return s
 
@@ -226,6 +304,8 @@ class DeviceFleetLoop:
             self.S[k].copy_(torch.from_numpy(np.ascontiguousarray(s[k])).to(self.dev))
         for k in _PLANT_KEYS:
             self.P[k].copy_(torch.from_numpy(np.ascontiguousarray(s[k])).to(self.dev))
+        for k in _INJECT_KEYS if self.J is not None else ():
+            self.J[k].copy_(torch.from_numpy(np.ascontiguousarray(s[k])).to(self.dev))
         self.k, self._stepped = int(s["k"]), bool(s["stepped"])
         torch.cuda.synchronize(self.dev)
 
@@ -235,7 +315,9 @@ class DeviceFleetLoop:
         (k + 1, B, FLEET_LOG_W): row j is the plant record (site position,
         normal force, contact flag) tick j's controllers saw, the last row the
         one after the last command (the plant is stepped for it, once), ``t``
-        (k,) the ticks' times, ``plant_fail`` (B,) plant steps that failed."""
+        (k,) the ticks' times, ``plant_fail`` (B,) plant steps that failed; with
+        ``uncertainty`` also ``inject_a``, ``inject_b`` (B,): the injectors'
+        actuation gain and bias, NaN where there is none."""
         torch, k = self.torch, self.k
         if not self._stepped and k > 0:
             self._plant_step()
@@ -247,4 +329,6 @@ class DeviceFleetLoop:
                    plant_fail=self.log_fail[: k + 1].sum(0).cpu().numpy())
         for i, name in enumerate(_abi.FLEET_INFO_FIELDS):
             out[name] = info[:, :, i]
+        if self.inject_a is not None:
+            out.update(inject_a=self.inject_a.copy(), inject_b=self.inject_b.copy())
         return out

@@ -376,6 +376,76 @@ class BatchedBoxFDDP:
         )
         self._check(rc, "ffddp_fleet_post_dev")
 
+    # -- the uncertainty injector around the tick (include/ffddp.h: ffddp_fleet_inject_*_dev) --
+    @staticmethod
+    def fleet_inject(t, d_obs: int, d_cmd: int, sigma, lpf: float, noise: str) -> _abi.FleetInject:
+        """ffddp_fleet_inject from the delays (ticks), sigma = (sigma_q,
+        sigma_dq, sigma_tau), the measurement filter's alpha, the noise source
+        ("numpy": a pre-drawn table, "philox": generated on the device) and the
+        device tensors t["row"] (B,) int32, t["a"], t["b"] (rows,),
+        t["seed"] (rows,) uint64 bits (philox; else optional), t["obs_ring"]
+        (d_obs + 1, B, 14), t["cmd_ring"] (d_cmd + 1, B, 7), t["tau_hat_filt"],
+        t["z_cmd"] (B, 7).  The struct holds the pointers: keep the tensors alive."""
+        if noise not in _abi.INJECT_NOISE_MODES:
+            raise ValueError(f"fleet_inject: unknown noise source {noise!r} (numpy or philox)")
+        B = int(t["row"].shape[0])
+        assert tuple(t["obs_ring"].shape) == (int(d_obs) + 1, B, 14) and tuple(t["cmd_ring"].shape) == (int(d_cmd) + 1, B, 7)
+        assert t["a"].shape == t["b"].shape and (t.get("seed") is None or t["seed"].shape == t["a"].shape)
+        inj = _abi.FleetInject()
+        inj.d_obs, inj.d_cmd, inj.noise, inj.rows = int(d_obs), int(d_cmd), _abi.INJECT_NOISE_MODES[noise], int(t["a"].shape[0])
+        inj.sigma_q, inj.sigma_dq, inj.sigma_tau = (float(s) for s in sigma)
+        inj.lpf = float(lpf)
+        for k in ("row", "a", "b", "seed", "obs_ring", "cmd_ring", "tau_hat_filt", "z_cmd"):
+            assert t.get(k) is None or t[k].is_contiguous()
+            setattr(inj, k, int(t[k].data_ptr()) if t.get(k) is not None else 0)
+        return inj
+
+    def fleet_inject_obs_dev(self, t, inj: _abi.FleetInject, k: int, z=None, stream=None):
+        """Tick k's observation_for_controller for B instances in one launch,
+        enqueued after the plant step and before fleet_pre_dev.  t["q"], t["v"]
+        (B, 7): the plant's true state (strided views of its records); z
+        (rows, 28): tick k's row of uncertainty.predraw's table (numpy noise).
+        Writes t["qv_ctrl"] (B, 14), optionally t["tau_hat"] and t["tau_ctrl"]
+        (B, 7: the raw and the filtered torque measurement), and the injector
+        state in `inj`; instances with row -1 pass (q, v) and, when given,
+        t["tau_filt"] (B, 7) through.  Asynchronous on `stream`."""
+        B = int(t["qv_ctrl"].shape[0])
+        p = lambda k_: C.c_void_p(int(t[k_].data_ptr()) if t.get(k_) is not None else 0)
+        assert t["q"].stride(0) == t["v"].stride(0) and t["qv_ctrl"].is_contiguous()
+        assert z is None or (z.is_contiguous() and tuple(z.shape) == (inj.rows, _abi.INJECT_NZ))
+        rc = self._lib.ffddp_fleet_inject_obs_dev(
+            self._h, B, C.byref(inj), int(k), C.c_void_p(int(z.data_ptr()) if z is not None else 0), p("q"), p("v"),
+            int(t["q"].stride(0)), p("tau_filt"), p("qv_ctrl"), p("tau_hat"), p("tau_ctrl"),
+            C.c_void_p(stream if stream else 0),
+        )
+        self._check(rc, "ffddp_fleet_inject_obs_dev")
+
+    def fleet_inject_cmd_dev(self, t, inj: _abi.FleetInject, k: int, stream=None):
+        """Tick k's command_for_plant, enqueued after fleet_post_dev and before
+        the next plant step: t["tau_app"] (B, 7) of the injected instances
+        becomes a * (delayed t["tau_cmd"]) + b + noise; the others keep what
+        post wrote.  Asynchronous on `stream`."""
+        B = int(t["tau_cmd"].shape[0])
+        rc = self._lib.ffddp_fleet_inject_cmd_dev(
+            self._h, B, C.byref(inj), int(k), C.c_void_p(int(t["tau_cmd"].data_ptr())),
+            C.c_void_p(int(t["tau_app"].data_ptr())), C.c_void_p(stream if stream else 0),
+        )
+        self._check(rc, "ffddp_fleet_inject_cmd_dev")
+
+    def fleet_noise_dev(self, seed, k: int, z, words=None, stream=None):
+        """The device Philox source alone: z (B, 28) float64 <- tick k's normals
+        of the streams keyed by seed (B,) (uint64 bits in an int64 tensor), as
+        uncertainty.philox_normals; words (B, 7, 4) int64, optional, takes the
+        raw blocks.  Asynchronous on `stream`."""
+        B = int(seed.shape[0])
+        assert tuple(z.shape) == (B, _abi.INJECT_NZ) and z.is_contiguous() and seed.is_contiguous()
+        assert words is None or (tuple(words.shape) == (B, 7, 4) and words.is_contiguous())
+        rc = self._lib.ffddp_fleet_noise_dev(
+            self._h, B, C.c_void_p(int(seed.data_ptr())), int(k), C.c_void_p(int(z.data_ptr())),
+            C.c_void_p(int(words.data_ptr()) if words is not None else 0), C.c_void_p(stream if stream else 0),
+        )
+        self._check(rc, "ffddp_fleet_noise_dev")
+
     # -- device-side problem builder ----------------------------------------------
     def build_problem_dev(self, task, t, stream=None):
         """Fill t["node_ref"], t["inst_ref"], t["surface"] on the device from

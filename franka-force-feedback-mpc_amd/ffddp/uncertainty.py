@@ -192,3 +192,89 @@ class BatchedUncertaintyInjector:
         self._cmd[self._ci] = np.asarray(tau_cmd, float)
         self._ci = (self._ci + 1) % (self.cmd_delay_steps + 1)
         return self._tau_hat(self._z_tick[:, 3 * self.nu:])
+
+
+# -- the injector on the device (fleet_loop.DeviceFleetLoop, csrc/ffddp_inject.hpp) --------------
+NZ = 28  # normals per instance and tick: q, dq, tau (observation), tau (command), 7 each
+PHILOX_TAG = 0x4646444450494E4A  # key word 1 of the device noise stream (ffddp_consts.hpp INJECT_PHILOX_TAG)
+
+
+def delay_steps(config: UncertaintyProfileConfig, dt: float):
+    """(observation, command) delay in control steps of period dt, as the injectors round them."""
+    dt = float(max(dt, 1.0e-9))
+    d_obs = int(max(np.round(int(max(config.delta_obs_cycles, 0)) * 1.0e-3 / dt), 0))
+    d_cmd = int(max(np.round(float(config.delta_cmd_s) / dt), 0))
+    return d_obs, d_cmd
+
+
+def draw_gain_bias(configs):
+    """Each instance's actuation gain a and bias b (B,): the first two uniforms
+    of default_rng(seed), as the injectors draw them; also the Generators,
+    advanced past them."""
+    rngs = [np.random.default_rng(int(c.seed)) for c in configs]
+    ab = [(float(r.uniform(float(c.a_min), float(c.a_max))), float(r.uniform(float(c.b_min), float(c.b_max))))
+          for r, c in zip(rngs, configs)]
+    return np.array([x[0] for x in ab]), np.array([x[1] for x in ab]), rngs
+
+
+def predraw(configs, steps: int, max_table_bytes: int = 1 << 30):
+    """The noise of ``steps`` ticks of BatchedUncertaintyInjector(configs),
+    drawn ahead: a, b (B,) and z (steps, B, 28), row k of instance i being the
+    28 standard normals its default_rng(seed) stream gives tick k, in the host
+    class's order (q, dq, tau of the observation, tau of the command).  The
+    device loop's ``noise="numpy"`` uploads z once.  It takes 224 * steps * B
+    bytes (46 MB for the sweep's 256 instances x 800 ticks); above
+    max_table_bytes this raises ValueError: use noise="philox", which needs
+    no table."""
+    configs = list(configs)
+    steps = int(steps)
+    nbytes = 8 * NZ * steps * len(configs)
+    if nbytes > int(max_table_bytes):
+        raise ValueError(f"predraw: the noise table of {len(configs)} instances x {steps} ticks takes {nbytes} bytes, "
+                         f"above max_table_bytes = {int(max_table_bytes)}; use noise=\"philox\", which generates "
+                         "the normals on the device and needs no table")
+    a, b, rngs = draw_gain_bias(configs)
+    z = np.zeros((steps, len(configs), NZ))
+    for i, r in enumerate(rngs):  # a Generator's normals are one stream however many a call asks for
+        z[:, i] = r.standard_normal(steps * NZ).reshape(steps, NZ)
+    return a, b, z
+
+
+_PHILOX_M = (0xD2E7470EE14C6C93, 0xCA5A826395121157)
+_PHILOX_W = (0x9E3779B97F4A7C15, 0xBB67AE8584CAA73B)
+_M64 = (1 << 64) - 1
+
+
+def philox4x64_10(counter, key):
+    """One Philox4x64-10 block (Salmon et al. 2011) in Python integers: four 64-bit words."""
+    c0, c1, c2, c3 = (int(x) & _M64 for x in counter)
+    k0, k1 = (int(x) & _M64 for x in key)
+    for _ in range(10):
+        p0, p1 = _PHILOX_M[0] * c0, _PHILOX_M[1] * c2
+        c0, c1, c2, c3 = (p1 >> 64) ^ c1 ^ k0, p1 & _M64, (p0 >> 64) ^ c3 ^ k1, p0 & _M64
+        k0, k1 = (k0 + _PHILOX_W[0]) & _M64, (k1 + _PHILOX_W[1]) & _M64
+    return c0, c1, c2, c3
+
+
+def philox_normals(seeds, k: int, return_words: bool = False):
+    """The device loop's ``noise="philox"`` normals of tick k, restated in
+    numpy: z (B, 28) in the table's order.  Joint j of the instance seeded s
+    takes the block philox4x64_10([k + 1, j, 0, 0], [s, PHILOX_TAG]) -- the
+    first four words of numpy.random.Philox(key=[s, PHILOX_TAG], counter=[k, j,
+    0, 0]).random_raw(4), which increments the counter before it generates --
+    and Box-Muller on its pairs: u1 = ((w0 >> 11) + 1) 2^-53, u2 = (w1 >> 11)
+    2^-53, z0 = sqrt(-2 ln u1) cos(2 pi u2), z1 = sqrt(-2 ln u1) sin(2 pi u2);
+    (w0, w1) -> the joint's q and dq normals, (w2, w3) -> its two torque
+    normals (observation, command).  return_words: also the raw words
+    (B, 7, 4) uint64."""
+    seeds = [int(s) for s in np.asarray(seeds, dtype=object).reshape(-1)]
+    w = np.array([[philox4x64_10((int(k) + 1, j, 0, 0), (s, PHILOX_TAG)) for j in range(7)] for s in seeds],
+                 dtype=np.uint64).reshape(len(seeds), 7, 4)
+    u1 = ((w[..., 0::2] >> np.uint64(11)).astype(np.float64) + 1.0) * 2.0 ** -53
+    u2 = (w[..., 1::2] >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    r = np.sqrt(-2.0 * np.log(u1))
+    t = (2.0 * np.pi) * u2
+    zn = np.stack([r[..., 0] * np.cos(t[..., 0]), r[..., 0] * np.sin(t[..., 0]),
+                   r[..., 1] * np.cos(t[..., 1]), r[..., 1] * np.sin(t[..., 1])], 1)  # (B, 4, 7)
+    z = zn.reshape(len(seeds), NZ)
+    return (z, w) if return_words else z

@@ -442,6 +442,82 @@ int ffddp_fleet_post_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, co
                          double* tau_cmd, double* info, const double* scale, double* tau_app, double* tau_filt,
                          double lpf, const double* obs, int ld_obs, double* log_obs, void* stream);
 
+/* The closed-loop sweep's actuation-uncertainty injector on the device
+ * (ffddp/uncertainty.py BatchedUncertaintyInjector, bit for bit): two more
+ * launches per tick around the three above.  Tick k of an injected fleet is
+ *   plant step, ffddp_fleet_inject_obs_dev, ffddp_fleet_pre_dev, the solve,
+ *   ffddp_fleet_post_dev, ffddp_fleet_inject_cmd_dev
+ * on one stream.  The scalars travel by value; the arrays are caller-owned
+ * device memory.  row[b] >= 0 is instance b's row in a, b, seed and the noise
+ * table; row[b] = -1 marks an instance without an injector (both kinds share
+ * one fleet).  The rings, the filter and z_cmd are indexed by the instance.
+ * The ring slots are functions of the tick number k alone (no device-side
+ * counter): the observation ring is written at (k - 1) mod (d_obs + 1) and
+ * read at k mod (d_obs + 1), at k = 0 every slot takes the first observation;
+ * the command ring (zero before the first tick) is written at k mod
+ * (d_cmd + 1) and read at (k + 1) mod (d_cmd + 1).  The arithmetic is
+ * compiled without contraction in the host class's order and grouping, so the
+ * results are numpy's bits. */
+#define FFDDP_INJECT_NOISE_TABLE 0  /* the caller passes tick k's normals (uncertainty.predraw) */
+#define FFDDP_INJECT_NOISE_PHILOX 1 /* Philox4x64-10 and Box-Muller on the device, from seed */
+#define FFDDP_INJECT_NZ 28          /* normals per instance and tick: q, dq, tau (observation), tau (command) */
+typedef struct ffddp_fleet_inject {
+  int32_t d_obs;         /* observation delay in ticks (>= 0) */
+  int32_t d_cmd;         /* command delay in ticks (>= 0) */
+  int32_t noise;         /* FFDDP_INJECT_NOISE_* */
+  int32_t rows;          /* length of a / b / seed and of a tick's noise table; row[b] >= rows counts as -1 */
+  double sigma_q, sigma_dq, sigma_tau;
+  double lpf;            /* the torque measurement filter's alpha */
+  const int32_t* row;    /* [B] row in a / b / seed / z, or -1: no injector */
+  const double* a;       /* [rows] actuation gain */
+  const double* b;       /* [rows] actuation bias */
+  const uint64_t* seed;  /* [rows] Philox key word 0 (FFDDP_INJECT_NOISE_PHILOX only, else may be NULL) */
+  double* obs_ring;      /* [d_obs+1][B][14] delayed (q, dq) */
+  double* cmd_ring;      /* [d_cmd+1][B][7] delayed commands */
+  double* tau_hat_filt;  /* [B][7] the filtered torque measurement (state) */
+  double* z_cmd;         /* [B][7] the command normals the obs kernel leaves for the cmd kernel */
+} ffddp_fleet_inject;
+
+/* ffddp_fleet_inject_obs_dev: BatchedUncertaintyInjector.observation_for_controller.
+ * q, v: rows of 7 with stride ld_qv (views of the plant's records).  z: tick
+ * k's normals [rows][FFDDP_INJECT_NZ] (table mode; ignored for Philox, may be
+ * NULL).  Per injected instance: push (q, v) into the ring, read the oldest
+ * slot, qv_ctrl[b] = old + (0.0 + sigma * z) (q then dq, [B][14]); tau_hat[b]
+ * = a cmd_ring[oldest] + b + (0.0 + sigma_tau z[14..20]); tau_hat_filt <-
+ * (1 - lpf) tau_hat_filt + lpf tau_hat; z_cmd[b] = z[21..27].  tau_hat
+ * ([B][7], the raw measurement) and tau_ctrl ([B][7], the controllers'
+ * measured torque: tau_hat_filt) are optional outputs.  row[b] = -1:
+ * qv_ctrl[b] is the plant's (q, v) unchanged and, when tau_filt ([B][7], the
+ * filter ffddp_fleet_post_dev maintains; may be NULL) is given, tau_hat[b] =
+ * tau_ctrl[b] = tau_filt[b].
+ *
+ * ffddp_fleet_inject_cmd_dev: command_for_plant.  Per injected instance:
+ * cmd_ring[k mod (d_cmd+1)][b] = tau_cmd[b], then tau_app[b] = a
+ * cmd_ring[(k+1) mod (d_cmd+1)][b] + b + (0.0 + sigma_tau z_cmd[b]); with
+ * row[b] = -1 tau_app[b] (ffddp_fleet_post_dev's scale * tau_cmd) is left.
+ *
+ * ffddp_fleet_noise_dev: the Philox source alone.  z [B][FFDDP_INJECT_NZ] for
+ * tick k from seed [B]; words ([B][7][4], may be NULL) the raw blocks.  Lane
+ * j of instance b evaluates philox4x64_10(counter = [k + 1, j, 0, 0], key =
+ * [seed_b, TAG]) with TAG = 0x4646444450494e4a ("FFDDPINJ"; INJECT_PHILOX_TAG
+ * of csrc/ffddp_consts.hpp) -- the first four words of numpy.random.
+ * Philox(key = ..., counter = [k, j, 0, 0]).random_raw(4), which increments
+ * the counter before it generates.  Box-Muller on pairs: u1 = ((w0 >> 11) + 1)
+ * 2^-53, u2 = (w1 >> 11) 2^-53, z0 = sqrt(-2 ln u1) cos(2 pi u2), z1 = sqrt(-2
+ * ln u1) sin(2 pi u2); (w0, w1) -> joint j's q and dq normals, (w2, w3) -> its
+ * two torque normals (observation, command).
+ *
+ * All three: device pointers, asynchronous on `stream`.  FFDDP_E_INVALID for
+ * a null handle, a null required pointer, a delay below 0, an unknown noise
+ * mode, a bad stride, k < 0 or B <= 0; FFDDP_E_CAPACITY for B > max_batch. */
+int ffddp_fleet_inject_obs_dev(ffddp_handle* h, int B, const ffddp_fleet_inject* inj, int k, const double* z,
+                               const double* q, const double* v, int ld_qv, const double* tau_filt, double* qv_ctrl,
+                               double* tau_hat, double* tau_ctrl, void* stream);
+int ffddp_fleet_inject_cmd_dev(ffddp_handle* h, int B, const ffddp_fleet_inject* inj, int k, const double* tau_cmd,
+                               double* tau_app, void* stream);
+int ffddp_fleet_noise_dev(ffddp_handle* h, int B, const uint64_t* seed, int k, double* z, uint64_t* words,
+                          void* stream);
+
 /* ---------------------------------------------------------------------------
  * Closed-loop plant stand-in: the MuJoCo plant of the
  * reference's closed loop, FrankaMujocoSim.step() in torque mode

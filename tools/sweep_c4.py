@@ -9,8 +9,9 @@ wall time, closed-loop ticks/s).
   python tools/sweep_c4.py [--seeds 256] [--time 4]            # 1 GPU
   python tools/sweep_c4.py --variant ff                        # force-feedback fleet
   python tools/sweep_c4.py --device-tick 1                     # classical, tick glue in HIP kernels
-  python tools/sweep_c4.py --device-loop 1 --scenarios flat tilted_5 tilted_10 tilted_15
-                                                               # the whole closed loop on the device
+  python tools/sweep_c4.py --device-loop 1 --device-noise numpy   # the whole closed loop on the device, the
+                                                               # injector's normals from a pre-drawn table
+  python tools/sweep_c4.py --device-loop 1 --device-noise philox  # ... or generated on the device
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/sweep_c4.py
 """
 import argparse
@@ -40,8 +41,11 @@ def main():
                     help="classical only: 1 runs the tick's glue through the library's fleet kernels "
                          "(the ff fleet always does)")
     ap.add_argument("--device-loop", type=int, choices=(0, 1), default=0,
-                    help="1 runs the whole closed loop on the device (DeviceFleetLoop); not for scenarios "
-                         "with an uncertainty injector (actuation_uncertainty)")
+                    help="1 runs the whole closed loop on the device (DeviceFleetLoop); scenarios with an "
+                         "uncertainty injector (actuation_uncertainty) need --device-noise")
+    ap.add_argument("--device-noise", choices=("numpy", "philox"), default=None,
+                    help="with --device-loop 1: run the uncertainty injector on the device, its normals from a "
+                         "table drawn ahead with numpy (the host loop's perturbations) or from Philox on the device")
     ap.add_argument("--scenarios", nargs="+", default=list(ALL_SCENARIOS), help="scenarios to sweep (default: all 5)")
     a = ap.parse_args()
     import torch
@@ -56,7 +60,7 @@ def main():
     t0 = time.perf_counter()
     res = fleet.run_sweep(scenarios=tuple(a.scenarios), seeds=a.seeds, total_time=a.time, rank=rank, world=world,
                            device=local, verbose=(rank == 0), neg_step_rule=a.neg_step_rule, variant=a.variant, device_tick=bool(a.device_tick),
-                           device_loop=bool(a.device_loop))
+                           device_loop=bool(a.device_loop), device_noise=a.device_noise)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -65,7 +69,7 @@ def main():
     names, _, _, _ = fleet._sweep_instances(tuple(a.scenarios), a.seeds)
     if rank == 0:
         line = {"config": "%d scenarios x %d seeds closed loop, %.1f s each" % (len(a.scenarios), a.seeds, a.time),
-                "ranks": world, "device_loop": int(a.device_loop), "loop_wall_s": res["wall_s"],
+                "ranks": world, "device_loop": int(a.device_loop), "device_noise": a.device_noise, "loop_wall_s": res["wall_s"],
                 "neg_step_rule": a.neg_step_rule, "variant": a.variant,
                 "device_tick": int(a.device_tick or a.variant == "ff"),
                 "instances": int(res["n_all"]), "ticks": res["ticks"], "wall_s": wall,
