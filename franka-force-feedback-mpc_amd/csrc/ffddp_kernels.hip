@@ -158,27 +158,67 @@ __device__ __forceinline__ long xcd_block(long b, long n) {
 // ---------------------------------------------------------------------------
 // xs_init / us_init may be d.xs / d.us (warm start in place, ffddp.h): not
 // __restrict__; each element is read and written by the same thread
-__global__ void k_init(const DevConsts* __restrict__ Cg, Dev d, const double* xs_init, const double* us_init,
-                       int is_feasible) {
+//
+// SEL (ffddp_solve_batch_sel_dev): `active` [B] selects the instances that
+// solve.  An unselected instance's rows of xs_init / us_init are not read and
+// its rows of xs / us / K / k not written; it starts done with no accepted
+// trial, so no later kernel visits it (k_commit skips it, k_finalize returns
+// on the mask).  The first active list is the selected instances in
+// ascending order: a chunk of INIT_BLOCK instances per block, its base the
+// number of selected instances before the chunk (counted by the block
+// itself), the order inside by ballot and popcount -- a function of the mask
+// alone, no atomic append.
+constexpr int INIT_BLOCK = 256;
+template <bool SEL>
+__global__ __launch_bounds__(INIT_BLOCK) void k_init(const DevConsts* __restrict__ Cg, Dev d, const double* xs_init,
+                                                     const double* us_init, int is_feasible,
+                                                     const uint8_t* __restrict__ active) {
   const DevConsts& C = *Cg;
   const int N = C.N, nx = C.nx;
+  if constexpr (SEL) {
+    __shared__ int red[INIT_BLOCK / 64], wcnt[INIT_BLOCK / 64];
+    const int w = threadIdx.x / 64, l = threadIdx.x % 64;
+    for (int c0 = (int)blockIdx.x * INIT_BLOCK; c0 < d.B; c0 += (int)gridDim.x * INIT_BLOCK) {
+      int n = 0;  // selected instances before the chunk
+      for (int i = threadIdx.x; i < c0; i += INIT_BLOCK) n += active[i] != 0;
+      for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+      const int b = c0 + (int)threadIdx.x;
+      const bool sel = b < d.B && active[b] != 0;
+      const unsigned long long m = __ballot(sel);
+      if (l == 0) {
+        red[w] = n;
+        wcnt[w] = __popcll(m);
+      }
+      __syncthreads();
+      int base = 0, tot = 0;
+      for (int j = 0; j < INIT_BLOCK / 64; ++j) {
+        base += red[j] + (j < w ? wcnt[j] : 0);
+        tot += wcnt[j];
+      }
+      if (sel) d.alist[base + __popcll(m & ((1ull << l) - 1ull))] = b;
+      if (threadIdx.x == 0 && c0 + INIT_BLOCK >= d.B) d.acnt[0] = base + tot;  // the last chunk
+      __syncthreads();
+    }
+  }
   const long nX = (long)d.B * (N + 1) * nx;
   const long nU = (long)d.B * N * NU;
   const long nK = (long)d.B * N * NU * nx;
   const long nT = d.trace ? (long)d.B * d.trace_it * FFDDP_TRACE_W : 0;
+  const long perX = (long)(N + 1) * nx, perU = (long)N * NU, perK = perU * nx;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nK || i < nT; i += (long)gridDim.x * blockDim.x) {
     if (i < nT) d.trace[i] = __builtin_nan("");
     if (i >= nK) continue;
-    if (i < nX) d.xs[i] = xs_init[i];
-    if (i < nU) {
+    // SEL: the flat index is another instance's in each array
+    if (i < nX && (!SEL || active[i / perX] != 0)) d.xs[i] = xs_init[i];
+    if (i < nU && (!SEL || active[i / perU] != 0)) {
       d.us[i] = us_init[i];
       d.k[i] = 0.0;
     }
-    d.K[i] = 0.0;
+    if (!SEL || active[i / perK] != 0) d.K[i] = 0.0;
     if (i < d.B) {
-      d.alist[i] = (int)i;
+      if (!SEL) d.alist[i] = (int)i;
       if (i == 0) {
-        d.acnt[0] = d.B;
+        if (!SEL) d.acnt[0] = d.B;
         d.acnt[1] = 0;
         d.acnt[2] = 0;
         d.acnt[3] = 0;
@@ -190,7 +230,7 @@ __global__ void k_init(const DevConsts* __restrict__ Cg, Dev d, const double* xs
       s.stop = __builtin_nan("");
       s.is_feasible = is_feasible;
       s.was_feasible = 0;
-      s.done = 0;
+      s.done = (SEL && active[i] == 0) ? 1 : 0;
       s.ok = 0;
       s.iter = 0;
       s.recalc = 1;
@@ -2300,13 +2340,14 @@ template <int NC, bool FF>
 __global__ __launch_bounds__(64) void k_finalize(const DevConsts* __restrict__ Cg, Dev d, int maxiter, const double* __restrict__ x0,
                            const double* __restrict__ node_ref, const double* __restrict__ inst_ref,
                            const uint8_t* __restrict__ surface, double* cost, int32_t* iters, uint8_t* ok,
-                           double* fn_pred, int32_t* stats) {
+                           double* fn_pred, int32_t* stats, const uint8_t* __restrict__ active) {
   const DevConsts& C = *Cg;
   const int N = C.N;
   constexpr int nx = FF ? 21 : 14;
   const long gid = blockIdx.x * (long)blockDim.x + threadIdx.x;
   const int b = (int)(gid / 2), knot = (int)(gid % 2);
   if (b >= d.B) return;
+  if (active && active[b] == 0) return;  // not selected: its output rows stay as they are
   const InstState s = d.st[b];
   if (knot == 0) {
     cost[b] = s.cost;
@@ -2549,8 +2590,17 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_keep(
 // itself, so they are uniform; the state is rewritten by thread 0 after a
 // barrier, which is why the instance is not split over several blocks as in
 // k_fleet_warm_start (another block could read valid[b] after the rewrite).
+//
+// SCHED (ffddp_fleet_pre_sched_dev): the instance solves this tick (Q.need[b],
+// the solve's `active`) iff it has no warm start or its period has run out.
+// The kept solution is never moved between solves: Q.age[b] counts the
+// receding-horizon shifts since it was kept (_rollout_shift, pure copying), so
+// knot i of the shifted lists is knot min(i + age, N) of keep_xs and knot
+// min(i + age, N - 1) of keep_us / keep_K.  Only solving instances get a warm
+// start.  SCHED = false is ffddp_fleet_pre_dev's kernel, unchanged (Q unused).
+template <bool SCHED>
 __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_pre(
-    const ffddp_robot* __restrict__ rb, int N, int nx, ffddp_fleet_params P, ffddp_fleet_state S,
+    const ffddp_robot* __restrict__ rb, int N, int nx, ffddp_fleet_params P, ffddp_fleet_state S, ffddp_fleet_sched Q,
     const double* __restrict__ q, const double* __restrict__ v, const double* __restrict__ fn_meas,
     const double* __restrict__ contact, const double* __restrict__ ee_z, long ld, long ld1,
     const double* __restrict__ tau_hat, long ld_th, const double* __restrict__ q_nom, const double* __restrict__ node1, int hint,
@@ -2580,6 +2630,9 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_pre(
   // _phase: a mode switch drops the warm start
   const bool changed = pm >= 0 && (surf != (pm == 1));
   const bool warm = valid0 && !changed;
+  // _need_solve (since / age are written by the post kernel only)
+  const bool need = !SCHED || !warm || Q.since[b] + 1 >= Q.period;
+  const int age = SCHED ? (Q.age[b] < N ? Q.age[b] : N) : 0;  // every index below saturates at N
   __syncthreads();  // every wave holds the old state
   if (tid == 0) {
     S.valid[b] = warm ? 1 : 0;
@@ -2587,6 +2640,7 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_pre(
     S.loss_count[b] = cnt;
     S.prev_mode[b] = surf ? 1 : 0;
     surface[b] = surf ? 1 : 0;
+    if (SCHED) Q.need[b] = need ? 1 : 0;
   }
   const double *qb = q + b * ld, *vb = v + b * ld, *th = ff ? tau_hat + b * ld_th : nullptr, *qn = q_nom + b * NQ;
   auto x0at = [&](int j) -> double { return j < 7 ? qb[j] : (j < 14 ? vb[j - 7] : th[j - 14]); };
@@ -2608,11 +2662,23 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_pre(
   // _shift_guess, as k_fleet_warm_start
   const double* kx = S.keep_xs + b * nxs;
   double* xo = xs_init + b * nxs;
-  for (int i = tid; i < nxs; i += FLEET_BLOCK) xo[i] = (warm && i >= nx) ? kx[i] : x0at(i % nx);
   const double* ub = ff ? th : S.tau_prev + b * NU;
   const double* ku = S.keep_us + b * nus;
   double* uo = us_init + b * nus;
-  for (int i = tid; i < nus; i += FLEET_BLOCK) uo[i] = warm ? ku[i + NU < nus ? i + NU : i] : ub[i % NU];
+  if (!SCHED) {
+    for (int i = tid; i < nxs; i += FLEET_BLOCK) xo[i] = (warm && i >= nx) ? kx[i] : x0at(i % nx);
+    for (int i = tid; i < nus; i += FLEET_BLOCK) uo[i] = warm ? ku[i + NU < nus ? i + NU : i] : ub[i % NU];
+  } else if (need) {
+    // _shift_guess of the lists shifted `age` times: xs knot min(k + age, N), us knot min(k + 1 + age, N - 1)
+    for (int i = tid; i < nxs; i += FLEET_BLOCK) {
+      const int k = i / nx, j = i - k * nx, ks = k + age < N ? k + age : N;
+      xo[i] = (warm && k >= 1) ? kx[ks * nx + j] : x0at(j);
+    }
+    for (int i = tid; i < nus; i += FLEET_BLOCK) {
+      const int k = i / NU, j = i - k * NU, ks = k + 1 + age < N - 1 ? k + 1 + age : N - 1;
+      uo[i] = warm ? ku[ks * NU + j] : ub[j];
+    }
+  }
 }
 
 // max |x| over lanes 0..6 of the wave; a NaN propagates, as in np.max(np.abs(.))
@@ -2634,8 +2700,8 @@ __device__ __forceinline__ double fleet_absmax7(double x) {
 // 1041-1093) -> tau_des, then the inverse actuation map -> the return value.
 template <bool FF>
 __device__ __forceinline__ double fleet_policy_row(const ffddp_fleet_params& P, int i, bool valid, const double* ur,
-                                                   const double* xr, const double* Kr, const double* x0b,
-                                                   const double* tau_prev, double& tau_des) {
+                                                   const double* xr, const double* xr1, const double* Kr,
+                                                   const double* x0b, const double* tau_prev, double& tau_des) {
 #pragma clang fp contract(off)
   if (!FF) {
     double t = valid ? ur[i] : tau_prev[i];
@@ -2648,7 +2714,7 @@ __device__ __forceinline__ double fleet_policy_row(const ffddp_fleet_params& P, 
     return t;
   }
   const double eps = P.ff_use_tau_interpolation ? P.eps_pol : 0.0;
-  const double tau0 = xr[14 + i], tau1 = xr[21 + 14 + i], th = x0b[14 + i];
+  const double tau0 = xr[14 + i], tau1 = xr1[14 + i], th = x0b[14 + i];  // xr1: the knot after xr
   double tp = tau0 + eps * (tau1 - tau0);
   if (P.use_feedback_policy) {
     const double c = eps * (1.0 - P.alpha_ocp);
@@ -2666,11 +2732,24 @@ __device__ __forceinline__ double fleet_policy_row(const ffddp_fleet_params& P, 
   return t;
 }
 
+// np.clip(x, lo, hi): a NaN propagates
+__device__ __forceinline__ double fleet_clip(double x, double lo, double hi) {
+  return x != x ? x : fmin(fmax(x, lo), hi);
+}
+
 // Everything after the solve: k_fleet_keep's keep, then (wave 0 of the
 // instance's first block, lanes 0-6 = the seven joints) the policy, _command,
 // the info record, and the sweep's actuation and log columns when asked for.
+//
+// SCHED (ffddp_fleet_post_sched_dev): only the instances that solved this tick
+// (Q.need) can be kept; the policy reads the kept solution through Q.age (see
+// k_fleet_pre), _safe_tau's trust / rate / smoothing filter follows the clip
+// when Q.apply_filter, and the policy wave updates since / age last (the
+// instance's other blocks read only need).  SCHED = false is
+// ffddp_fleet_post_dev's kernel, unchanged (Q unused).
+template <bool SCHED>
 __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_post(
-    int N, int nx, ffddp_fleet_params P, ffddp_fleet_state S, const double* __restrict__ xs,
+    int N, int nx, ffddp_fleet_params P, ffddp_fleet_state S, ffddp_fleet_sched Q, const double* __restrict__ xs,
     const double* __restrict__ us, const double* __restrict__ K, const double* __restrict__ cost,
     const int32_t* __restrict__ iters, const uint8_t* __restrict__ ok, const double* __restrict__ fn_pred,
     const int32_t* __restrict__ stats, const double* __restrict__ x0, const uint8_t* __restrict__ surface,
@@ -2684,7 +2763,9 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_post(
   double *xk = S.keep_xs + b * nxs, *uk = S.keep_us + b * nus, *Kk = S.keep_K + b * nK;
   const int lane = threadIdx.x & 63;
   const unsigned long long m = __ballot(lane < NU ? (isfinite(un[lane]) ? 1 : 0) : 1);
-  const bool fin = m == ~0ull;
+  // SCHED: an instance that did not solve keeps nothing (its us row is its last solve's)
+  const bool need = !SCHED || Q.need[b] != 0;
+  const bool fin = need && m == ~0ull;
   if (fin) {
     for (int i = t0; i < nxs; i += step) xk[i] = xn[i];
     for (int i = t0; i < nus; i += step) uk[i] = un[i];
@@ -2693,6 +2774,17 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_post(
   if (blockIdx.y != 0 || threadIdx.x >= 64) return;
   // the kept first knot (when fin the new solution, read in place: the copy above is other waves' work)
   const double *xr = fin ? xn : xk, *ur = fin ? un : uk, *Kr = fin ? Kn : Kk;
+  const double* xr1 = xr + nx;
+  int age0 = 0;
+  if (SCHED) {
+    // knot 0 of the shifted lists: us / K knot min(age, N-1), xs knot min(age, N), the next xs knot min(age+1, N)
+    age0 = fin ? 0 : Q.age[b];
+    const int a = age0 < N ? age0 : N, au = a < N - 1 ? a : N - 1, a1 = a + 1 < N ? a + 1 : N;
+    xr1 = xr + (long)a1 * nx;
+    xr += (long)a * nx;
+    ur += (long)au * NU;
+    Kr += (long)au * NU * nx;
+  }
   const bool ff = nx == 21, on = lane < NU;
   const int i = on ? lane : 0;  // lanes 7.. repeat joint 0 and write nothing
   const bool valid = S.valid[b] != 0 || fin;
@@ -2700,8 +2792,8 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_post(
   double* tprev = S.tau_prev + b * NU;
   const bool surf = surface[b] != 0;
   double tau_des;
-  double traw = ff ? fleet_policy_row<true>(P, i, valid, ur, xr, Kr, x0b, tprev, tau_des)
-                   : fleet_policy_row<false>(P, i, valid, ur, xr, Kr, x0b, tprev, tau_des);
+  double traw = ff ? fleet_policy_row<true>(P, i, valid, ur, xr, xr1, Kr, x0b, tprev, tau_des)
+                   : fleet_policy_row<false>(P, i, valid, ur, xr, xr1, Kr, x0b, tprev, tau_des);
   const double tau_des_inf = ff ? fleet_absmax7(tau_des) : __builtin_nan("");
   // _command: unstable fallback (crocoddyl_classical.py:392-404), _safe_tau (:260-284)
   const double tau_raw_inf = fleet_absmax7(traw), cb = cost[b];
@@ -2713,6 +2805,12 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_post(
     const bool bad = __ballot(on && !isfinite(traw)) != 0;
     const double lim = P.tau_limits[i], x = bad ? tprev[i] : traw;
     tc = x != x ? x : fmin(fmax(x, -lim), lim);
+    if (SCHED && Q.apply_filter) {  // _safe_tau's filter (crocoddyl_classical.py:272-284), its order and grouping
+      const double prev = tprev[i], al = Q.tau_smoothing_alpha, ms = Q.tau_rate_limit[i] * Q.dt;
+      double d = fleet_clip(tc - prev, -Q.tau_trust_inf, Q.tau_trust_inf);
+      d = fleet_clip(d, -ms, ms);
+      tc = fleet_clip((1.0 - al) * prev + al * (prev + d), -lim, lim);
+    }
   }
   const double tau_cmd_inf = fleet_absmax7(tc);
   if (on) {
@@ -2737,7 +2835,7 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_post(
   f[4] = unstable ? 1.0 : 0.0;
   f[5] = surf ? 1.0 : 0.0;
   f[6] = valid ? 0.0 : -1.0;
-  f[7] = (double)stats[b * FFDDP_NSTATS + 9];
+  f[7] = need ? (double)stats[b * FFDDP_NSTATS + 9] : 0.0;
   f[8] = tau_raw_inf;
   f[9] = tau_cmd_inf;
   f[10] = tau_des_inf;
@@ -2754,6 +2852,10 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_post(
     fp = (surf && isfinite(fnx)) ? fnx : __builtin_nan("");
   }
   f[11] = fp;
+  if (SCHED) {  // last: since / age belong to this lane
+    Q.since[b] = need ? 0 : Q.since[b] + 1;
+    Q.age[b] = need ? age0 : age0 + 1;
+  }
 }
 
 }  // namespace
@@ -3057,7 +3159,7 @@ template <int NC, bool FF>
 int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref, const double* iref,
                  const uint8_t* surf, const double* xs_init, const double* us_init, int maxiter, int is_feasible,
                  double* xs, double* us, double* K, double* cost, int32_t* iters, uint8_t* ok, double* fn_pred,
-                 int32_t* stats, hipStream_t s, HostIO* io) {
+                 int32_t* stats, hipStream_t s, HostIO* io, const uint8_t* active) {
   const int N = h->hc.N, nx = h->hc.nx;
   int S = h->nstreams;
   if (B < 64 * S) S = 1;
@@ -3129,8 +3231,12 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
   auto enqueue_init = [&](int k) {
     ProfScope p(h, sl[k].s, KC_INIT);
     const long b0 = sl[k].b0;
-    hipLaunchKernelGGL(k_init, dim3(1024), dim3(256), 0, sl[k].s, h->dc, sl[k].d, xs_init + b0 * N1 * nxl,
-                       us_init + b0 * (long)N * NU, is_feasible);
+    if (active)
+      hipLaunchKernelGGL(k_init<true>, dim3(1024), dim3(INIT_BLOCK), 0, sl[k].s, h->dc, sl[k].d,
+                         xs_init + b0 * N1 * nxl, us_init + b0 * (long)N * NU, is_feasible, active + b0);
+    else
+      hipLaunchKernelGGL(k_init<false>, dim3(1024), dim3(INIT_BLOCK), 0, sl[k].s, h->dc, sl[k].d,
+                         xs_init + b0 * N1 * nxl, us_init + b0 * (long)N * NU, is_feasible, nullptr);
   };
   // one FDDP iteration of slice k: node stage, backward pass, line search, step decision
   auto enqueue_iter = [&](int k, int it) -> int {
@@ -3264,7 +3370,8 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
       ProfScope p(h, ss, KC_FINALIZE);
       hipLaunchKernelGGL((k_finalize<NC, FF>), dim3((2 * Bk + 63) / 64), dim3(64), 0, ss, h->dc, d, maxiter,
                          x0 + b0 * nxl, nref + b0 * N1 * 6, iref + b0 * 21, surf + b0, cost + b0, iters + b0, ok + b0,
-                         fn_pred ? fn_pred + 2 * b0 : nullptr, stats ? stats + b0 * FFDDP_NSTATS : nullptr);
+                         fn_pred ? fn_pred + 2 * b0 : nullptr, stats ? stats + b0 * FFDDP_NSTATS : nullptr,
+                         active ? active + b0 : nullptr);
     }
     // host entry point: page-locked host memory, the slice's results go
     // down as soon as it finishes (the device entry point solved in place)
@@ -3327,11 +3434,11 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
 int launch_solve(ffddp_handle* h, int B, const double* x0, const double* nref, const double* iref,
                  const uint8_t* surf, const double* xs_init, const double* us_init, int maxiter, int is_feasible,
                  double* xs, double* us, double* K, double* cost, int32_t* iters, uint8_t* ok, double* fn_pred,
-                 int32_t* stats, hipStream_t s, HostIO* io = nullptr) {
+                 int32_t* stats, hipStream_t s, HostIO* io = nullptr, const uint8_t* active = nullptr) {
   const bool ff = h->hc.variant == FFDDP_FORCE_FEEDBACK;
   const int nc = h->hc.nc;
 #define FFDDP_LS(NC_, FF_) \
-  launch_solve_t<NC_, FF_>(h, B, x0, nref, iref, surf, xs_init, us_init, maxiter, is_feasible, xs, us, K, cost, iters, ok, fn_pred, stats, s, io)
+  launch_solve_t<NC_, FF_>(h, B, x0, nref, iref, surf, xs_init, us_init, maxiter, is_feasible, xs, us, K, cost, iters, ok, fn_pred, stats, s, io, active)
   if (nc == 1) return ff ? FFDDP_LS(1, true) : FFDDP_LS(1, false);
   return ff ? FFDDP_LS(3, true) : FFDDP_LS(3, false);
 #undef FFDDP_LS
@@ -3597,10 +3704,11 @@ static int mark_solve_done(ffddp_handle* h, hipStream_t s) {
   return 0;
 }
 
-int ffddp_solve_batch_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref, const double* inst_ref,
-                          const uint8_t* surface, const double* xs_init, const double* us_init, int maxiter,
-                          int is_feasible, double* xs, double* us, double* K, double* cost, int32_t* iters,
-                          uint8_t* ok, double* fn_pred, int32_t* stats, void* stream) {
+int ffddp_solve_batch_sel_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                              const double* inst_ref, const uint8_t* surface, const double* xs_init,
+                              const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
+                              double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
+                              const uint8_t* active, void* stream) {
   if (!h) return FFDDP_E_INVALID;
   if (B < 0 || maxiter < 0) return fail(h, FFDDP_E_INVALID, "negative B or maxiter");
   if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
@@ -3612,9 +3720,17 @@ int ffddp_solve_batch_dev(ffddp_handle* h, int B, const double* x0, const double
   // another (possibly non-blocking) stream must finish before this one starts
   if (h->last_done_set) HIPCHK(h, hipStreamWaitEvent((hipStream_t)stream, h->last_done, 0));
   const int rc = launch_solve(h, B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs, us,
-                              K, cost, iters, ok, fn_pred, stats, (hipStream_t)stream);
+                              K, cost, iters, ok, fn_pred, stats, (hipStream_t)stream, nullptr, active);
   if (rc) return rc;
   return mark_solve_done(h, (hipStream_t)stream);
+}
+
+int ffddp_solve_batch_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref, const double* inst_ref,
+                          const uint8_t* surface, const double* xs_init, const double* us_init, int maxiter,
+                          int is_feasible, double* xs, double* us, double* K, double* cost, int32_t* iters,
+                          uint8_t* ok, double* fn_pred, int32_t* stats, void* stream) {
+  return ffddp_solve_batch_sel_dev(h, B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs,
+                                   us, K, cost, iters, ok, fn_pred, stats, nullptr, stream);
 }
 
 // error exit of the host entry point after its first asynchronous copy: the
@@ -4115,7 +4231,7 @@ int ffddp_calc_diff(ffddp_handle* h, int B, const double* x0, const double* node
   HIPCHK(h, hipMemcpy(h->in_xs, xs, (size_t)B * (N + 1) * nx * 8, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->in_us, us, (size_t)B * N * NU * 8, hipMemcpyHostToDevice));
   // node kernel reads (xs, us) from the solver state: initialise it from the inputs
-  hipLaunchKernelGGL(k_init, dim3(1024), dim3(256), 0, nullptr, h->dc, d, h->in_xs, h->in_us, 0);
+  hipLaunchKernelGGL(k_init<false>, dim3(1024), dim3(INIT_BLOCK), 0, nullptr, h->dc, d, h->in_xs, h->in_us, 0, nullptr);
   if (h->hc.nc == 1)
     ff ? launch_node<1, true>(h, d, B, nullptr, 1) : launch_node<1, false>(h, d, B, nullptr, 1);
   else
@@ -4281,8 +4397,8 @@ int ffddp_fleet_pre_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, con
       p->torque_mode > 2 || p->posture_mode < 0 || p->posture_mode > 1)
     return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_dev: bad stride or mode");
   HIPCHK(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(k_fleet_pre, dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx, *p, *s,
-                     q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar, tau_hat, (long)ld_tau_hat, q_nom, node_ref1,
+  hipLaunchKernelGGL(k_fleet_pre<false>, dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx, *p, *s,
+                     ffddp_fleet_sched{}, q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar, tau_hat, (long)ld_tau_hat, q_nom, node_ref1,
                      contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init);
   HIPCHK(h, hipGetLastError());
   return 0;
@@ -4303,8 +4419,66 @@ int ffddp_fleet_post_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, co
   if (ld_tau_bias < NU || (log_obs && (!obs || ld_obs < FFDDP_PLANT_OBS)) || (tau_filt && !tau_app))
     return fail(h, FFDDP_E_INVALID, "ffddp_fleet_post_dev: bad stride or optional arguments");
   HIPCHK(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(k_fleet_post, dim3(B, FLEET_CHUNKS), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->hc.N, h->hc.nx,
-                     *p, *s, xs, us, K, cost, iters, ok, fn_pred, stats, x0, surface, tau_bias, (long)ld_tau_bias,
+  hipLaunchKernelGGL(k_fleet_post<false>, dim3(B, FLEET_CHUNKS), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->hc.N, h->hc.nx,
+                     *p, *s, ffddp_fleet_sched{}, xs, us, K, cost, iters, ok, fn_pred, stats, x0, surface, tau_bias, (long)ld_tau_bias,
+                     tau_cmd, info, scale, tau_app, tau_filt, lpf, obs, (long)ld_obs, log_obs);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// the scheduled tick: the same checks, then the SCHED instantiations
+static int fleet_sched_check(ffddp_handle* h, const ffddp_fleet_sched& c, const char* who) {
+  if (!c.since || !c.age || !c.need) return fail(h, FFDDP_E_INVALID, std::string(who) + ": null pointer");
+  if (c.period < 1) return fail(h, FFDDP_E_INVALID, std::string(who) + ": period must be at least 1");
+  if (c.apply_filter && !(c.tau_smoothing_alpha >= 0.0 && c.tau_smoothing_alpha <= 1.0))
+    return fail(h, FFDDP_E_INVALID, std::string(who) + ": tau_smoothing_alpha outside [0, 1]");
+  return 0;
+}
+
+int ffddp_fleet_pre_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                              const double* q, const double* v, const double* fn_meas, const double* contact,
+                              const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
+                              const double* q_nom, const double* node_ref1, int contact_hint, double* x0,
+                              uint8_t* surface, double* inst_ref, double* node_ref, double* xs_init, double* us_init,
+                              ffddp_fleet_sched sched, void* stream) {
+  if (!h) return FFDDP_E_INVALID;
+  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_sched_dev: B must be positive");
+  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  const bool ff = h->hc.nx == 21;
+  if (!p || !s || !fleet_state_complete(s) || !q || !v || !fn_meas || !ee_z || (ff && !tau_hat) || !q_nom ||
+      !node_ref1 || !x0 || !surface || !inst_ref || !node_ref || !xs_init || !us_init)
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_sched_dev: null pointer");
+  if (ld_qv < NQ || ld_scalar < 1 || (ff && ld_tau_hat < NU) || p->phase_source < 0 || p->phase_source > 1 || p->torque_mode < 0 ||
+      p->torque_mode > 2 || p->posture_mode < 0 || p->posture_mode > 1)
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_sched_dev: bad stride or mode");
+  if (const int rc = fleet_sched_check(h, sched, "ffddp_fleet_pre_sched_dev")) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_fleet_pre<true>, dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx, *p, *s,
+                     sched, q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar, tau_hat, (long)ld_tau_hat, q_nom,
+                     node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int ffddp_fleet_post_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                               const double* xs, const double* us, const double* K, const double* cost,
+                               const int32_t* iters, const uint8_t* ok, const double* fn_pred, const int32_t* stats,
+                               const double* x0, const uint8_t* surface, const double* tau_bias, int ld_tau_bias,
+                               double* tau_cmd, double* info, const double* scale, double* tau_app, double* tau_filt,
+                               double lpf, const double* obs, int ld_obs, double* log_obs, ffddp_fleet_sched sched,
+                               void* stream) {
+  if (!h) return FFDDP_E_INVALID;
+  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_post_sched_dev: B must be positive");
+  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  if (!p || !s || !fleet_state_complete(s) || !xs || !us || !K || !cost || !iters || !ok || !fn_pred || !stats ||
+      !x0 || !surface || !tau_bias || !tau_cmd || !info)
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_post_sched_dev: null pointer");
+  if (ld_tau_bias < NU || (log_obs && (!obs || ld_obs < FFDDP_PLANT_OBS)) || (tau_filt && !tau_app))
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_post_sched_dev: bad stride or optional arguments");
+  if (const int rc = fleet_sched_check(h, sched, "ffddp_fleet_post_sched_dev")) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_fleet_post<true>, dim3(B, FLEET_CHUNKS), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->hc.N, h->hc.nx,
+                     *p, *s, sched, xs, us, K, cost, iters, ok, fn_pred, stats, x0, surface, tau_bias, (long)ld_tau_bias,
                      tau_cmd, info, scale, tau_app, tau_filt, lpf, obs, (long)ld_obs, log_obs);
   HIPCHK(h, hipGetLastError());
   return 0;

@@ -26,6 +26,7 @@ SYMBOLS = (
     "ffddp_last_error",
     "ffddp_solve_batch",
     "ffddp_solve_batch_dev",
+    "ffddp_solve_batch_sel_dev",
     "ffddp_calc_diff",
     "ffddp_frame_placement",
     "ffddp_gravity_torque",
@@ -50,6 +51,8 @@ SYMBOLS = (
     "ffddp_fleet_keep_dev",
     "ffddp_fleet_pre_dev",
     "ffddp_fleet_post_dev",
+    "ffddp_fleet_pre_sched_dev",
+    "ffddp_fleet_post_sched_dev",
     "ffddp_fleet_inject_obs_dev",
     "ffddp_fleet_inject_cmd_dev",
     "ffddp_fleet_noise_dev",
@@ -79,6 +82,33 @@ class FleetState(C.Structure):
 
     _fields_ = [(n, C.c_void_p) for n in ("valid", "latched", "loss_count", "prev_mode", "tau_prev", "keep_xs",
                                           "keep_us", "keep_K")]
+
+
+class FleetSched(C.Structure):
+    """ffddp_fleet_sched: the scheduled tick's period, command filter and per-instance counters (device pointers)."""
+
+    _fields_ = [
+        ("period", C.c_int32),
+        ("apply_filter", C.c_int32),
+        ("tau_trust_inf", C.c_double),
+        ("tau_smoothing_alpha", C.c_double),
+        ("dt", C.c_double),
+        ("tau_rate_limit", C.c_double * 7),
+        ("since", C.c_void_p),
+        ("age", C.c_void_p),
+        ("need", C.c_void_p),
+    ]
+
+
+def fleet_sched(cfg, period: int, dt: float) -> FleetSched:
+    """ffddp_fleet_sched's scalars from a controller configuration (the pointers are left null)."""
+    s = FleetSched()
+    s.period, s.apply_filter = int(period), int(bool(cfg.apply_command_filter))
+    s.tau_trust_inf = float(cfg.tau_trust_inf)
+    s.tau_smoothing_alpha = float(np.clip(cfg.tau_smoothing_alpha, 0.0, 1.0))
+    s.dt = float(dt)
+    s.tau_rate_limit[:] = [float(x) for x in np.asarray(cfg.tau_rate_limit, float).reshape(7)]
+    return s
 
 
 INJECT_NOISE_TABLE = 0
@@ -363,6 +393,8 @@ def load() -> C.CDLL:
     dev_args = [C.c_void_p, C.c_int] + [vp] * 6 + [C.c_int, C.c_int] + [vp] * 8 + [vp]
     lib.ffddp_solve_batch_dev.argtypes = dev_args
     lib.ffddp_solve_batch_dev.restype = C.c_int
+    lib.ffddp_solve_batch_sel_dev.argtypes = dev_args[:-1] + [vp, vp]  # ..., stats, active, stream
+    lib.ffddp_solve_batch_sel_dev.restype = C.c_int
     lib.ffddp_calc_diff.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, up, dp, dp] + [dp] * 10
     lib.ffddp_calc_diff.restype = C.c_int
     lib.ffddp_frame_placement.argtypes = [C.POINTER(Robot), dp, dp, dp]
@@ -415,6 +447,11 @@ def load() -> C.CDLL:
     lib.ffddp_fleet_post_dev.argtypes = (fl + [vp] * 8 + [vp, vp, vp, C.c_int, vp, vp] + [vp, vp, vp, C.c_double]
                                          + [vp, C.c_int, vp] + [vp])
     lib.ffddp_fleet_post_dev.restype = C.c_int
+    # the scheduled tick: the same arguments, then ffddp_fleet_sched by value before the stream
+    lib.ffddp_fleet_pre_sched_dev.argtypes = lib.ffddp_fleet_pre_dev.argtypes[:-1] + [FleetSched, vp]
+    lib.ffddp_fleet_pre_sched_dev.restype = C.c_int
+    lib.ffddp_fleet_post_sched_dev.argtypes = lib.ffddp_fleet_post_dev.argtypes[:-1] + [FleetSched, vp]
+    lib.ffddp_fleet_post_sched_dev.restype = C.c_int
     fi = [C.c_void_p, C.c_int, C.POINTER(FleetInject), C.c_int]
     lib.ffddp_fleet_inject_obs_dev.argtypes = fi + [vp, vp, vp, C.c_int, vp, vp, vp, vp] + [vp]
     lib.ffddp_fleet_inject_obs_dev.restype = C.c_int

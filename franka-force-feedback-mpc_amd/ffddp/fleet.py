@@ -7,8 +7,18 @@ logic of ``ClassicalCrocoddylMPC.compute_control`` (crocoddyl_classical.py:
 305-440, our B = 1 mirror in controller.py) in arrays, and runs ONE batched
 device solve per control tick for all B instances (warm starts, problem
 references and results stay in HBM; only x0, the shared node references and
-the first knot of the solution cross PCIe).  Supported configuration: the
-benchmark one (solve every tick, ``mpc_update_steps = 1``; no command filter).
+the first knot of the solution cross PCIe).  With ``mpc_update_steps = P > 1``
+an instance solves on every P-th tick, or at once when it has no plan (a mode
+switch, an unstable tick or a non-finite solve dropped it), and runs the
+feedback policy on the receding plan in between; the batched solve then takes
+the tick's ``solved_now`` mask (``solve_dev(active=...)``).  The kept solution
+is never moved between solves: ``age`` counts the controllers' _rollout_shift
+calls since it was kept and every reader indexes through it (knot i of the
+shifted lists is knot min(i + age, N - 1) of keep_us / keep_K, min(i + age, N)
+of keep_xs), the convention of the device tick (include/ffddp.h,
+ffddp_fleet_sched), so the state can be copied between the two.
+``apply_command_filter`` is _safe_tau's filter, ``safe_tau_batch``.  At
+period 1 without the filter a tick's launches and results are unchanged.
 
 ``FleetForceFeedbackMPC`` is the same for ``ForceFeedbackCrocoddylMPC``
 (state y = (q, v, tau_hat), nx = 21; torque policy of Eq. 14-18 on the host).
@@ -87,6 +97,27 @@ def fleet_ocp_config(cfg, variant: str, N: int, dt_ocp: float, R_des) -> OcpConf
     return ocp
 
 
+def safe_tau_batch(target, prev, cfg, dt: float) -> np.ndarray:
+    """_safe_tau (crocoddyl_classical.py:260-284) for B rows at once, bit for
+    bit the scalar controller's: a row with a non-finite entry becomes the
+    previous command, the clip to tau_limits, and with apply_command_filter
+    the trust region, the rate limit (tau_rate_limit * dt) and the smoothing,
+    in its order and grouping.  target, prev (B, 7) -> the commands (B, 7),
+    which are also the next ``prev``."""
+    target = np.asarray(target, float)
+    prev = np.asarray(prev, float)
+    lim = np.asarray(cfg.tau_limits, float)
+    bad = ~np.all(np.isfinite(target), 1)
+    target = np.clip(np.where(bad[:, None], prev, target), -lim, lim)
+    if not bool(cfg.apply_command_filter):
+        return target
+    d = np.clip(target - prev, -cfg.tau_trust_inf, cfg.tau_trust_inf)
+    max_step = np.asarray(cfg.tau_rate_limit, float) * float(dt)
+    d = np.clip(d, -max_step, max_step)
+    a = float(np.clip(cfg.tau_smoothing_alpha, 0.0, 1.0))
+    return np.clip((1.0 - a) * prev + a * (prev + d), -lim, lim)
+
+
 class _FleetBase:
     """What the fleet controllers share: the solver and its device arrays, the
     kept solution and its ``valid`` mask, the surface latch, the problem
@@ -100,9 +131,11 @@ class _FleetBase:
         import torch
 
         cfg = config
-        if int(cfg.mpc_update_steps) != 1 or bool(cfg.apply_command_filter):
-            raise NotImplementedError(
-                f"{type(self).__name__} supports the benchmark setup: mpc_update_steps=1, no filter")
+        if int(cfg.mpc_update_steps) < 1:
+            raise ValueError(f"{type(self).__name__}: mpc_update_steps must be at least 1")
+        self.period = int(cfg.mpc_update_steps)
+        # the scheduled tick (_tick_sched); period 1 without the filter keeps the plain one
+        self.sched = self.period != 1 or bool(cfg.apply_command_filter)
         self.torch = torch
         self.B, self.cfg, self.traj_fn = int(B), cfg, traj_fn
         self.N = int(cfg.horizon)
@@ -135,6 +168,8 @@ class _FleetBase:
         self.latched = np.zeros(B, bool)
         self.loss_count = np.zeros(B, np.int64)
         self.prev_mode = np.full(B, -1, np.int8)
+        self.since = np.zeros(B, np.int32)  # ticks since the instance's last solve
+        self.age = np.zeros(B, np.int32)    # _rollout_shift calls since the kept solution was kept
         self._stream = torch.cuda.current_stream(self.dev).cuda_stream
         self._tk = None  # the device tick's arrays, made on its first use
         self.last_info = {}
@@ -217,6 +252,61 @@ class _FleetBase:
         self.valid |= r["fin"]
         return r
 
+    # -- the scheduled tick (mpc_update_steps > 1 or the command filter) ---------------
+    def _tick_sched(self, x0, inst_ref, u_cold, surface_now, t: float) -> dict:
+        """One tick in which only the instances that need it solve
+        (_need_solve: no kept solution, or the period has run out), as torch
+        indexing around solve_dev(active=need).  Returns _tick_device's record
+        -- the kept first knot read through ``age`` -- plus ``need``.  The
+        counters are advanced by _sched_advance once the command is out."""
+        torch, B, N, nx, T, dev = self.torch, self.B, self.N, self.nx, self.T, self.dev
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        need = (~self.valid) | (self.since.astype(np.int64) + 1 >= self.period)
+        T["x0"].copy_(up(x0))
+        T["inst_ref"].copy_(up(inst_ref))
+        T["surface"].copy_(up(np.asarray(surface_now).astype(np.uint8)))
+        T["node_ref"].copy_(up(self._node_ref(t))[None].expand(B, N + 1, 6))
+        # _shift_guess of the lists shifted `age` times; rows of instances that do not solve stay as they are
+        a_d = up(np.minimum(self.age, N).astype(np.int64))
+        valid_d, need_d = up(self.valid)[:, None, None], up(need.astype(np.uint8))
+        ix = torch.clamp(torch.arange(N + 1, device=dev)[None, :] + a_d[:, None], max=N)
+        xs_sh = torch.gather(self.keep_xs, 1, ix[:, :, None].expand(B, N + 1, nx))
+        xs_i = T["x0"][:, None, :].expand(B, N + 1, nx).clone()
+        xs_i[:, 1:] = torch.where(valid_d, xs_sh[:, 1:], xs_i[:, 1:])
+        iu = torch.clamp(torch.arange(N, device=dev)[None, :] + 1 + a_d[:, None], max=N - 1)
+        us_sh = torch.gather(self.keep_us, 1, iu[:, :, None].expand(B, N, 7))
+        us_i = torch.where(valid_d, us_sh, up(u_cold)[:, None, :].expand(B, N, 7))
+        nm = need_d.bool()
+        T["xs_init"].copy_(torch.where(nm[:, None, None], xs_i, T["xs_init"]))
+        T["us_init"].copy_(torch.where(nm[:, None, None], us_i, T["us_init"]))
+        self._need_d = need_d  # alive until the solve has run
+        self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream,
+                              active=need_d)
+        fin = nm & torch.isfinite(T["us"][:, 0]).all(1)
+        f3 = fin[:, None, None]
+        self.keep_xs.copy_(torch.where(f3, T["xs"], self.keep_xs))
+        self.keep_us.copy_(torch.where(f3, T["us"], self.keep_us))
+        self.keep_K.copy_(torch.where(fin[:, None, None, None], T["K"], self.keep_K))
+        fin_h = fin.cpu().numpy()
+        self.age = np.where(fin_h, 0, self.age).astype(np.int32)
+        self.valid |= fin_h
+        # knot 0 of the shifted lists
+        a = np.minimum(self.age, N).astype(np.int64)
+        ar = torch.arange(B, device=dev)
+        ku, kx, kx1 = up(np.minimum(a, N - 1)), up(a), up(np.minimum(a + 1, N))
+        h = lambda x: x.cpu().numpy()  # noqa: E731
+        stats9 = h(T["stats"][:, 9]).astype(np.int32)
+        return dict(need=need, fin=fin_h, us0=h(self.keep_us[ar, ku]), xs0=h(self.keep_xs[ar, kx]),
+                    xs1=h(self.keep_xs[ar, kx1]), K0=h(self.keep_K[ar, ku]), cost=h(T["cost"]).copy(),
+                    iters=h(T["iters"]).astype(np.int32), ok=h(T["ok"]) != 0, neg_acc=np.where(need, stats9, 0),
+                    fn0=h(T["fn_pred"][:, 0]), fn1=h(T["fn_pred"][:, 1]))
+
+    def _sched_advance(self, need):
+        """The end of a scheduled tick: ``since`` restarts for the instances
+        that solved; the others' plan recedes by one knot (_rollout_shift)."""
+        self.since = np.where(need, 0, self.since + 1).astype(np.int32)
+        self.age = np.where(need, self.age, self.age + 1).astype(np.int32)
+
     # -- per-tick pieces (crocoddyl_classical.py line refs as in controller.py) -------
     def _surface(self, fn_meas, ee_z, hint: bool) -> np.ndarray:
         """_surface_mode / _detect_surface (:286-303), vectorised."""
@@ -236,16 +326,14 @@ class _FleetBase:
 
     def _command(self, tau_raw, cost, v, tau_bias):
         """The unstable fallback (crocoddyl_classical.py:392-404) and _safe_tau
-        (:260-284) without the command filter -> tau_cmd, |tau_raw|inf, unstable."""
+        (:260-284, safe_tau_batch) -> tau_cmd, |tau_raw|inf, unstable."""
         cfg, B = self.cfg, self.B
         tau_raw_inf = np.max(np.abs(tau_raw), 1)
         unstable = (~np.isfinite(cost)) | (cost > float(cfg.max_solver_cost)) | (tau_raw_inf > float(cfg.max_tau_raw_inf))
         fallback = np.asarray(tau_bias, float).reshape(B, 7) - float(cfg.fallback_dq_damping) * v
         tau_raw = np.where(unstable[:, None], fallback, tau_raw)
         self.valid &= ~unstable
-        lim = np.asarray(cfg.tau_limits, float)
-        bad = ~np.all(np.isfinite(tau_raw), 1)
-        tau_cmd = np.clip(np.where(bad[:, None], self.tau_prev, tau_raw), -lim, lim)
+        tau_cmd = safe_tau_batch(tau_raw, self.tau_prev, cfg, float(cfg.dt))
         self.tau_prev = tau_cmd.copy()
         return tau_cmd, tau_raw_inf, unstable
 
@@ -259,7 +347,9 @@ class FleetClassicalMPC(_FleetBase):
     (crocoddyl_classical.py:199-226; one robot model, so shared).
     device_tick: run the tick's glue (warm start, keep, packing) through the
     library's two fleet kernels instead of torch operations; same results bit
-    for bit (tests/test_gpu_fleet_ff.py).  Off by default.
+    for bit (tests/test_gpu_fleet_ff.py).  Off by default.  A scheduled tick
+    (mpc_update_steps > 1 or apply_command_filter) is torch indexing around
+    the selected-instance solve on either path (_tick_sched).
     """
 
     variant = "classical"
@@ -323,7 +413,13 @@ class FleetClassicalMPC(_FleetBase):
         mode = str(cfg.posture_ref_mode).strip().lower()
         xreg = np.concatenate([self.q_nom, np.zeros((B, 7))], 1) if mode == "q_nom" else x0.copy()
         tref = self._tau_ref(q)
-        if self.device_tick:
+        need = np.ones(B, bool)
+        if self.sched:  # either glue path: the scheduled tick is torch indexing
+            r = self._tick_sched(x0, np.concatenate([xreg, tref], 1), self.tau_prev, surface_now, t)
+            need = r["need"]
+            us0, xs0, K0, cost, iters, ok, neg_acc, fn0 = (r[k] for k in ("us0", "xs0", "K0", "cost", "iters", "ok",
+                                                                         "neg_acc", "fn0"))
+        elif self.device_tick:
             r = self._tick_device(x0, np.concatenate([xreg, tref], 1), self.tau_prev, surface_now, t)
             us0, xs0, K0, cost, iters, ok, neg_acc, fn0 = (r[k] for k in ("us0", "xs0", "K0", "cost", "iters", "ok",
                                                                          "neg_acc", "fn0"))
@@ -342,8 +438,10 @@ class FleetClassicalMPC(_FleetBase):
         tau_cmd, tau_raw_inf, unstable = self._command(tau_raw, cost, v, tau_bias)
         self.last_info = dict(ok=ok, cost=cost, iters=iters, tau_raw_inf=tau_raw_inf,
                               tau_cmd_inf=np.max(np.abs(tau_cmd), 1), surface_mode=surface_now, unstable=unstable,
-                              fn_pred=fn_pred, solved_now=np.ones(B, bool), policy_idx=policy_idx,
+                              fn_pred=fn_pred, solved_now=need, policy_idx=policy_idx,
                               neg_accepted=neg_acc)
+        if self.sched:
+            self._sched_advance(need)
         return tau_cmd
 
 
@@ -385,7 +483,9 @@ class FleetForceFeedbackMPC(_FleetBase):
         else:
             xreg = np.concatenate([self.q_nom, np.zeros((B, 7))], 1)
         # cold start: w = y0[14:21] (_cold_control)
-        r = self._tick_device(y0, np.concatenate([xreg, self._tau_ref(q)], 1), tau_hat, surface_now, t)
+        tick = self._tick_sched if self.sched else self._tick_device
+        r = tick(y0, np.concatenate([xreg, self._tau_ref(q)], 1), tau_hat, surface_now, t)
+        need = r["need"] if self.sched else np.ones(B, bool)
         cost, xs0, xs1, K0 = r["cost"], r["xs0"], r["xs1"], r["K0"]
         dt_mpc = float(cfg.dt)
         alpha = ff_filter_alpha(cfg, self.dt_ocp)
@@ -423,8 +523,10 @@ class FleetForceFeedbackMPC(_FleetBase):
         tau_cmd, tau_raw_inf, unstable = self._command(tau_raw, cost, v, tau_bias)
         self.last_info = dict(ok=r["ok"], cost=cost, iters=r["iters"], tau_des_inf=tau_des_inf, tau_raw_inf=tau_raw_inf,
                               tau_cmd_inf=np.max(np.abs(tau_cmd), 1), surface_mode=surface_now, unstable=unstable,
-                              fn_pred=fn_pred_raw.copy(), fn_pred_raw=fn_pred_raw, solved_now=np.ones(B, bool),
+                              fn_pred=fn_pred_raw.copy(), fn_pred_raw=fn_pred_raw, solved_now=need,
                               policy_idx=policy_idx, neg_accepted=r["neg_acc"])
+        if self.sched:
+            self._sched_advance(need)
         return tau_cmd
 
 
@@ -455,7 +557,8 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
               seeds: int = 256, total_time: float = 4.0, rank: int = 0, world: int = 1, device: int = 0,
               q_sigma: float = 0.02, verbose: bool = True, record: Sequence[int] = (),
               neg_step_rule: int = 0, variant: str = "classical", device_tick: bool = False,
-              device_loop: bool = False, device_noise: Optional[str] = None) -> dict:
+              device_loop: bool = False, device_noise: Optional[str] = None, solve_period: int = 1,
+              command_filter: bool = False) -> dict:
     """Closed-loop sweep of len(scenarios) * seeds instances; this rank runs
     its contiguous shard.  Returns per-instance summary arrays (this shard).
     record: shard-local instance indices whose controller inputs (the plant
@@ -483,10 +586,20 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     host path's perturbations exactly; "philox": generated on the device, no
     table (another stream).  The summary then also carries ``inject_a`` /
     ``inject_b`` (the injectors' gain and bias, NaN without one).  None: a
-    scenario with an injector is refused (NotImplementedError)."""
+    scenario with an injector is refused (NotImplementedError).
+    solve_period, command_filter: the controllers' mpc_update_steps (solve
+    every solve_period-th tick, the feedback policy in between) and
+    apply_command_filter; on the host path they go into the configuration, on
+    the device path to the loop.  The summary's ``solved_ticks`` counts each
+    instance's ticks with a solve."""
     variant = str(variant).strip().lower()
     if variant not in ("classical", "ff"):
         raise ValueError(f"run_sweep: unknown variant {variant!r}")
+    if isinstance(solve_period, bool) or int(solve_period) != solve_period or int(solve_period) < 1:
+        raise ValueError(f"run_sweep: solve_period must be an integer >= 1, not {solve_period!r}")
+    if not isinstance(command_filter, (bool, np.bool_)) and command_filter not in (0, 1):
+        raise ValueError(f"run_sweep: command_filter must be a flag, not {command_filter!r}")
+    solve_period, command_filter = int(solve_period), bool(command_filter)
     if device_noise is not None:
         if device_noise not in ("numpy", "philox"):
             raise ValueError(f"run_sweep: unknown device_noise {device_noise!r} (numpy or philox)")
@@ -525,7 +638,8 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
         if device_noise is not None:  # per instance, as the host path below
             ucfgs = [config_for_scenario(str(names[b]), seed=int(seed[b])) for b in range(B)]
         out = _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, (R_site_from_pin_ee, p_off), total_time,
-                                neg_step_rule, device, t_cp, verbose, ucfgs, device_noise)
+                                neg_step_rule, device, t_cp, verbose, ucfgs, device_noise, solve_period,
+                                command_filter)
         out.update(names=names, seed=seed, shard=(lo, hi), n_all=n_all)
         return out
     plant = BatchedPlant(B, timestep=0.001, n_substeps=5, device=device)
@@ -536,10 +650,12 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     tau0 = plant.obs[:, 14:21].copy()
     if variant == "ff":
         cfg = ff_benchmark_config(plant.dt, z_contact, neg_step_rule=neg_step_rule)
+        cfg.mpc_update_steps, cfg.apply_command_filter = solve_period, command_filter
         mpc = FleetForceFeedbackMPC(B, traj, cfg, q_nom=q0, tau0=np.zeros((B, 7)),
                                     R_site_from_pin_ee=R_site_from_pin_ee, p_site_minus_frame_pin=p_off, device=device)
     else:
         cfg = classical_benchmark_config(plant.dt, z_contact, neg_step_rule=neg_step_rule)
+        cfg.mpc_update_steps, cfg.apply_command_filter = solve_period, command_filter
         mpc = FleetClassicalMPC(B, traj, cfg, q_nom=q0, tau0=tau0, R_site_from_pin_ee=R_site_from_pin_ee,
                                 p_site_minus_frame_pin=p_off, device=device, device_tick=device_tick)
     plant.set_tilt(tilt)  # hidden from the controllers
@@ -558,6 +674,7 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     unstable_ticks = np.zeros(B)
     neg_ticks = np.zeros(B)
     not_ok_ticks = np.zeros(B)
+    solved_ticks = np.zeros(B)
     rec_idx = [int(i) for i in record]
     rec_obs = np.zeros((steps, len(rec_idx), plant.obs.shape[1]))
     rec_tau = np.zeros((steps, len(rec_idx), 7))
@@ -595,6 +712,7 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
         unstable_ticks += mpc.last_info["unstable"]
         neg_ticks += mpc.last_info["neg_accepted"] > 0
         not_ok_ticks += ~mpc.last_info["ok"]
+        solved_ticks += mpc.last_info["solved_now"]
         if rec_idx:
             rec_t[k] = t
             rec_obs[k] = obs[rec_idx]
@@ -632,7 +750,7 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     per_inst["neg_accepted_ticks"] = neg_ticks
     per_inst["solve_not_ok_ticks"] = not_ok_ticks
     out = dict(names=names, seed=seed, per_instance=per_inst, ticks=steps, wall_s=wall, controller_s=ctrl_s,
-               instances=B, shard=(lo, hi), n_all=n_all, variant=variant)
+               instances=B, shard=(lo, hi), n_all=n_all, variant=variant, solved_ticks=solved_ticks)
     if rec_idx:
         out["record"] = dict(index=np.array(rec_idx), t=rec_t, obs=rec_obs, tau=rec_tau, q0=q0[rec_idx], traj=traj,
                              config=cfg, dt=plant.dt, calibration_obs=obs0)
@@ -642,7 +760,7 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
 
 
 def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, total_time, neg_step_rule, device, t_cp,
-                      verbose, ucfgs=None, noise=None) -> dict:
+                      verbose, ucfgs=None, noise=None, solve_period=1, command_filter=False) -> dict:
     """run_sweep's loop on the device (fleet_loop.DeviceFleetLoop) and the
     host path's summary from the downloaded logs."""
     import torch
@@ -654,10 +772,11 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     dt = float(timestep * n_substeps)  # BatchedPlant.dt
     make_cfg = ff_benchmark_config if variant == "ff" else classical_benchmark_config
     cfg = make_cfg(dt, z_contact, neg_step_rule=neg_step_rule)
+    cfg.apply_command_filter = bool(command_filter)
     steps = int(total_time / dt)
     loop = DeviceFleetLoop(variant, B, traj, cfg, q0, tilt_deg=tilt, torque_scale=scale, device=device, steps=steps,
                            calibration=calibration, timestep=timestep, n_substeps=n_substeps, uncertainty=ucfgs,
-                           noise=noise or "numpy")
+                           noise=noise or "numpy", solve_period=int(solve_period))
     wall0 = time.perf_counter()
     loop.run(steps)
     torch.cuda.synchronize(loop.dev)
@@ -686,7 +805,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     per_inst["unstable_ticks"] = (r["unstable"] != 0).sum(0).astype(float)
     per_inst["neg_accepted_ticks"] = (r["neg_accepted"] > 0).sum(0).astype(float)
     per_inst["solve_not_ok_ticks"] = (r["ok"] == 0).sum(0).astype(float)
-    out = dict(per_instance=per_inst, ticks=steps, wall_s=wall, controller_s=None, instances=B, variant=variant)
+    out = dict(per_instance=per_inst, ticks=steps, wall_s=wall, controller_s=None, instances=B, variant=variant,
+               solved_ticks=r["solved"].sum(0).astype(float))
     if ucfgs is not None:
         out.update(inject_a=r["inject_a"], inject_b=r["inject_b"])
     return out

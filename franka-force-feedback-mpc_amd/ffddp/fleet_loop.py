@@ -30,6 +30,15 @@ fleets' bit for bit.  Per instance the loop computes what ``FleetClassicalMPC``
 summation inside the policy's dot products and the device (rather than host)
 evaluation of the gravity torque reference.
 
+With ``solve_period = P > 1`` or ``apply_command_filter`` the tick is the
+scheduled one (include/ffddp.h, ffddp_fleet_sched): ffddp_fleet_pre_sched_dev
+decides on the device which instances solve (every P-th tick, or at once
+after a mode switch, an unstable tick or a non-finite solve), the solve takes
+that mask (ffddp_solve_batch_sel_dev), ffddp_fleet_post_sched_dev runs the
+policy on the receding plan of the others.  The mask of tick k is row k of a
+(steps, B) log, returned as ``solved``.  With period 1 and no filter the loop
+enqueues exactly the unscheduled calls.
+
 Not on the device, and so not supported here: ``run_sweep``'s ``record`` and
 any per-tick host callback; ``tick()`` lets a caller look between ticks at the price of its own
 synchronisation.
@@ -98,14 +107,39 @@ def fleet_params(cfg, variant: str, dt_ocp: float) -> _abi.FleetParams:
 STATE_KEYS = ("valid", "latched", "loss_count", "prev_mode", "tau_prev", "keep_xs", "keep_us", "keep_K")
 _PLANT_KEYS = ("q", "v", "obs", "tau_app", "tau_filt")
 _INJECT_KEYS = ("obs_ring", "cmd_ring", "tau_hat_filt", "z_cmd")  # the injector's state (ffddp_fleet_inject)
+# the scheduled tick's state: its counters (ffddp_fleet_sched) and the solve's output rows post reads for an
+# instance that does not solve (its last solve's cost, iters, ok, fn_pred: the controllers' _last_solve_*)
+_SCHED_KEYS = ("since", "age", "cost", "iters", "ok", "fn_pred")
+
+
+def resolve_solve_period(cfg, solve_period: Optional[int]) -> int:
+    """The loop's solve period from its ``solve_period`` argument and the
+    configuration.  None: the configuration must say 1 (NotImplementedError
+    otherwise: a period other than 1 is asked for through the argument).
+    P >= 1: the period; a configuration that names another one (neither 1 nor
+    P) contradicts it (ValueError).  Host only: needs no device."""
+    steps = int(cfg.mpc_update_steps)
+    if solve_period is None:
+        if steps != 1:
+            raise NotImplementedError("DeviceFleetLoop: mpc_update_steps other than 1 is selected with solve_period")
+        return 1
+    if isinstance(solve_period, bool) or int(solve_period) != solve_period or int(solve_period) < 1:
+        raise ValueError(f"DeviceFleetLoop: solve_period must be an integer >= 1, not {solve_period!r}")
+    P = int(solve_period)
+    if steps not in (1, P):
+        raise ValueError(f"DeviceFleetLoop: solve_period={P} contradicts the configuration's mpc_update_steps={steps}")
+    return P
 
 
 class DeviceFleetLoop:
     """B closed loops (plant + controller) resident on one device.
 
     variant: "classical" or "ff"; traj_fn: the task; config: the controller
-    configuration (the fleets' supported one: mpc_update_steps = 1, no command
-    filter); q0 (B, 7): start postures (also each instance's q_nom); tilt_deg,
+    configuration; solve_period: None (the configuration's mpc_update_steps
+    must be 1) or the period P >= 1 of the scheduled tick (a configuration
+    with mpc_update_steps other than 1 or P is a ValueError);
+    apply_command_filter is taken from the configuration; q0 (B, 7): start
+    postures (also each instance's q_nom); tilt_deg,
     torque_scale: per-instance table tilt (hidden from the controllers) and
     command scale, (B, 7) per joint (both broadcast); steps: the most ticks
     the loop will run (sizes the reference table and the logs); calibration:
@@ -119,14 +153,15 @@ class DeviceFleetLoop:
     ``S``: the controller state, ``T``: the solve's arrays, ``P``: the plant's
     (q, v, obs, tau_app, tau_filt, plane), ``J``: the injector's (row, a, b,
     seed, the rings, the filter, qv_ctrl, tau_hat, tau_ctrl; with
-    ``uncertainty`` only) -- all device tensors.
+    ``uncertainty`` only), ``Q``: the scheduled tick's counters (since, age)
+    -- all device tensors.
     """
 
     def __init__(self, variant: str, B: int, traj_fn: Traj, config, q0, tilt_deg=0.0, torque_scale=1.0,
                  device: int = 0, steps: int = 800, calibration: Optional[tuple] = None, t0: float = 0.0,
                  timestep: float = 0.001, n_substeps: int = 5,
                  uncertainty: Optional[Sequence[Optional[UncertaintyProfileConfig]]] = None, noise: str = "numpy",
-                 max_table_bytes: int = 1 << 30):
+                 max_table_bytes: int = 1 << 30, solve_period: Optional[int] = None):
         variant = str(variant).strip().lower()
         if variant not in ("classical", "ff"):
             raise ValueError(f"DeviceFleetLoop: unknown variant {variant!r}")
@@ -141,8 +176,7 @@ class DeviceFleetLoop:
             if any(dataclasses.replace(c, seed=0) != dataclasses.replace(given[0], seed=0) for c in given):
                 raise ValueError("DeviceFleetLoop: the uncertainty configs may differ by seed only")
         cfg = config
-        if int(cfg.mpc_update_steps) != 1 or bool(cfg.apply_command_filter):
-            raise NotImplementedError("DeviceFleetLoop supports the benchmark setup: mpc_update_steps=1, no filter")
+        self.period = resolve_solve_period(cfg, solve_period)
         import torch
 
         from .plant import BatchedPlant, PandaTablePlant, table_plane
@@ -198,6 +232,14 @@ class DeviceFleetLoop:
             self.inject_a, self.inject_b = np.full(B, np.nan), np.full(B, np.nan)
             if any(c is not None for c in ucfgs):  # else the plain loop
                 self._init_inject(ucfgs, noise, max_table_bytes)
+        # the scheduled tick: its counters, and one row of `need` per tick (the log `solved`)
+        self.Q = dict(since=z(B, dtype=torch.int32), age=z(B, dtype=torch.int32))
+        self.log_need = z(self.steps, B, dtype=torch.uint8)
+        self.sched = None
+        if self.period != 1 or bool(cfg.apply_command_filter):
+            self.sched = _abi.fleet_sched(cfg, self.period, self.dt)
+            self.T.update(self.Q)
+        self.Q.update({k: self.T[k] for k in ("cost", "iters", "ok", "fn_pred")})
         self.ref_table = up(self.refs)
         self.log_info = torch.full((self.steps, B, _abi.FLEET_INFO_W), float("nan"), **f64)
         self.log_obs = torch.full((self.steps + 1, B, _abi.FLEET_LOG_W), float("nan"), **f64)
@@ -266,16 +308,24 @@ class DeviceFleetLoop:
         if self.inject is not None:
             self.solver.fleet_inject_obs_dev(self.J, self.inject, k, z=None if self.z_table is None else self.z_table[k],
                                              stream=self._stream)
-        self.solver.fleet_pre_dev(T, self.params, bool(self.hints[k]), stream=self._stream)
-        self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream)
-        self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream)
+        if self.sched is None:
+            self.solver.fleet_pre_dev(T, self.params, bool(self.hints[k]), stream=self._stream)
+            self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream)
+            self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream)
+        else:
+            T["need"] = self.log_need[k]
+            self.solver.fleet_pre_dev(T, self.params, bool(self.hints[k]), stream=self._stream, sched=self.sched)
+            self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream,
+                                  active=T["need"])
+            self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream, sched=self.sched)
         if self.inject is not None:
             self.solver.fleet_inject_cmd_dev(self.J, self.inject, k, stream=self._stream)
         self._stepped = False
         self.k = k + 1
 
     def run(self, steps: int):
-        """Enqueue `steps` ticks: plant step, (inject_obs,) pre, solve, post(, inject_cmd).
+        """Enqueue `steps` ticks: plant step, (inject_obs,) pre, solve, post(, inject_cmd);
+        scheduled: pre_sched, the selected-instance solve, post_sched.
         Returns without waiting for the device."""
         for _ in range(int(steps)):
             self._enqueue_tick()
@@ -288,12 +338,14 @@ class DeviceFleetLoop:
     # -- state and logs -----------------------------------------------------------------
     def state(self) -> dict:
         """Host copies of the controller state (STATE_KEYS), the plant state, the
-        injector state (_INJECT_KEYS, with ``uncertainty``) and the tick counter."""
+        injector state (_INJECT_KEYS, with ``uncertainty``), the scheduled
+        tick's counters and last-solve rows (_SCHED_KEYS) and the tick counter."""
         self.torch.cuda.synchronize(self.dev)
         s = {k: self.S[k].cpu().numpy().copy() for k in STATE_KEYS}
         s.update({k: self.P[k].cpu().numpy().copy() for k in _PLANT_KEYS})
         if self.J is not None:
             s.update({k: self.J[k].cpu().numpy().copy() for k in _INJECT_KEYS})
+        s.update({k: self.Q[k].cpu().numpy().copy() for k in _SCHED_KEYS})
         s.update(k=self.k, stepped=self._stepped)
         return s
 
@@ -306,6 +358,9 @@ class DeviceFleetLoop:
             self.P[k].copy_(torch.from_numpy(np.ascontiguousarray(s[k])).to(self.dev))
         for k in _INJECT_KEYS if self.J is not None else ():
             self.J[k].copy_(torch.from_numpy(np.ascontiguousarray(s[k])).to(self.dev))
+        for k in _SCHED_KEYS:
+            if k in s:  # a state saved without them: a loop that solves every tick
+                self.Q[k].copy_(torch.from_numpy(np.ascontiguousarray(s[k])).to(self.dev))
         self.k, self._stepped = int(s["k"]), bool(s["stepped"])
         torch.cuda.synchronize(self.dev)
 
@@ -315,7 +370,8 @@ class DeviceFleetLoop:
         (k + 1, B, FLEET_LOG_W): row j is the plant record (site position,
         normal force, contact flag) tick j's controllers saw, the last row the
         one after the last command (the plant is stepped for it, once), ``t``
-        (k,) the ticks' times, ``plant_fail`` (B,) plant steps that failed; with
+        (k,) the ticks' times, ``plant_fail`` (B,) plant steps that failed,
+        ``solved`` (k, B) bool the instances that solved in each tick; with
         ``uncertainty`` also ``inject_a``, ``inject_b`` (B,): the injectors'
         actuation gain and bias, NaN where there is none."""
         torch, k = self.torch, self.k
@@ -326,7 +382,8 @@ class DeviceFleetLoop:
         torch.cuda.synchronize(self.dev)
         info = self.log_info[:k].cpu().numpy()
         out = dict(info=info, obs=self.log_obs[: k + 1].cpu().numpy(), t=self.times[:k].copy(),
-                   plant_fail=self.log_fail[: k + 1].sum(0).cpu().numpy())
+                   plant_fail=self.log_fail[: k + 1].sum(0).cpu().numpy(),
+                   solved=(self.log_need[:k].cpu().numpy() != 0) if self.sched is not None else np.ones((k, self.B), bool))
         for i, name in enumerate(_abi.FLEET_INFO_FIELDS):
             out[name] = info[:, :, i]
         if self.inject_a is not None:

@@ -284,12 +284,28 @@ class BatchedBoxFDDP:
         return plan
 
     # -- solve (device-resident torch tensors; bench path) ---------------------------
-    def solve_dev(self, t, maxiter: int = 10, is_feasible: bool = False, stream=None):
+    def solve_dev(self, t, maxiter: int = 10, is_feasible: bool = False, stream=None, active=None):
         """t: dict of contiguous torch.cuda tensors with keys x0, node_ref, inst_ref,
         surface (uint8), xs_init, us_init and outputs xs, us, K, cost, iters (int32),
-        ok (uint8), fn_pred, stats (int32).  Asynchronous on `stream` (hipStream_t int)."""
+        ok (uint8), fn_pred, stats (int32).  Asynchronous on `stream` (hipStream_t int).
+        active: optional (B,) uint8 device tensor, the instances that solve
+        (ffddp_solve_batch_sel_dev); the others' input rows are not read and
+        their output rows not written."""
         B = int(t["x0"].shape[0])
         p = lambda k: C.c_void_p(int(t[k].data_ptr()))
+        if active is not None:
+            import torch
+
+            if (active.dtype != torch.uint8 or not active.is_cuda or not active.is_contiguous()
+                    or tuple(active.shape) != (B,)):
+                raise ValueError("active must be a contiguous (B,) uint8 device tensor")
+            rc = self._lib.ffddp_solve_batch_sel_dev(
+                self._h, B, p("x0"), p("node_ref"), p("inst_ref"), p("surface"), p("xs_init"), p("us_init"),
+                int(maxiter), int(bool(is_feasible)), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
+                p("fn_pred"), p("stats"), C.c_void_p(int(active.data_ptr())), C.c_void_p(stream if stream else 0),
+            )
+            self._check(rc, "ffddp_solve_batch_sel_dev")
+            return
         rc = self._lib.ffddp_solve_batch_dev(
             self._h, B, p("x0"), p("node_ref"), p("inst_ref"), p("surface"), p("xs_init"), p("us_init"),
             int(maxiter), int(bool(is_feasible)), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
@@ -331,7 +347,18 @@ class BatchedBoxFDDP:
             setattr(s, k, int(t[k].data_ptr()))
         return s
 
-    def fleet_pre_dev(self, t, params: _abi.FleetParams, hint: bool, stream=None):
+    @staticmethod
+    def _fleet_sched(t, sched: _abi.FleetSched) -> _abi.FleetSched:
+        """A copy of `sched` pointing at t["since"], t["age"] (int32) and t["need"] (uint8), all (B,)."""
+        import torch
+
+        s = _abi.FleetSched.from_buffer_copy(sched)
+        for k, dt in (("since", torch.int32), ("age", torch.int32), ("need", torch.uint8)):
+            assert t[k].dtype == dt and t[k].is_contiguous() and t[k].shape[0] >= t["x0"].shape[0], k
+            setattr(s, k, int(t[k].data_ptr()))
+        return s
+
+    def fleet_pre_dev(self, t, params: _abi.FleetParams, hint: bool, stream=None, sched: _abi.FleetSched = None):
         """Everything a fleet tick does before the solve, for B instances in one
         launch.  Inputs t["q"], t["v"] (B, 7), t["fn_meas"], t["ee_z"] (B,),
         optionally t["contact"] (B,) and, for force feedback, t["tau_hat"]
@@ -341,6 +368,9 @@ class BatchedBoxFDDP:
         t["loss_count"] (int32), t["prev_mode"] (int8), t["tau_prev"] and the
         kept solution.  Writes the state and the solve's inputs t["x0"],
         t["surface"], t["inst_ref"], t["node_ref"], t["xs_init"], t["us_init"].
+        sched (_abi.fleet_sched): the scheduled tick (ffddp_fleet_pre_sched_dev)
+        with the counters t["since"], t["age"] (int32); writes t["need"]
+        (uint8), the solve's `active`, and warm starts only those instances.
         Asynchronous on `stream`."""
         B = int(t["x0"].shape[0])
         p = lambda k: C.c_void_p(int(t[k].data_ptr()) if t.get(k) is not None else 0)
@@ -348,32 +378,41 @@ class BatchedBoxFDDP:
         assert t.get("contact") is None or t["contact"].stride(0) == t["fn_meas"].stride(0)
         th = t.get("tau_hat")
         st = self._fleet_state(t)
-        rc = self._lib.ffddp_fleet_pre_dev(
-            self._h, B, C.byref(params), C.byref(st), p("q"), p("v"), p("fn_meas"), p("contact"), p("ee_z"),
-            int(t["q"].stride(0)), int(t["fn_meas"].stride(0)), p("tau_hat"), int(th.stride(0)) if th is not None else 0,
-            p("q_nom"), p("node_ref1"), int(bool(hint)), p("x0"), p("surface"), p("inst_ref"), p("node_ref"),
-            p("xs_init"), p("us_init"), C.c_void_p(stream if stream else 0),
-        )
+        args = (self._h, B, C.byref(params), C.byref(st), p("q"), p("v"), p("fn_meas"), p("contact"), p("ee_z"),
+                int(t["q"].stride(0)), int(t["fn_meas"].stride(0)), p("tau_hat"),
+                int(th.stride(0)) if th is not None else 0, p("q_nom"), p("node_ref1"), int(bool(hint)), p("x0"),
+                p("surface"), p("inst_ref"), p("node_ref"), p("xs_init"), p("us_init"))
+        if sched is not None:
+            rc = self._lib.ffddp_fleet_pre_sched_dev(*args, self._fleet_sched(t, sched), C.c_void_p(stream if stream else 0))
+            self._check(rc, "ffddp_fleet_pre_sched_dev")
+            return
+        rc = self._lib.ffddp_fleet_pre_dev(*args, C.c_void_p(stream if stream else 0))
         self._check(rc, "ffddp_fleet_pre_dev")
 
-    def fleet_post_dev(self, t, params: _abi.FleetParams, lpf: float = 0.0, stream=None):
+    def fleet_post_dev(self, t, params: _abi.FleetParams, lpf: float = 0.0, stream=None,
+                       sched: _abi.FleetSched = None):
         """Everything a fleet tick does after solve_dev(t): keep, torque policy,
         unstable fallback and _safe_tau -> t["tau_cmd"] (B, 7), t["info"]
         (B, _abi.FLEET_INFO_W; fields _abi.FLEET_INFO_FIELDS) and the state.
         t["tau_bias"] (B, 7) may be a strided view.  Optional: t["tau_app"]
         (B, 7) = t["scale"] (B, 7) * tau_cmd, t["tau_filt"] (B, 7) low-passed by
         `lpf`, t["log_obs"] (B, _abi.FLEET_LOG_W) from the plant records
-        t["obs"].  Asynchronous on `stream`."""
+        t["obs"].  sched: the scheduled tick (ffddp_fleet_post_sched_dev), after
+        solve_dev(t, active=t["need"]); reads t["need"], updates t["since"] and
+        t["age"].  Asynchronous on `stream`."""
         B = int(t["x0"].shape[0])
         p = lambda k: C.c_void_p(int(t[k].data_ptr()) if t.get(k) is not None else 0)
         st = self._fleet_state(t)
         obs = t.get("obs")
-        rc = self._lib.ffddp_fleet_post_dev(
-            self._h, B, C.byref(params), C.byref(st), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
-            p("fn_pred"), p("stats"), p("x0"), p("surface"), p("tau_bias"), int(t["tau_bias"].stride(0)),
-            p("tau_cmd"), p("info"), p("scale"), p("tau_app"), p("tau_filt"), float(lpf), p("obs"),
-            int(obs.stride(0)) if obs is not None else 0, p("log_obs"), C.c_void_p(stream if stream else 0),
-        )
+        args = (self._h, B, C.byref(params), C.byref(st), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
+                p("fn_pred"), p("stats"), p("x0"), p("surface"), p("tau_bias"), int(t["tau_bias"].stride(0)),
+                p("tau_cmd"), p("info"), p("scale"), p("tau_app"), p("tau_filt"), float(lpf), p("obs"),
+                int(obs.stride(0)) if obs is not None else 0, p("log_obs"))
+        if sched is not None:
+            rc = self._lib.ffddp_fleet_post_sched_dev(*args, self._fleet_sched(t, sched), C.c_void_p(stream if stream else 0))
+            self._check(rc, "ffddp_fleet_post_sched_dev")
+            return
+        rc = self._lib.ffddp_fleet_post_dev(*args, C.c_void_p(stream if stream else 0))
         self._check(rc, "ffddp_fleet_post_dev")
 
     # -- the uncertainty injector around the tick (include/ffddp.h: ffddp_fleet_inject_*_dev) --

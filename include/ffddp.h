@@ -173,6 +173,29 @@ int ffddp_solve_batch_dev(ffddp_handle* h, int B, const double* x0, const double
                           double* us, double* K, double* cost, int32_t* iters, uint8_t* ok,
                           double* fn_pred, int32_t* stats, void* stream);
 
+/* ffddp_solve_batch_dev for a subset of the batch: `active` is [B] device
+ * bytes, instance b solves iff active[b] != 0; NULL selects every instance
+ * (ffddp_solve_batch_dev is this call with NULL: same launches, same bits).
+ * For an unselected instance the solve reads none of its xs_init / us_init
+ * rows and writes none of its rows of xs, us, K, cost, iters, ok, fn_pred,
+ * stats (its x0, node_ref, inst_ref, surface rows are not read either); its
+ * part of the handle's workspace is left stale.  A selected instance's
+ * outputs are the bits the unmasked call gives it (stats [5..7] count
+ * line-search passes, which follow the slice's active count as they do
+ * across batch sizes; they agree whenever the first pass already takes
+ * every step length, as it does for small batches).  The first active list is
+ * the selected instances in ascending order, a function of the mask alone.
+ * The grids stay sized by the batch: blocks beyond the selected count exit at
+ * once, as in a late iteration.  An all-zero mask is legal (returns 0, writes
+ * nothing).  Errors, the trace, the per-kernel profile and the in-place rule
+ * (xs_init == xs, us_init == us) are ffddp_solve_batch_dev's.  The
+ * host-pointer entry point and solve plans take no mask. */
+int ffddp_solve_batch_sel_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                              const double* inst_ref, const uint8_t* surface, const double* xs_init,
+                              const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
+                              double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
+                              const uint8_t* active, void* stream);
+
 /* Solve plan for a receding-horizon loop: one solve of a fixed batch per
  * control tick (crocoddyl_classical.py:367 called every tick at
  * run_classical.py:412).  ffddp_plan_create captures the whole host-array
@@ -441,6 +464,72 @@ int ffddp_fleet_post_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, co
                          const double* x0, const uint8_t* surface, const double* tau_bias, int ld_tau_bias,
                          double* tau_cmd, double* info, const double* scale, double* tau_app, double* tau_filt,
                          double lpf, const double* obs, int ld_obs, double* log_obs, void* stream);
+
+/* The scheduled tick: the controllers' mpc_update_steps (solve every
+ * period-th tick, the Riccati feedback policy on the receding plan in
+ * between; crocoddyl_classical.py:430-438, _need_solve) and
+ * apply_command_filter (_safe_tau's trust / rate / smoothing filter, :272-284).
+ * A tick is ffddp_fleet_pre_sched_dev, ffddp_solve_batch_sel_dev with
+ * active = need, ffddp_fleet_post_sched_dev on one stream.  The arguments are
+ * the unscheduled entry points' plus this struct by value; those entry points
+ * themselves are unchanged.
+ *
+ * Instances do not solve in lockstep: a mode switch, an unstable tick or a
+ * non-finite solve drops an instance's plan (valid = 0) and it solves on its
+ * next tick whatever the period says.  pre:  need[b] = !warm || since[b] + 1
+ * >= period, with warm = valid && no mode change, after the unchanged latch
+ * and mode logic.
+ *
+ * The kept solution is never moved.  The reference shifts its lists by one
+ * knot per tick without a solve (us, xs, Ks -> [1:] + [last]), which is pure
+ * copying: after age[b] shifts, knot i of the shifted lists is knot
+ * min(i + age, N - 1) of keep_us / keep_K and knot min(i + age, N) of
+ * keep_xs, and every reader indexes through age.
+ *   pre   x0, surface, inst_ref, node_ref and the state for every instance, as
+ *         ffddp_fleet_pre_dev; for need instances the warm start of the
+ *         shifted lists, xs_init[k >= 1] = keep_xs[min(k + age, N)], us_init[k]
+ *         = keep_us[min(k + 1 + age, N - 1)] (cold start as before); the
+ *         xs_init / us_init rows of the others are not written.
+ *   post  fin = need && us[b][0] finite; a keep sets age = 0.  The policy
+ *         reads knot min(age, N - 1) of keep_us / keep_K, knot min(age, N) of
+ *         keep_xs and (force feedback, tau1) knot min(age + 1, N).  info's
+ *         cost, ok, iters, fn_pred come from the solve's output rows, which
+ *         for an instance that did not solve still hold its last solve's
+ *         values (the controllers' _last_solve_* and carried fn_pred);
+ *         neg_accepted is 0 for it.  With apply_filter, after the non-finite
+ *         row substitution and the clip to tau_limits:
+ *             d   = clip(target - prev, +-tau_trust_inf)
+ *             d   = clip(d, +-tau_rate_limit[i] * dt)
+ *             cmd = clip((1 - a) prev + a (prev + d), +-tau_limits[i])
+ *         without contraction, a NaN propagating as in numpy.clip; tau_prev =
+ *         cmd.  Last: since = solved ? 0 : since + 1, age += 1 unless solved.
+ * With period = 1, apply_filter = 0 and age = 0 both give the unscheduled
+ * entry points' bits.  FFDDP_E_INVALID also for a null since / age / need,
+ * period < 1, or (apply_filter) tau_smoothing_alpha outside [0, 1]. */
+typedef struct ffddp_fleet_sched {
+  int32_t period;             /* mpc_update_steps, >= 1 */
+  int32_t apply_filter;       /* apply_command_filter */
+  double tau_trust_inf;
+  double tau_smoothing_alpha; /* already clipped to [0, 1] */
+  double dt;                  /* the control period */
+  double tau_rate_limit[7];
+  int32_t* since;             /* [B] state: ticks since the instance's last solve */
+  int32_t* age;               /* [B] state: shifts of the kept solution since it was kept */
+  uint8_t* need;              /* [B] written by pre: 1 = the instance solves this tick */
+} ffddp_fleet_sched;
+int ffddp_fleet_pre_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                              const double* q, const double* v, const double* fn_meas, const double* contact,
+                              const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
+                              const double* q_nom, const double* node_ref1, int contact_hint, double* x0,
+                              uint8_t* surface, double* inst_ref, double* node_ref, double* xs_init, double* us_init,
+                              ffddp_fleet_sched sched, void* stream);
+int ffddp_fleet_post_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                               const double* xs, const double* us, const double* K, const double* cost,
+                               const int32_t* iters, const uint8_t* ok, const double* fn_pred, const int32_t* stats,
+                               const double* x0, const uint8_t* surface, const double* tau_bias, int ld_tau_bias,
+                               double* tau_cmd, double* info, const double* scale, double* tau_app, double* tau_filt,
+                               double lpf, const double* obs, int ld_obs, double* log_obs, ffddp_fleet_sched sched,
+                               void* stream);
 
 /* The closed-loop sweep's actuation-uncertainty injector on the device
  * (ffddp/uncertainty.py BatchedUncertaintyInjector, bit for bit): two more

@@ -12,6 +12,8 @@ wall time, closed-loop ticks/s).
   python tools/sweep_c4.py --device-loop 1 --device-noise numpy   # the whole closed loop on the device, the
                                                                # injector's normals from a pre-drawn table
   python tools/sweep_c4.py --device-loop 1 --device-noise philox  # ... or generated on the device
+  python tools/sweep_c4.py --device-loop 1 --solve-period 2     # solve every 2nd tick, the feedback policy between
+  python tools/sweep_c4.py --command-filter 1                   # _safe_tau's trust / rate / smoothing filter
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/sweep_c4.py
 """
 import argparse
@@ -46,6 +48,10 @@ def main():
     ap.add_argument("--device-noise", choices=("numpy", "philox"), default=None,
                     help="with --device-loop 1: run the uncertainty injector on the device, its normals from a "
                          "table drawn ahead with numpy (the host loop's perturbations) or from Philox on the device")
+    ap.add_argument("--solve-period", type=int, default=1,
+                    help="mpc_update_steps: solve every P-th tick, the feedback policy on the receding plan between")
+    ap.add_argument("--command-filter", type=int, choices=(0, 1), default=0,
+                    help="1: apply_command_filter (trust region, rate limit, smoothing of the command)")
     ap.add_argument("--scenarios", nargs="+", default=list(ALL_SCENARIOS), help="scenarios to sweep (default: all 5)")
     a = ap.parse_args()
     import torch
@@ -60,7 +66,8 @@ def main():
     t0 = time.perf_counter()
     res = fleet.run_sweep(scenarios=tuple(a.scenarios), seeds=a.seeds, total_time=a.time, rank=rank, world=world,
                            device=local, verbose=(rank == 0), neg_step_rule=a.neg_step_rule, variant=a.variant, device_tick=bool(a.device_tick),
-                           device_loop=bool(a.device_loop), device_noise=a.device_noise)
+                           device_loop=bool(a.device_loop), device_noise=a.device_noise,
+                           solve_period=a.solve_period, command_filter=bool(a.command_filter))
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -72,6 +79,8 @@ def main():
                 "ranks": world, "device_loop": int(a.device_loop), "device_noise": a.device_noise, "loop_wall_s": res["wall_s"],
                 "neg_step_rule": a.neg_step_rule, "variant": a.variant,
                 "device_tick": int(a.device_tick or a.variant == "ff"),
+                "solve_period": a.solve_period, "command_filter": int(a.command_filter),
+                "rank0_solve_share": float(res["solved_ticks"].sum() / max(1, res["ticks"] * res["instances"])),
                 "instances": int(res["n_all"]), "ticks": res["ticks"], "wall_s": wall,
                 "closed_loop_ticks_per_s": res["n_all"] * res["ticks"] / wall,
                 "rank0_controller_s": res["controller_s"], "scenarios": fleet.scenario_table(names, m)}
