@@ -46,6 +46,7 @@
 #include "ffddp_plant.hpp"
 #include "ffddp_primal_g8.hpp"
 #include "ffddp_rollout.hpp"
+#include "ffddp_task.hpp"
 
 using namespace ffddp;
 
@@ -2598,17 +2599,27 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_keep(
 // knot i of the shifted lists is knot min(i + age, N) of keep_xs and knot
 // min(i + age, N - 1) of keep_us / keep_K.  Only solving instances get a warm
 // start.  SCHED = false is ffddp_fleet_pre_dev's kernel, unchanged (Q unused).
-template <bool SCHED>
+//
+// TASK (ffddp_fleet_pre_task_dev): the instance's references and hint come
+// from its own record (ffddp_task.hpp) at the task time T.t - delay instead of
+// node1 / hint1.  The flag is two comparisons, so every wave derives it with
+// the rest of the old state; the knots are spread over the threads.  TASK =
+// false compiles the code as it was (T, dt_ocp unused).
+template <bool SCHED, bool TASK>
 __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_pre(
     const ffddp_robot* __restrict__ rb, int N, int nx, ffddp_fleet_params P, ffddp_fleet_state S, ffddp_fleet_sched Q,
     const double* __restrict__ q, const double* __restrict__ v, const double* __restrict__ fn_meas,
     const double* __restrict__ contact, const double* __restrict__ ee_z, long ld, long ld1,
-    const double* __restrict__ tau_hat, long ld_th, const double* __restrict__ q_nom, const double* __restrict__ node1, int hint,
+    const double* __restrict__ tau_hat, long ld_th, const double* __restrict__ q_nom, const double* __restrict__ node1, int hint1,
     double* __restrict__ x0, uint8_t* __restrict__ surface, double* __restrict__ inst_ref,
-    double* __restrict__ node_ref, double* __restrict__ xs_init, double* __restrict__ us_init) {
+    double* __restrict__ node_ref, double* __restrict__ xs_init, double* __restrict__ us_init, ffddp_fleet_tasks T,
+    double dt_ocp) {
   const long b = blockIdx.x;
   const int tid = threadIdx.x;
   const bool ff = nx == 21;
+  const double* rec = TASK ? T.rec + b * FFDDP_FLEET_TASK_W : nullptr;
+  const double t_task = TASK ? T.t - rec[FFDDP_FLEET_TASK_DELAY] : 0.0;
+  const int hint = TASK ? (fleet_task_surface(rec, t_task) ? 1 : 0) : hint1;
   const bool latched0 = S.latched[b] != 0, valid0 = S.valid[b] != 0;
   const int cnt0 = S.loss_count[b], pm = S.prev_mode[b];
   // _surface (fleet.py; crocoddyl_classical.py:286-303)
@@ -2658,7 +2669,11 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_pre(
   }
   const int nref = (N + 1) * 6, nxs = (N + 1) * nx, nus = N * NU;
   double* nr = node_ref + b * nref;
-  for (int i = tid; i < nref; i += FLEET_BLOCK) nr[i] = node1[i];
+  if (TASK) {
+    for (int k = tid; k <= N; k += FLEET_BLOCK) fleet_task_ref(rec, T.p_site_minus_frame, t_task, k, dt_ocp, nr + k * 6);
+  } else {
+    for (int i = tid; i < nref; i += FLEET_BLOCK) nr[i] = node1[i];
+  }
   // _shift_guess, as k_fleet_warm_start
   const double* kx = S.keep_xs + b * nxs;
   double* xo = xs_init + b * nxs;
@@ -4397,9 +4412,9 @@ int ffddp_fleet_pre_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, con
       p->torque_mode > 2 || p->posture_mode < 0 || p->posture_mode > 1)
     return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_dev: bad stride or mode");
   HIPCHK(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(k_fleet_pre<false>, dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx, *p, *s,
+  hipLaunchKernelGGL((k_fleet_pre<false, false>), dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx, *p, *s,
                      ffddp_fleet_sched{}, q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar, tau_hat, (long)ld_tau_hat, q_nom, node_ref1,
-                     contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init);
+                     contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init, ffddp_fleet_tasks{}, 0.0);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -4453,9 +4468,9 @@ int ffddp_fleet_pre_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params* 
     return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_sched_dev: bad stride or mode");
   if (const int rc = fleet_sched_check(h, sched, "ffddp_fleet_pre_sched_dev")) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(k_fleet_pre<true>, dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx, *p, *s,
+  hipLaunchKernelGGL((k_fleet_pre<true, false>), dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx, *p, *s,
                      sched, q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar, tau_hat, (long)ld_tau_hat, q_nom,
-                     node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init);
+                     node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init, ffddp_fleet_tasks{}, 0.0);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -4480,6 +4495,53 @@ int ffddp_fleet_post_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params*
   hipLaunchKernelGGL(k_fleet_post<true>, dim3(B, FLEET_CHUNKS), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->hc.N, h->hc.nx,
                      *p, *s, sched, xs, us, K, cost, iters, ok, fn_pred, stats, x0, surface, tau_bias, (long)ld_tau_bias,
                      tau_cmd, info, scale, tau_app, tau_filt, lpf, obs, (long)ld_obs, log_obs);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// per-instance tasks (ffddp_task.hpp): the sampler alone, and pre with it in place of node_ref1 / contact_hint
+int ffddp_fleet_task_refs_dev(ffddp_handle* h, int B, ffddp_fleet_tasks tasks, const double* t, double* node_ref,
+                              uint8_t* hint, void* stream) {
+  if (!h) return FFDDP_E_INVALID;
+  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_task_refs_dev: B must be positive");
+  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  if (!tasks.rec || !t || !node_ref || !hint) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_task_refs_dev: null pointer");
+  HIPCHK(h, hipSetDevice(h->device));
+  const long n = (long)B * (h->hc.N + 1);
+  hipLaunchKernelGGL(k_fleet_task_refs, dim3((unsigned)((n + TASK_BLOCK - 1) / TASK_BLOCK)), dim3(TASK_BLOCK), 0,
+                     (hipStream_t)stream, B, h->hc.N, h->hc.dt, tasks, t, node_ref, hint);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int ffddp_fleet_pre_task_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                             const double* q, const double* v, const double* fn_meas, const double* contact,
+                             const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
+                             const double* q_nom, ffddp_fleet_tasks tasks, double* x0, uint8_t* surface,
+                             double* inst_ref, double* node_ref, double* xs_init, double* us_init,
+                             const ffddp_fleet_sched* sched, void* stream) {
+  if (!h) return FFDDP_E_INVALID;
+  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_task_dev: B must be positive");
+  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  const bool ff = h->hc.nx == 21;
+  if (!p || !s || !fleet_state_complete(s) || !q || !v || !fn_meas || !ee_z || (ff && !tau_hat) || !q_nom ||
+      !tasks.rec || !x0 || !surface || !inst_ref || !node_ref || !xs_init || !us_init)
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_task_dev: null pointer");
+  if (ld_qv < NQ || ld_scalar < 1 || (ff && ld_tau_hat < NU) || p->phase_source < 0 || p->phase_source > 1 || p->torque_mode < 0 ||
+      p->torque_mode > 2 || p->posture_mode < 0 || p->posture_mode > 1)
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_task_dev: bad stride or mode");
+  if (sched)
+    if (const int rc = fleet_sched_check(h, *sched, "ffddp_fleet_pre_task_dev")) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (sched)
+    hipLaunchKernelGGL((k_fleet_pre<true, true>), dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx,
+                       *p, *s, *sched, q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar, tau_hat, (long)ld_tau_hat,
+                       q_nom, (const double*)nullptr, 0, x0, surface, inst_ref, node_ref, xs_init, us_init, tasks, h->hc.dt);
+  else
+    hipLaunchKernelGGL((k_fleet_pre<false, true>), dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx,
+                       *p, *s, ffddp_fleet_sched{}, q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar, tau_hat,
+                       (long)ld_tau_hat, q_nom, (const double*)nullptr, 0, x0, surface, inst_ref, node_ref, xs_init, us_init, tasks,
+                       h->hc.dt);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

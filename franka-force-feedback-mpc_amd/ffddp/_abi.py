@@ -56,6 +56,8 @@ SYMBOLS = (
     "ffddp_fleet_inject_obs_dev",
     "ffddp_fleet_inject_cmd_dev",
     "ffddp_fleet_noise_dev",
+    "ffddp_fleet_task_refs_dev",
+    "ffddp_fleet_pre_task_dev",
 )
 PLANT_OBS = 69
 NSTATS = 10
@@ -130,6 +132,15 @@ class FleetInject(C.Structure):
         ("sigma_tau", C.c_double),
         ("lpf", C.c_double),
     ] + [(n, C.c_void_p) for n in ("row", "a", "b", "seed", "obs_ring", "cmd_ring", "tau_hat_filt", "z_cmd")]
+
+
+FLEET_TASK_W = 22  # FFDDP_FLEET_TASK_W: doubles per task record (trajectory.task_records fills them)
+
+
+class FleetTasks(C.Structure):
+    """ffddp_fleet_tasks: the site offset, the tick's time and the device pointer to the (B, FLEET_TASK_W) records."""
+
+    _fields_ = [("p_site_minus_frame", C.c_double * 3), ("t", C.c_double), ("rec", C.c_void_p)]
 
 
 class FleetParams(C.Structure):
@@ -459,6 +470,13 @@ def load() -> C.CDLL:
     lib.ffddp_fleet_inject_cmd_dev.restype = C.c_int
     lib.ffddp_fleet_noise_dev.argtypes = [C.c_void_p, C.c_int, vp, C.c_int, vp, vp] + [vp]
     lib.ffddp_fleet_noise_dev.restype = C.c_int
+    # per-instance tasks: ffddp_fleet_tasks by value; pre_task takes it in place of node_ref1 / contact_hint
+    # and a const ffddp_fleet_sched* (NULL = unscheduled) before the stream
+    lib.ffddp_fleet_task_refs_dev.argtypes = [C.c_void_p, C.c_int, FleetTasks, vp, vp, vp] + [vp]
+    lib.ffddp_fleet_task_refs_dev.restype = C.c_int
+    lib.ffddp_fleet_pre_task_dev.argtypes = (fl + [vp] * 5 + [C.c_int, C.c_int, vp, C.c_int, vp, FleetTasks] + [vp] * 6
+                                             + [C.POINTER(FleetSched), vp])
+    lib.ffddp_fleet_pre_task_dev.restype = C.c_int
     _lib = lib
     return lib
 

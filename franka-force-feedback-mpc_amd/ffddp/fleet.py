@@ -55,7 +55,8 @@ from .controller import (_OCP_FIELDS, _quat_wxyz_to_R, classical_benchmark_confi
 from .plant import BatchedPlant, PandaTablePlant
 from .runlog import summary_metrics
 from .solver import BatchedBoxFDDP
-from .trajectory import TABLE_CENTER, TABLE_HALF_Z, TOOL_RADIUS, make_approach_then_circle, with_contact_hold
+from .trajectory import (TABLE_CENTER, TABLE_HALF_Z, TOOL_RADIUS, FleetTask, make_approach_then_circle,
+                         sample_records, task_records, with_contact_hold)
 from .uncertainty import BatchedUncertaintyInjector, config_for_scenario
 
 Traj = Callable[[float], Tuple[np.ndarray, np.ndarray, bool]]
@@ -558,7 +559,8 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
               q_sigma: float = 0.02, verbose: bool = True, record: Sequence[int] = (),
               neg_step_rule: int = 0, variant: str = "classical", device_tick: bool = False,
               device_loop: bool = False, device_noise: Optional[str] = None, solve_period: int = 1,
-              command_filter: bool = False) -> dict:
+              command_filter: bool = False, device_refs: bool = False,
+              task_spread: Optional[Tuple[float, float]] = None, stagger: int = 0) -> dict:
     """Closed-loop sweep of len(scenarios) * seeds instances; this rank runs
     its contiguous shard.  Returns per-instance summary arrays (this shard).
     record: shard-local instance indices whose controller inputs (the plant
@@ -591,7 +593,17 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     every solve_period-th tick, the feedback policy in between) and
     apply_command_filter; on the host path they go into the configuration, on
     the device path to the loop.  The summary's ``solved_ticks`` counts each
-    instance's ticks with a solve."""
+    instance's ticks with a solve.
+    device_refs, task_spread, stagger (with device_loop only, NotImplementedError
+    otherwise: the host fleets keep their single traj_fn): the instances'
+    references are sampled on the device from per-instance task records
+    (DeviceFleetLoop(tasks=...)) instead of a host table.  device_refs alone
+    runs the sweep's one task that way.  task_spread = (dr, dw) varies the
+    task: instance radius = 0.10 (1 + dr u1), omega = 1.5 (1 + dw u2) with u
+    uniform in [-1, 1] from default_rng([seed_b, 1]) (the q0 draws do not
+    move).  stagger = S delays instance b (its index in the whole sweep) by
+    (b mod S) dt.  Either implies device_refs.  The summary's reference
+    position and contact-phase window are then per instance, in task time."""
     variant = str(variant).strip().lower()
     if variant not in ("classical", "ff"):
         raise ValueError(f"run_sweep: unknown variant {variant!r}")
@@ -600,6 +612,17 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     if not isinstance(command_filter, (bool, np.bool_)) and command_filter not in (0, 1):
         raise ValueError(f"run_sweep: command_filter must be a flag, not {command_filter!r}")
     solve_period, command_filter = int(solve_period), bool(command_filter)
+    if isinstance(stagger, bool) or int(stagger) != stagger or int(stagger) < 0:
+        raise ValueError(f"run_sweep: stagger must be an integer >= 0, not {stagger!r}")
+    stagger = int(stagger)
+    if task_spread is not None:
+        task_spread = tuple(float(x) for x in task_spread)
+        if len(task_spread) != 2 or not all(0.0 <= x < 1.0 for x in task_spread):
+            raise ValueError(f"run_sweep: task_spread is (dr, dw), each in [0, 1), not {task_spread!r}")
+    device_refs = bool(device_refs) or task_spread is not None or stagger > 0
+    if device_refs and not device_loop:
+        raise NotImplementedError("run_sweep: device_refs, task_spread and stagger need device_loop=True "
+                                  "(the host fleets take one traj_fn)")
     if device_noise is not None:
         if device_noise not in ("numpy", "philox"):
             raise ValueError(f"run_sweep: unknown device_noise {device_noise!r} (numpy or philox)")
@@ -637,9 +660,19 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
         ucfgs = None
         if device_noise is not None:  # per instance, as the host path below
             ucfgs = [config_for_scenario(str(names[b]), seed=int(seed[b])) for b in range(B)]
+        tasks = None
+        if device_refs:
+            dr, dw = task_spread if task_spread is not None else (0.0, 0.0)
+            tasks = []
+            for b in range(B):
+                u = np.random.default_rng([int(seed[b]), 1]).uniform(-1.0, 1.0, 2) if task_spread is not None else (0.0, 0.0)
+                tasks.append(FleetTask(center=center, radius=0.10 * (1.0 + dr * u[0]), omega=1.5 * (1.0 + dw * u[1]),
+                                       z_contact=z_contact, t_approach=0.55, t_pre=0.25, ee_start=obs0.ee_pos.copy(),
+                                       z_pre=z_contact + 0.05, t_contact_phase=t_cp, t_hold=0.2,
+                                       delay=((lo + b) % stagger) * (0.001 * 5) if stagger else 0.0))  # BatchedPlant.dt
         out = _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, (R_site_from_pin_ee, p_off), total_time,
                                 neg_step_rule, device, t_cp, verbose, ucfgs, device_noise, solve_period,
-                                command_filter)
+                                command_filter, tasks)
         out.update(names=names, seed=seed, shard=(lo, hi), n_all=n_all)
         return out
     plant = BatchedPlant(B, timestep=0.001, n_substeps=5, device=device)
@@ -760,9 +793,11 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
 
 
 def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, total_time, neg_step_rule, device, t_cp,
-                      verbose, ucfgs=None, noise=None, solve_period=1, command_filter=False) -> dict:
+                      verbose, ucfgs=None, noise=None, solve_period=1, command_filter=False, tasks=None) -> dict:
     """run_sweep's loop on the device (fleet_loop.DeviceFleetLoop) and the
-    host path's summary from the downloaded logs."""
+    host path's summary from the downloaded logs.  tasks: per-instance
+    FleetTasks in place of traj; the summary's reference position and its
+    contact phase are then each instance's own, in its task time."""
     import torch
 
     from .fleet_loop import DeviceFleetLoop
@@ -774,9 +809,10 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     cfg = make_cfg(dt, z_contact, neg_step_rule=neg_step_rule)
     cfg.apply_command_filter = bool(command_filter)
     steps = int(total_time / dt)
-    loop = DeviceFleetLoop(variant, B, traj, cfg, q0, tilt_deg=tilt, torque_scale=scale, device=device, steps=steps,
+    loop = DeviceFleetLoop(variant, B, traj if tasks is None else None, cfg, q0, tilt_deg=tilt, torque_scale=scale,
+                           device=device, steps=steps,
                            calibration=calibration, timestep=timestep, n_substeps=n_substeps, uncertainty=ucfgs,
-                           noise=noise or "numpy", solve_period=int(solve_period))
+                           noise=noise or "numpy", solve_period=int(solve_period), tasks=tasks)
     wall0 = time.perf_counter()
     loop.run(steps)
     torch.cuda.synchronize(loop.dev)
@@ -788,10 +824,17 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     # series[k]: the plant after tick k's command, at the time t_k + dt (the host loop's t += dt)
     t_after = np.array([float(t) + dt for t in r["t"]])
     obs = r["obs"][1:]
-    p_ref = np.stack([np.asarray(traj(float(t))[0], float) for t in t_after])
-    err = obs[:, :, 0:3] - p_ref[:, None, :]
+    if tasks is None:
+        p_ref = np.stack([np.asarray(traj(float(t))[0], float) for t in t_after])[:, None, :]
+        t_series, t_cps = np.repeat(t_after[:, None], B, 1), np.full(B, float(t_cp))
+    else:
+        rec = task_records(tasks)
+        t_series = r["t_task"] + dt
+        p_ref = np.stack([sample_records(rec, t_series[k])[0] for k in range(steps)])
+        t_cps = np.array([float(k.t_contact_phase) for k in tasks])
+    err = obs[:, :, 0:3] - p_ref
     fnm = obs[:, :, 3] * (obs[:, :, 4] > 0.5)
-    series = dict(t=np.repeat(t_after[:, None], B, 1), err_tan=np.linalg.norm(err[:, :, :2], axis=2),
+    series = dict(t=t_series, err_tan=np.linalg.norm(err[:, :, :2], axis=2),
                   err_3d=np.linalg.norm(err, axis=2), fn_meas=fnm, contact=(fnm > 0.5).astype(float))
     if verbose:
         print(f"device loop: B={B} ticks={steps} | final median |p-p_ref|={np.median(series['err_3d'][-1]):.4f} m | "
@@ -799,7 +842,7 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     per_inst = {k: np.zeros(B) for k in SUMMARY_KEYS}
     for b in range(B):
         s = summary_metrics(series["t"][:, b], series["err_tan"][:, b], series["err_3d"][:, b],
-                            series["fn_meas"][:, b], series["contact"][:, b], float(cfg.fn_des), t_cp)
+                            series["fn_meas"][:, b], series["contact"][:, b], float(cfg.fn_des), float(t_cps[b]))
         for k_ in SUMMARY_KEYS[:-3]:
             per_inst[k_][b] = s[k_]
     per_inst["unstable_ticks"] = (r["unstable"] != 0).sum(0).astype(float)
@@ -809,6 +852,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
                solved_ticks=r["solved"].sum(0).astype(float))
     if ucfgs is not None:
         out.update(inject_a=r["inject_a"], inject_b=r["inject_b"])
+    if tasks is not None:
+        out.update(solved=r["solved"], surface=r["surface"] != 0)  # (ticks, B): the per-tick solve share
     return out
 
 

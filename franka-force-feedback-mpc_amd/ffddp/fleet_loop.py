@@ -39,6 +39,16 @@ policy on the receding plan of the others.  The mask of tick k is row k of a
 (steps, B) log, returned as ``solved``.  With period 1 and no filter the loop
 enqueues exactly the unscheduled calls.
 
+With ``tasks`` (one trajectory.FleetTask per instance, or one for all) in
+place of ``traj_fn`` no table is built: every instance carries a record of its
+own task and a start delay, and the pre kernel (ffddp_fleet_pre_task_dev)
+samples that instance's N+1 references and its contact hint itself, at the
+tick's time minus the delay.  An instance delayed by d ticks waits at the
+start pose (the smoothstep clamps at negative task time) and reaches the
+contact switch d ticks after its neighbours; ``_need_solve`` re-anchors its
+solve grid there, so delays that are no multiples of the period spread the
+fleet's solves over the ticks.  ``steps`` then sizes the logs only.
+
 Not on the device, and so not supported here: ``run_sweep``'s ``record`` and
 any per-tick host callback; ``tick()`` lets a caller look between ticks at the price of its own
 synchronisation.
@@ -54,6 +64,7 @@ from . import _abi
 from . import robot as R
 from .controller import ff_filter_alpha
 from .fleet import Traj, fleet_ocp_config, node_ref, site_calibration
+from .trajectory import FleetTask, task_records
 from .uncertainty import UncertaintyProfileConfig, delay_steps, draw_gain_bias, predraw
 
 LPF_ALPHA = 0.2  # PandaTablePlant's tau_meas_lpf_alpha: the ff sweep's torque measurement filter
@@ -134,7 +145,10 @@ def resolve_solve_period(cfg, solve_period: Optional[int]) -> int:
 class DeviceFleetLoop:
     """B closed loops (plant + controller) resident on one device.
 
-    variant: "classical" or "ff"; traj_fn: the task; config: the controller
+    variant: "classical" or "ff"; traj_fn: the task, shared by the instances
+    and tabulated on the host, or None with ``tasks``: a sequence of B
+    FleetTask (or one, broadcast), sampled per instance on the device (both
+    or neither is a ValueError); config: the controller
     configuration; solve_period: None (the configuration's mpc_update_steps
     must be 1) or the period P >= 1 of the scheduled tick (a configuration
     with mpc_update_steps other than 1 or P is a ValueError);
@@ -157,14 +171,22 @@ class DeviceFleetLoop:
     -- all device tensors.
     """
 
-    def __init__(self, variant: str, B: int, traj_fn: Traj, config, q0, tilt_deg=0.0, torque_scale=1.0,
+    def __init__(self, variant: str, B: int, traj_fn: Optional[Traj], config, q0, tilt_deg=0.0, torque_scale=1.0,
                  device: int = 0, steps: int = 800, calibration: Optional[tuple] = None, t0: float = 0.0,
                  timestep: float = 0.001, n_substeps: int = 5,
                  uncertainty: Optional[Sequence[Optional[UncertaintyProfileConfig]]] = None, noise: str = "numpy",
-                 max_table_bytes: int = 1 << 30, solve_period: Optional[int] = None):
+                 max_table_bytes: int = 1 << 30, solve_period: Optional[int] = None,
+                 tasks: Optional[Sequence[FleetTask]] = None):
         variant = str(variant).strip().lower()
         if variant not in ("classical", "ff"):
             raise ValueError(f"DeviceFleetLoop: unknown variant {variant!r}")
+        if (traj_fn is None) == (tasks is None):
+            raise ValueError("DeviceFleetLoop: give either traj_fn (one task, tabulated on the host) or tasks "
+                             "(per instance, sampled on the device)")
+        if tasks is not None:
+            tasks = [tasks] * int(B) if isinstance(tasks, FleetTask) else list(tasks)
+            if len(tasks) != int(B) or not all(isinstance(k, FleetTask) for k in tasks):
+                raise ValueError("DeviceFleetLoop: tasks takes one FleetTask per instance, or one for all")
         if noise not in _abi.INJECT_NOISE_MODES:
             raise ValueError(f"DeviceFleetLoop: unknown noise source {noise!r} (numpy or philox)")
         ucfgs = None
@@ -197,8 +219,19 @@ class DeviceFleetLoop:
         self.R_des = R.R_MJ_FROM_PIN.T @ R.vertical_down_rotation_mj() @ R_site.T
         self.plant = BatchedPlant(self.B, timestep=timestep, n_substeps=n_substeps, device=device)
         self.dt = self.plant.dt
-        self.refs, self.hints, self.times = reference_table(traj_fn, self.steps, self.dt, self.N, self.dt_ocp,
-                                                            R.R_MJ_FROM_PIN, p_off, t0)
+        self.tasks, self.task_rec, self.task_delay = tasks, None, None
+        if tasks is None:
+            self.refs, self.hints, self.times = reference_table(traj_fn, self.steps, self.dt, self.N, self.dt_ocp,
+                                                                R.R_MJ_FROM_PIN, p_off, t0)
+        else:  # no table: the ticks' times only, by the sweep's t += dt
+            self.refs = self.hints = None
+            self.times = np.zeros(self.steps)
+            t = float(t0)
+            for k in range(self.steps):
+                self.times[k] = t
+                t += self.dt
+            self.task_rec = task_records(tasks)
+            self.task_delay = np.array([float(k.delay) for k in tasks])
         self.params = fleet_params(cfg, variant, self.dt_ocp)
         self.solver = BatchedBoxFDDP(fleet_ocp_config(cfg, variant, self.N, self.dt_ocp, self.R_des),
                                      max_batch=self.B, device=device)
@@ -240,7 +273,12 @@ class DeviceFleetLoop:
             self.sched = _abi.fleet_sched(cfg, self.period, self.dt)
             self.T.update(self.Q)
         self.Q.update({k: self.T[k] for k in ("cost", "iters", "ok", "fn_pred")})
-        self.ref_table = up(self.refs)
+        self.ref_table = self.rec = self.ktasks = None
+        if tasks is None:
+            self.ref_table = up(self.refs)
+        else:
+            self.rec = up(self.task_rec)
+            self.ktasks = self.solver.fleet_tasks(self.rec, p_off)
         self.log_info = torch.full((self.steps, B, _abi.FLEET_INFO_W), float("nan"), **f64)
         self.log_obs = torch.full((self.steps + 1, B, _abi.FLEET_LOG_W), float("nan"), **f64)
         self.log_fail = z(self.steps + 1, B, dtype=torch.int32)
@@ -304,17 +342,21 @@ class DeviceFleetLoop:
             raise RuntimeError(f"DeviceFleetLoop: the loop was sized for {self.steps} ticks")
         if not self._stepped:
             self._plant_step()
-        T["node_ref1"], T["info"], T["log_obs"] = self.ref_table[k], self.log_info[k], self.log_obs[k]
+        T["info"], T["log_obs"] = self.log_info[k], self.log_obs[k]
+        if self.ktasks is None:
+            T["node_ref1"], hint = self.ref_table[k], bool(self.hints[k])
+        else:
+            self.ktasks.t, hint = float(self.times[k]), False
         if self.inject is not None:
             self.solver.fleet_inject_obs_dev(self.J, self.inject, k, z=None if self.z_table is None else self.z_table[k],
                                              stream=self._stream)
         if self.sched is None:
-            self.solver.fleet_pre_dev(T, self.params, bool(self.hints[k]), stream=self._stream)
+            self.solver.fleet_pre_dev(T, self.params, hint, stream=self._stream, tasks=self.ktasks)
             self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream)
             self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream)
         else:
             T["need"] = self.log_need[k]
-            self.solver.fleet_pre_dev(T, self.params, bool(self.hints[k]), stream=self._stream, sched=self.sched)
+            self.solver.fleet_pre_dev(T, self.params, hint, stream=self._stream, sched=self.sched, tasks=self.ktasks)
             self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream,
                                   active=T["need"])
             self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream, sched=self.sched)
@@ -372,6 +414,8 @@ class DeviceFleetLoop:
         one after the last command (the plant is stepped for it, once), ``t``
         (k,) the ticks' times, ``plant_fail`` (B,) plant steps that failed,
         ``solved`` (k, B) bool the instances that solved in each tick; with
+        ``tasks`` also ``t_task`` (k, B): each instance's task time per tick
+        (t minus its delay, the subtraction the pre kernel does); with
         ``uncertainty`` also ``inject_a``, ``inject_b`` (B,): the injectors'
         actuation gain and bias, NaN where there is none."""
         torch, k = self.torch, self.k
@@ -388,4 +432,6 @@ class DeviceFleetLoop:
             out[name] = info[:, :, i]
         if self.inject_a is not None:
             out.update(inject_a=self.inject_a.copy(), inject_b=self.inject_b.copy())
+        if self.task_delay is not None:
+            out["t_task"] = self.times[:k, None] - self.task_delay[None, :]
         return out

@@ -358,7 +358,33 @@ class BatchedBoxFDDP:
             setattr(s, k, int(t[k].data_ptr()))
         return s
 
-    def fleet_pre_dev(self, t, params: _abi.FleetParams, hint: bool, stream=None, sched: _abi.FleetSched = None):
+    @staticmethod
+    def fleet_tasks(rec, p_site_minus_frame, t: float = 0.0) -> _abi.FleetTasks:
+        """ffddp_fleet_tasks over the device tensor rec (B, _abi.FLEET_TASK_W)
+        float64 (trajectory.task_records, uploaded) with the site offset and
+        the tick's time.  The struct holds the pointer: keep the tensor alive."""
+        assert rec.is_cuda and rec.is_contiguous() and rec.dim() == 2 and rec.shape[1] == _abi.FLEET_TASK_W
+        assert str(rec.dtype) == "torch.float64"
+        k = _abi.FleetTasks()
+        k.p_site_minus_frame[:] = [float(x) for x in np.asarray(p_site_minus_frame, float).reshape(3)]
+        k.t, k.rec = float(t), int(rec.data_ptr())
+        return k
+
+    def fleet_task_refs_dev(self, tasks: _abi.FleetTasks, t, node_ref, hint, stream=None):
+        """The device task sampler alone: t (B,) float64, the instances' task
+        times (the delay already subtracted) -> node_ref (B, N+1, 6) and hint
+        (B,) uint8, the surface flag at t.  Asynchronous on `stream`."""
+        B = int(t.shape[0])
+        assert t.is_contiguous() and node_ref.is_contiguous() and hint.is_contiguous()
+        assert tuple(node_ref.shape) == (B, self.N + 1, 6) and tuple(hint.shape) == (B,)
+        rc = self._lib.ffddp_fleet_task_refs_dev(
+            self._h, B, tasks, C.c_void_p(int(t.data_ptr())), C.c_void_p(int(node_ref.data_ptr())),
+            C.c_void_p(int(hint.data_ptr())), C.c_void_p(stream if stream else 0),
+        )
+        self._check(rc, "ffddp_fleet_task_refs_dev")
+
+    def fleet_pre_dev(self, t, params: _abi.FleetParams, hint: bool = False, stream=None, sched: _abi.FleetSched = None,
+                      tasks: _abi.FleetTasks = None):
         """Everything a fleet tick does before the solve, for B instances in one
         launch.  Inputs t["q"], t["v"] (B, 7), t["fn_meas"], t["ee_z"] (B,),
         optionally t["contact"] (B,) and, for force feedback, t["tau_hat"]
@@ -371,6 +397,9 @@ class BatchedBoxFDDP:
         sched (_abi.fleet_sched): the scheduled tick (ffddp_fleet_pre_sched_dev)
         with the counters t["since"], t["age"] (int32); writes t["need"]
         (uint8), the solve's `active`, and warm starts only those instances.
+        tasks (fleet_tasks): per-instance tasks (ffddp_fleet_pre_task_dev):
+        every instance's references and hint are sampled from its record at
+        tasks.t minus its delay; t["node_ref1"] and `hint` are not read.
         Asynchronous on `stream`."""
         B = int(t["x0"].shape[0])
         p = lambda k: C.c_void_p(int(t[k].data_ptr()) if t.get(k) is not None else 0)
@@ -378,10 +407,16 @@ class BatchedBoxFDDP:
         assert t.get("contact") is None or t["contact"].stride(0) == t["fn_meas"].stride(0)
         th = t.get("tau_hat")
         st = self._fleet_state(t)
-        args = (self._h, B, C.byref(params), C.byref(st), p("q"), p("v"), p("fn_meas"), p("contact"), p("ee_z"),
+        head = (self._h, B, C.byref(params), C.byref(st), p("q"), p("v"), p("fn_meas"), p("contact"), p("ee_z"),
                 int(t["q"].stride(0)), int(t["fn_meas"].stride(0)), p("tau_hat"),
-                int(th.stride(0)) if th is not None else 0, p("q_nom"), p("node_ref1"), int(bool(hint)), p("x0"),
-                p("surface"), p("inst_ref"), p("node_ref"), p("xs_init"), p("us_init"))
+                int(th.stride(0)) if th is not None else 0, p("q_nom"))
+        tail = (p("x0"), p("surface"), p("inst_ref"), p("node_ref"), p("xs_init"), p("us_init"))
+        if tasks is not None:
+            sp = C.byref(self._fleet_sched(t, sched)) if sched is not None else None
+            rc = self._lib.ffddp_fleet_pre_task_dev(*head, tasks, *tail, sp, C.c_void_p(stream if stream else 0))
+            self._check(rc, "ffddp_fleet_pre_task_dev")
+            return
+        args = head + (p("node_ref1"), int(bool(hint))) + tail
         if sched is not None:
             rc = self._lib.ffddp_fleet_pre_sched_dev(*args, self._fleet_sched(t, sched), C.c_void_p(stream if stream else 0))
             self._check(rc, "ffddp_fleet_pre_sched_dev")

@@ -607,6 +607,67 @@ int ffddp_fleet_inject_cmd_dev(ffddp_handle* h, int B, const ffddp_fleet_inject*
 int ffddp_fleet_noise_dev(ffddp_handle* h, int B, const uint64_t* seed, int k, double* z, uint64_t* words,
                           void* stream);
 
+/* Per-instance tasks and start delays: every instance carries a record of its
+ * own approach-then-circle task (ffddp/trajectory.py FleetTask, task_records)
+ * and the pre kernel samples that instance's N+1 node references and its
+ * contact hint itself, where ffddp_fleet_pre_dev takes one row shared by the
+ * instances.  A record is FFDDP_FLEET_TASK_W doubles, the closure constants of
+ * make_approach_then_circle and with_contact_hold as the host computed them:
+ *   [0..2] center, [3] radius, [4] omega, [5] z_contact, [6] t_pre (>= 0),
+ *   [7] t_approach (>= 1e-6), [8..10] p_start, [11..13] p_pre,
+ *   [14..16] p_contact_start, [17..19] p_hold (the base trajectory's position
+ *   at t_contact_phase), [20] t_hold_end (t_contact_phase + t_hold),
+ *   [21] delay in seconds (>= 0).
+ * The sampler evaluates a record at a task time: knot k at t + k dt_ocp (one
+ * multiply, one add; dt_ocp is the handle's), in the MuJoCo world, mapped to
+ * the Pinocchio frame as ffddp_build_problem_dev does (diag(-1, -1, 1), minus
+ * p_site_minus_frame).  It is compiled without contraction in trajectory.py's
+ * order and grouping: outside the circle phase (pre, approach, hold, negative
+ * task time, where the smoothstep clamps at the start pose) the entries are
+ * numpy's bits; in the circle phase the device sincos stands in for numpy's.
+ *
+ * ffddp_fleet_task_refs_dev: the sampler alone.  t [B] the instances' task
+ * times (the delay already subtracted; tasks.t is not read) -> node_ref
+ * [B][N+1][6] and hint [B], the surface flag at t[b].
+ *
+ * ffddp_fleet_pre_task_dev: ffddp_fleet_pre_dev (sched NULL) or
+ * ffddp_fleet_pre_sched_dev (sched given) with node_ref1 / contact_hint
+ * replaced per instance: instance b's task time is tasks.t - rec[b].delay (one
+ * subtraction), its hint the record's surface flag at that time, node_ref[b]
+ * the sampler's knots; everything else is the same code, so an instance given
+ * the same references and hint gets the same bits from both.
+ *
+ * Both: device pointers, asynchronous on `stream`.  FFDDP_E_INVALID for a
+ * null handle, a null record pointer or any other null required pointer, a
+ * scheduled call with a null since / age / need, B <= 0 and what
+ * ffddp_fleet_pre_dev refuses; FFDDP_E_CAPACITY for B > max_batch. */
+#define FFDDP_FLEET_TASK_W 22
+#define FFDDP_FLEET_TASK_CENTER 0
+#define FFDDP_FLEET_TASK_RADIUS 3
+#define FFDDP_FLEET_TASK_OMEGA 4
+#define FFDDP_FLEET_TASK_Z_CONTACT 5
+#define FFDDP_FLEET_TASK_T_PRE 6
+#define FFDDP_FLEET_TASK_T_APPROACH 7
+#define FFDDP_FLEET_TASK_P_START 8
+#define FFDDP_FLEET_TASK_P_PRE 11
+#define FFDDP_FLEET_TASK_P_CS 14
+#define FFDDP_FLEET_TASK_P_HOLD 17
+#define FFDDP_FLEET_TASK_T_HOLD_END 20
+#define FFDDP_FLEET_TASK_DELAY 21
+typedef struct ffddp_fleet_tasks {
+  double p_site_minus_frame[3]; /* the site calibration offset, Pinocchio frame */
+  double t;                     /* the tick's time (ffddp_fleet_pre_task_dev) */
+  const double* rec;            /* [B][FFDDP_FLEET_TASK_W] the records */
+} ffddp_fleet_tasks;
+int ffddp_fleet_task_refs_dev(ffddp_handle* h, int B, ffddp_fleet_tasks tasks, const double* t, double* node_ref,
+                              uint8_t* hint, void* stream);
+int ffddp_fleet_pre_task_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                             const double* q, const double* v, const double* fn_meas, const double* contact,
+                             const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
+                             const double* q_nom, ffddp_fleet_tasks tasks, double* x0, uint8_t* surface,
+                             double* inst_ref, double* node_ref, double* xs_init, double* us_init,
+                             const ffddp_fleet_sched* sched, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Closed-loop plant stand-in: the MuJoCo plant of the
  * reference's closed loop, FrankaMujocoSim.step() in torque mode

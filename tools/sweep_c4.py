@@ -14,6 +14,9 @@ wall time, closed-loop ticks/s).
   python tools/sweep_c4.py --device-loop 1 --device-noise philox  # ... or generated on the device
   python tools/sweep_c4.py --device-loop 1 --solve-period 2     # solve every 2nd tick, the feedback policy between
   python tools/sweep_c4.py --command-filter 1                   # _safe_tau's trust / rate / smoothing filter
+  python tools/sweep_c4.py --device-loop 1 --device-refs 1      # references sampled on the device from task records
+  python tools/sweep_c4.py --device-loop 1 --device-refs 1 --task-spread 0.3 0.3   # radius and speed vary per instance
+  python tools/sweep_c4.py --device-loop 1 --device-refs 1 --solve-period 4 --stagger 4   # start delays (b mod 4) dt
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/sweep_c4.py
 """
 import argparse
@@ -22,6 +25,8 @@ import os
 import sys
 import time
 from pathlib import Path
+
+import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import ffddp_path  # noqa: E402,F401
@@ -52,6 +57,12 @@ def main():
                     help="mpc_update_steps: solve every P-th tick, the feedback policy on the receding plan between")
     ap.add_argument("--command-filter", type=int, choices=(0, 1), default=0,
                     help="1: apply_command_filter (trust region, rate limit, smoothing of the command)")
+    ap.add_argument("--device-refs", type=int, choices=(0, 1), default=0,
+                    help="with --device-loop 1: sample every instance's references on the device from its task record")
+    ap.add_argument("--task-spread", type=float, nargs=2, default=None, metavar=("DR", "DW"),
+                    help="with --device-refs 1: per-instance radius 0.10 (1 + DR u1) and omega 1.5 (1 + DW u2), u in [-1, 1]")
+    ap.add_argument("--stagger", type=int, default=0,
+                    help="with --device-refs 1: instance b starts its task (b mod S) ticks late")
     ap.add_argument("--scenarios", nargs="+", default=list(ALL_SCENARIOS), help="scenarios to sweep (default: all 5)")
     a = ap.parse_args()
     import torch
@@ -67,7 +78,8 @@ def main():
     res = fleet.run_sweep(scenarios=tuple(a.scenarios), seeds=a.seeds, total_time=a.time, rank=rank, world=world,
                            device=local, verbose=(rank == 0), neg_step_rule=a.neg_step_rule, variant=a.variant, device_tick=bool(a.device_tick),
                            device_loop=bool(a.device_loop), device_noise=a.device_noise,
-                           solve_period=a.solve_period, command_filter=bool(a.command_filter))
+                           solve_period=a.solve_period, command_filter=bool(a.command_filter),
+                           device_refs=bool(a.device_refs), task_spread=a.task_spread, stagger=a.stagger)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -84,6 +96,14 @@ def main():
                 "instances": int(res["n_all"]), "ticks": res["ticks"], "wall_s": wall,
                 "closed_loop_ticks_per_s": res["n_all"] * res["ticks"] / wall,
                 "rank0_controller_s": res["controller_s"], "scenarios": fleet.scenario_table(names, m)}
+        line.update(device_refs=int(a.device_refs), task_spread=a.task_spread, stagger=a.stagger,
+                    loop_ms_per_tick=1.0e3 * res["wall_s"] / max(1, res["ticks"]))
+        if "solved" in res:  # the share of instances that solve per tick, once every instance has switched to contact
+            surf, share = res["surface"], res["solved"].mean(1)
+            k0 = int(np.max(np.argmax(surf, 0))) + 1 if surf.any(0).all() else len(share)
+            if k0 < len(share):
+                line.update(rank0_share_after_switch_mean=float(share[k0:].mean()),
+                            rank0_share_after_switch_max=float(share[k0:].max()), rank0_last_switch_tick=k0 - 1)
         print(json.dumps(line), flush=True)
         if a.out:
             Path(a.out).write_text(json.dumps(line, indent=1))
