@@ -43,6 +43,7 @@
 #include "ffddp_consts.hpp"
 #include "ffddp_group.hpp"
 #include "ffddp_inject.hpp"
+#include "ffddp_metrics.hpp"
 #include "ffddp_plant.hpp"
 #include "ffddp_primal_g8.hpp"
 #include "ffddp_rollout.hpp"
@@ -4542,6 +4543,29 @@ int ffddp_fleet_pre_task_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p
                        *p, *s, ffddp_fleet_sched{}, q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar, tau_hat,
                        (long)ld_tau_hat, q_nom, (const double*)nullptr, 0, x0, surface, inst_ref, node_ref, xs_init, us_init, tasks,
                        h->hc.dt);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// the sweep's task metrics (ffddp_metrics.hpp): one record per instance folded into acc [W][ld]
+int ffddp_fleet_metrics_dev(ffddp_handle* h, int B, int ld, const double* obs, int ld_obs, ffddp_fleet_tasks tasks,
+                            int rows, double dt, const double* p_ref, double ts, const double* t_phase, double fn_des,
+                            const double* info, const uint8_t* need, const int32_t* plant_fail, double* acc, void* stream) {
+  if (!h) return FFDDP_E_INVALID;
+  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_metrics_dev: B must be positive");
+  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  if (!obs || !t_phase || !acc || (!tasks.rec && !p_ref))
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_metrics_dev: null pointer");
+  if (ld < B || ld_obs < 48 || (tasks.rec && rows < 0))
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_metrics_dev: bad stride or record count");
+  HIPCHK(h, hipSetDevice(h->device));
+  const dim3 grid((unsigned)((B + METRICS_BLOCK - 1) / METRICS_BLOCK)), block(METRICS_BLOCK);
+  if (tasks.rec)
+    hipLaunchKernelGGL(k_fleet_metrics<true>, grid, block, 0, (hipStream_t)stream, B, (long)ld, obs, (long)ld_obs, tasks,
+                       rows, dt, p_ref, ts, t_phase, fn_des, info, need, plant_fail, acc);
+  else
+    hipLaunchKernelGGL(k_fleet_metrics<false>, grid, block, 0, (hipStream_t)stream, B, (long)ld, obs, (long)ld_obs, tasks,
+                       0, dt, p_ref, ts, t_phase, fn_des, info, need, plant_fail, acc);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

@@ -58,6 +58,7 @@ SYMBOLS = (
     "ffddp_fleet_noise_dev",
     "ffddp_fleet_task_refs_dev",
     "ffddp_fleet_pre_task_dev",
+    "ffddp_fleet_metrics_dev",
 )
 PLANT_OBS = 69
 NSTATS = 10
@@ -141,6 +142,12 @@ class FleetTasks(C.Structure):
     """ffddp_fleet_tasks: the site offset, the tick's time and the device pointer to the (B, FLEET_TASK_W) records."""
 
     _fields_ = [("p_site_minus_frame", C.c_double * 3), ("t", C.c_double), ("rec", C.c_void_p)]
+
+
+FLEET_METRICS_W = 17  # FFDDP_FLEET_METRICS_W: accumulator fields per instance (FFDDP_FLEET_METRICS_*, in order)
+FLEET_METRICS_FIELDS = ("n", "n_phase", "sum_tan2", "sum_tan2_phase", "sum_3d2", "sum_abs_tan", "sum_abs_fn_err",
+                        "max_fn", "sum_contact", "sum_contact_phase", "sum_fn_phase", "unstable_ticks",
+                        "neg_accepted_ticks", "not_ok_ticks", "solved_ticks", "max_err_3d", "plant_fail")
 
 
 class FleetParams(C.Structure):
@@ -477,6 +484,10 @@ def load() -> C.CDLL:
     lib.ffddp_fleet_pre_task_dev.argtypes = (fl + [vp] * 5 + [C.c_int, C.c_int, vp, C.c_int, vp, FleetTasks] + [vp] * 6
                                              + [C.POINTER(FleetSched), vp])
     lib.ffddp_fleet_pre_task_dev.restype = C.c_int
+    # the task metrics: B, ld, obs, ld_obs, tasks, rows, dt, p_ref, ts, t_phase, fn_des, info, need, plant_fail, acc
+    lib.ffddp_fleet_metrics_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, vp, C.c_int, FleetTasks, C.c_int, C.c_double,
+                                            vp, C.c_double, vp, C.c_double, vp, vp, vp, vp] + [vp]
+    lib.ffddp_fleet_metrics_dev.restype = C.c_int
     _lib = lib
     return lib
 

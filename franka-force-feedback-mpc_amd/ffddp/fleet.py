@@ -560,7 +560,8 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
               neg_step_rule: int = 0, variant: str = "classical", device_tick: bool = False,
               device_loop: bool = False, device_noise: Optional[str] = None, solve_period: int = 1,
               command_filter: bool = False, device_refs: bool = False,
-              task_spread: Optional[Tuple[float, float]] = None, stagger: int = 0) -> dict:
+              task_spread: Optional[Tuple[float, float]] = None, stagger: int = 0,
+              device_summary: bool = False, keep_logs: bool = True) -> dict:
     """Closed-loop sweep of len(scenarios) * seeds instances; this rank runs
     its contiguous shard.  Returns per-instance summary arrays (this shard).
     record: shard-local instance indices whose controller inputs (the plant
@@ -603,7 +604,16 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     uniform in [-1, 1] from default_rng([seed_b, 1]) (the q0 draws do not
     move).  stagger = S delays instance b (its index in the whole sweep) by
     (b mod S) dt.  Either implies device_refs.  The summary's reference
-    position and contact-phase window are then per instance, in task time."""
+    position and contact-phase window are then per instance, in task time.
+    device_summary, keep_logs (with device_loop only, NotImplementedError
+    otherwise): ``per_instance`` and ``solved_ticks`` come from sums the loop
+    accumulates on the device per tick (DeviceFleetLoop(metrics=True),
+    runlog.metrics_from_accumulators) instead of from the downloaded logs; the
+    sums run in tick order where numpy's means sum pairwise, so the two
+    summaries agree to summation rounding.  keep_logs = False (needs
+    device_summary, ValueError otherwise) drops the per-tick logs altogether
+    (logs=False): the run's memory no longer grows with its length and the
+    (ticks, B) outputs ``solved`` and ``surface`` are absent."""
     variant = str(variant).strip().lower()
     if variant not in ("classical", "ff"):
         raise ValueError(f"run_sweep: unknown variant {variant!r}")
@@ -623,6 +633,12 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     if device_refs and not device_loop:
         raise NotImplementedError("run_sweep: device_refs, task_spread and stagger need device_loop=True "
                                   "(the host fleets take one traj_fn)")
+    device_summary, keep_logs = bool(device_summary), bool(keep_logs)
+    if (device_summary or not keep_logs) and not device_loop:
+        raise NotImplementedError("run_sweep: device_summary and keep_logs need device_loop=True "
+                                  "(the host loop builds its summary as it goes)")
+    if not keep_logs and not device_summary:
+        raise ValueError("run_sweep: keep_logs=False needs device_summary=True")
     if device_noise is not None:
         if device_noise not in ("numpy", "philox"):
             raise ValueError(f"run_sweep: unknown device_noise {device_noise!r} (numpy or philox)")
@@ -672,7 +688,7 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
                                        delay=((lo + b) % stagger) * (0.001 * 5) if stagger else 0.0))  # BatchedPlant.dt
         out = _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, (R_site_from_pin_ee, p_off), total_time,
                                 neg_step_rule, device, t_cp, verbose, ucfgs, device_noise, solve_period,
-                                command_filter, tasks)
+                                command_filter, tasks, device_summary, keep_logs)
         out.update(names=names, seed=seed, shard=(lo, hi), n_all=n_all)
         return out
     plant = BatchedPlant(B, timestep=0.001, n_substeps=5, device=device)
@@ -792,12 +808,18 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     return out
 
 
+DEVICE_MEMORY: dict = {}  # the last device-loop sweep's memory figures (tools/sweep_c4.py reports them)
+
+
 def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, total_time, neg_step_rule, device, t_cp,
-                      verbose, ucfgs=None, noise=None, solve_period=1, command_filter=False, tasks=None) -> dict:
+                      verbose, ucfgs=None, noise=None, solve_period=1, command_filter=False, tasks=None,
+                      device_summary=False, keep_logs=True) -> dict:
     """run_sweep's loop on the device (fleet_loop.DeviceFleetLoop) and the
     host path's summary from the downloaded logs.  tasks: per-instance
     FleetTasks in place of traj; the summary's reference position and its
-    contact phase are then each instance's own, in its task time."""
+    contact phase are then each instance's own, in its task time.
+    device_summary: the summary from the loop's device accumulators instead;
+    keep_logs=False: the loop keeps no per-tick logs."""
     import torch
 
     from .fleet_loop import DeviceFleetLoop
@@ -812,15 +834,36 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     loop = DeviceFleetLoop(variant, B, traj if tasks is None else None, cfg, q0, tilt_deg=tilt, torque_scale=scale,
                            device=device, steps=steps,
                            calibration=calibration, timestep=timestep, n_substeps=n_substeps, uncertainty=ucfgs,
-                           noise=noise or "numpy", solve_period=int(solve_period), tasks=tasks)
+                           noise=noise or "numpy", solve_period=int(solve_period), tasks=tasks,
+                           metrics=bool(device_summary), logs=bool(keep_logs),
+                           t_contact_phase=float(t_cp) if device_summary and tasks is None else None)
     wall0 = time.perf_counter()
     loop.run(steps)
     torch.cuda.synchronize(loop.dev)
     wall = time.perf_counter() - wall0
     r = loop.results()
+    # device memory while the loop's arrays and the handles' workspaces are alive: torch's own peak, and what
+    # the device reports in use (torch's pool, the library's allocations and the runtime's)
+    free_b, total_b = torch.cuda.mem_get_info(loop.dev)
+    DEVICE_MEMORY.clear()
+    DEVICE_MEMORY.update(torch_peak_bytes=int(torch.cuda.max_memory_allocated(loop.dev)),
+                         device_used_bytes=int(total_b - free_b))
     loop.close()
     if np.any(r["plant_fail"]):
         raise RuntimeError("run_sweep(device_loop=True): a plant step failed (non-SPD mass matrix)")
+    if device_summary:  # B x FLEET_METRICS_W doubles came down; no series is built
+        s = r["summary"]
+        if verbose:
+            print(f"device loop: B={B} ticks={steps} | median rms |p-p_ref|={np.median(s['rms_3d_error']):.4f} m | "
+                  f"median max Fn={np.median(s['max_fn']):.2f} N | "
+                  f"ok={1.0 - float(np.sum(s['solve_not_ok_ticks'])) / max(B * steps, 1):.3f}", flush=True)
+        out = dict(per_instance={k: np.asarray(s[k], float) for k in SUMMARY_KEYS}, ticks=steps, wall_s=wall,
+                   controller_s=None, instances=B, variant=variant, solved_ticks=np.asarray(s["solved_ticks"], float))
+        if ucfgs is not None:
+            out.update(inject_a=r["inject_a"], inject_b=r["inject_b"])
+        if tasks is not None and keep_logs:
+            out.update(solved=r["solved"], surface=r["surface"] != 0)
+        return out
     # series[k]: the plant after tick k's command, at the time t_k + dt (the host loop's t += dt)
     t_after = np.array([float(t) + dt for t in r["t"]])
     obs = r["obs"][1:]

@@ -49,6 +49,16 @@ contact switch d ticks after its neighbours; ``_need_solve`` re-anchors its
 solve grid there, so delays that are no multiples of the period spread the
 fleet's solves over the ticks.  ``steps`` then sizes the logs only.
 
+With ``metrics=True`` the sweep's summary is accumulated on the device too:
+one more launch per tick (ffddp_fleet_metrics_dev, right after the plant step,
+before inject_obs and pre) folds the plant's record after the previous tick's
+command into per-instance running sums, maxima and counts, and ``results``
+returns them (``metrics``) with the statistics they determine (``summary``).
+With ``logs=False`` as well the per-tick logs shrink to rows reused every tick
+and, when neither a reference table nor a noise table is sized by ``steps``
+(``tasks`` given; no injector, or ``noise="philox"``), the loop runs for any
+number of ticks in constant memory.
+
 Not on the device, and so not supported here: ``run_sweep``'s ``record`` and
 any per-tick host callback; ``tick()`` lets a caller look between ticks at the price of its own
 synchronisation.
@@ -163,6 +173,13 @@ class DeviceFleetLoop:
     (None: no injector); the configs may differ by seed only.  noise: where
     the injector's normals come from, "numpy" (uncertainty.predraw's table of
     `steps` ticks, uploaded once; at most max_table_bytes) or "philox".
+    metrics: accumulate the summary's sums on the device (``acc``
+    (FLEET_METRICS_W, B), ``results()["metrics"]`` / ``["summary"]``);
+    t_contact_phase: the start of the contact phase the summary uses, a scalar
+    or one per instance (required with traj_fn; tasks carry their own).
+    logs: False (needs metrics, ValueError otherwise) keeps one row of each
+    per-tick log, reused every tick; ``steps`` then bounds the run only where
+    a table is sized by it (traj_fn, or the injector's numpy noise).
 
     ``S``: the controller state, ``T``: the solve's arrays, ``P``: the plant's
     (q, v, obs, tau_app, tau_filt, plane), ``J``: the injector's (row, a, b,
@@ -176,10 +193,16 @@ class DeviceFleetLoop:
                  timestep: float = 0.001, n_substeps: int = 5,
                  uncertainty: Optional[Sequence[Optional[UncertaintyProfileConfig]]] = None, noise: str = "numpy",
                  max_table_bytes: int = 1 << 30, solve_period: Optional[int] = None,
-                 tasks: Optional[Sequence[FleetTask]] = None):
+                 tasks: Optional[Sequence[FleetTask]] = None, metrics: bool = False, logs: bool = True,
+                 t_contact_phase=None):
         variant = str(variant).strip().lower()
         if variant not in ("classical", "ff"):
             raise ValueError(f"DeviceFleetLoop: unknown variant {variant!r}")
+        metrics, logs = bool(metrics), bool(logs)
+        if not logs and not metrics:
+            raise ValueError("DeviceFleetLoop: logs=False needs metrics=True (a run without either reports nothing)")
+        if metrics and tasks is None and t_contact_phase is None:
+            raise ValueError("DeviceFleetLoop: metrics=True with traj_fn needs t_contact_phase (tasks carry their own)")
         if (traj_fn is None) == (tasks is None):
             raise ValueError("DeviceFleetLoop: give either traj_fn (one task, tabulated on the host) or tasks "
                              "(per instance, sampled on the device)")
@@ -219,6 +242,11 @@ class DeviceFleetLoop:
         self.R_des = R.R_MJ_FROM_PIN.T @ R.vertical_down_rotation_mj() @ R_site.T
         self.plant = BatchedPlant(self.B, timestep=timestep, n_substeps=n_substeps, device=device)
         self.dt = self.plant.dt
+        self.metrics, self.logs, self.t0 = metrics, logs, float(t0)
+        # without logs nothing is sized by `steps` unless a table is: the references' or the injector's normals
+        self.unbounded = (not logs and tasks is not None
+                          and (ucfgs is None or noise == "philox" or all(c is None for c in ucfgs)))
+        self._t_run = (0, float(t0))
         self.tasks, self.task_rec, self.task_delay = tasks, None, None
         if tasks is None:
             self.refs, self.hints, self.times = reference_table(traj_fn, self.steps, self.dt, self.N, self.dt_ocp,
@@ -267,7 +295,8 @@ class DeviceFleetLoop:
                 self._init_inject(ucfgs, noise, max_table_bytes)
         # the scheduled tick: its counters, and one row of `need` per tick (the log `solved`)
         self.Q = dict(since=z(B, dtype=torch.int32), age=z(B, dtype=torch.int32))
-        self.log_need = z(self.steps, B, dtype=torch.uint8)
+        rows = self.steps if logs else 1  # without logs: one row of each, reused every tick
+        self.log_need = z(rows, B, dtype=torch.uint8)
         self.sched = None
         if self.period != 1 or bool(cfg.apply_command_filter):
             self.sched = _abi.fleet_sched(cfg, self.period, self.dt)
@@ -279,9 +308,24 @@ class DeviceFleetLoop:
         else:
             self.rec = up(self.task_rec)
             self.ktasks = self.solver.fleet_tasks(self.rec, p_off)
-        self.log_info = torch.full((self.steps, B, _abi.FLEET_INFO_W), float("nan"), **f64)
-        self.log_obs = torch.full((self.steps + 1, B, _abi.FLEET_LOG_W), float("nan"), **f64)
-        self.log_fail = z(self.steps + 1, B, dtype=torch.int32)
+        self.log_info = torch.full((rows, B, _abi.FLEET_INFO_W), float("nan"), **f64)
+        self.log_obs = torch.full((rows + 1 if logs else 1, B, _abi.FLEET_LOG_W), float("nan"), **f64)
+        self.log_fail = z(rows + 1, B, dtype=torch.int32)  # without logs: the start's row and the ticks'
+        # the task metrics (ffddp_fleet_metrics_dev): the accumulators, each instance's contact-phase start and,
+        # in table mode, the reference position after every tick (the sweep's traj(t + dt)[0])
+        self.acc = self.t_phase = self.p_tab = self.mtasks = None
+        self.m_k = 0  # ticks folded into the accumulators
+        if metrics:
+            from .runlog import metrics_accumulators
+
+            self.acc = up(metrics_accumulators(B))
+            if tasks is not None:
+                t_cp = [float(k.t_contact_phase) for k in tasks] if t_contact_phase is None else t_contact_phase
+                self.mtasks = self.solver.fleet_tasks(self.rec, np.zeros(3))
+            else:
+                t_cp = t_contact_phase
+                self.p_tab = up(np.stack([np.asarray(traj_fn(float(t) + self.dt)[0], float) for t in self.times]))
+            self.t_phase = up(np.broadcast_to(np.asarray(t_cp, float), (B,)))
         # the start: the controllers' first command is the bias torque on a level
         # table (run_sweep); then the tilted plant's first observation
         self._plant_step(integrate=False)
@@ -331,22 +375,54 @@ class DeviceFleetLoop:
         self.plant.close()
 
     # -- the tick ---------------------------------------------------------------------
+    def _row(self, k: int) -> int:
+        """Tick k's row of the per-tick arrays: its own, or without logs the one reused every tick."""
+        return k if self.logs else 0
+
+    def _tick_time(self, k: int) -> float:
+        """Tick k's time: t0 advanced k times by dt (the sweep's ``t += dt``), past the sized array too."""
+        if k < self.times.shape[0]:
+            return float(self.times[k])
+        kk, t = self._t_run if self._t_run[0] <= k else (0, self.t0)
+        while kk < k:
+            t += self.dt
+            kk += 1
+        self._t_run = (kk, t)
+        return t
+
     def _plant_step(self, integrate: bool = True):
+        """The plant step and, with ``metrics``, the fold of the record it leaves -- the observation after tick
+        k - 1's command -- into the accumulators: the plant's own record, as the log row, whatever the injector
+        shows the controllers."""
         P = self.P
-        self.plant.step_dev(P["q"], P["v"], P["tau_app"], P["plane"], P["obs"], fail=self.log_fail[self.k if integrate else 0],
-                            integrate=integrate, stream=self._stream)
+        fail = self.log_fail[(self.k if self.logs else 1) if integrate else 0]
+        self.plant.step_dev(P["q"], P["v"], P["tau_app"], P["plane"], P["obs"], fail=fail, integrate=integrate,
+                            stream=self._stream)
+        if self.metrics and integrate and self.m_k < self.k:
+            j = self.k - 1
+            r = self._row(j)
+            kw = dict(info=self.log_info[r], need=self.log_need[r] if self.sched is not None else None, plant_fail=fail,
+                      stream=self._stream)
+            if self.mtasks is not None:
+                self.mtasks.t = self._tick_time(j)
+                kw.update(tasks=self.mtasks, dt=self.dt)
+            else:
+                kw.update(p_ref=self.p_tab[j], ts=float(self.times[j]) + self.dt)
+            self.solver.fleet_metrics_dev(self.acc, P["obs"], self.t_phase, float(self.cfg.fn_des), **kw)
+            self.m_k = self.k
 
     def _enqueue_tick(self):
         k, T = self.k, self.T
-        if k >= self.steps:
+        if k >= self.steps and not self.unbounded:
             raise RuntimeError(f"DeviceFleetLoop: the loop was sized for {self.steps} ticks")
         if not self._stepped:
             self._plant_step()
-        T["info"], T["log_obs"] = self.log_info[k], self.log_obs[k]
+        r = self._row(k)
+        T["info"], T["log_obs"] = self.log_info[r], self.log_obs[r]
         if self.ktasks is None:
             T["node_ref1"], hint = self.ref_table[k], bool(self.hints[k])
         else:
-            self.ktasks.t, hint = float(self.times[k]), False
+            self.ktasks.t, hint = self._tick_time(k), False
         if self.inject is not None:
             self.solver.fleet_inject_obs_dev(self.J, self.inject, k, z=None if self.z_table is None else self.z_table[k],
                                              stream=self._stream)
@@ -355,7 +431,7 @@ class DeviceFleetLoop:
             self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream)
             self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream)
         else:
-            T["need"] = self.log_need[k]
+            T["need"] = self.log_need[r]
             self.solver.fleet_pre_dev(T, self.params, hint, stream=self._stream, sched=self.sched, tasks=self.ktasks)
             self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream,
                                   active=T["need"])
@@ -389,6 +465,10 @@ class DeviceFleetLoop:
             s.update({k: self.J[k].cpu().numpy().copy() for k in _INJECT_KEYS})
         s.update({k: self.Q[k].cpu().numpy().copy() for k in _SCHED_KEYS})
         s.update(k=self.k, stepped=self._stepped)
+        if self.metrics:  # the accumulators, the ticks folded, and the last tick's rows its fold will still read
+            r = self._row(max(self.k - 1, 0))
+            s.update(metrics=self.acc.cpu().numpy().copy(), metrics_k=self.m_k,
+                     metrics_info=self.log_info[r].cpu().numpy().copy(), metrics_need=self.log_need[r].cpu().numpy().copy())
         return s
 
     def load_state(self, s: dict):
@@ -404,6 +484,16 @@ class DeviceFleetLoop:
             if k in s:  # a state saved without them: a loop that solves every tick
                 self.Q[k].copy_(torch.from_numpy(np.ascontiguousarray(s[k])).to(self.dev))
         self.k, self._stepped = int(s["k"]), bool(s["stepped"])
+        if self.metrics:
+            if "metrics" in s:
+                self.acc.copy_(torch.from_numpy(np.ascontiguousarray(s["metrics"])).to(self.dev))
+                self.m_k = int(s["metrics_k"])
+                if self.k > 0:
+                    r = self._row(self.k - 1)
+                    self.log_info[r].copy_(torch.from_numpy(np.ascontiguousarray(s["metrics_info"])).to(self.dev))
+                    self.log_need[r].copy_(torch.from_numpy(np.ascontiguousarray(s["metrics_need"])).to(self.dev))
+            else:  # a state saved without them: the accumulators go on with the ticks run from here
+                self.m_k = self.k
         torch.cuda.synchronize(self.dev)
 
     def results(self) -> dict:
@@ -417,13 +507,30 @@ class DeviceFleetLoop:
         ``tasks`` also ``t_task`` (k, B): each instance's task time per tick
         (t minus its delay, the subtraction the pre kernel does); with
         ``uncertainty`` also ``inject_a``, ``inject_b`` (B,): the injectors'
-        actuation gain and bias, NaN where there is none."""
+        actuation gain and bias, NaN where there is none.  With ``metrics``
+        also ``metrics`` (FLEET_METRICS_W, B): the accumulators over the k
+        ticks (the closing plant step's record is folded in here, once), and
+        ``summary``: runlog.metrics_from_accumulators of them.  With
+        ``logs=False`` only ``ticks`` (k), ``plant_fail``, ``metrics``,
+        ``summary`` and the injectors' constants: no per-tick array exists."""
         torch, k = self.torch, self.k
         if not self._stepped and k > 0:
             self._plant_step()
             self._stepped = True
-        self.log_obs[k].copy_(self.P["obs"][:, [28, 29, 30, 46, 47]])
+        if self.logs:
+            self.log_obs[k].copy_(self.P["obs"][:, [28, 29, 30, 46, 47]])
         torch.cuda.synchronize(self.dev)
+        if self.metrics:
+            from .runlog import metrics_from_accumulators
+
+            acc = self.acc.cpu().numpy()[:, : self.B].copy()
+            m = dict(metrics=acc, summary=metrics_from_accumulators(acc))
+        if not self.logs:
+            fails = self.log_fail[0].cpu().numpy() + acc[_abi.FLEET_METRICS_FIELDS.index("plant_fail")].astype(np.int64)
+            out = dict(ticks=k, plant_fail=fails, **m)
+            if self.inject_a is not None:
+                out.update(inject_a=self.inject_a.copy(), inject_b=self.inject_b.copy())
+            return out
         info = self.log_info[:k].cpu().numpy()
         out = dict(info=info, obs=self.log_obs[: k + 1].cpu().numpy(), t=self.times[:k].copy(),
                    plant_fail=self.log_fail[: k + 1].sum(0).cpu().numpy(),
@@ -434,4 +541,6 @@ class DeviceFleetLoop:
             out.update(inject_a=self.inject_a.copy(), inject_b=self.inject_b.copy())
         if self.task_delay is not None:
             out["t_task"] = self.times[:k, None] - self.task_delay[None, :]
+        if self.metrics:
+            out.update(m)
         return out

@@ -15,6 +15,11 @@ scripts read our runs unchanged:
 * ``summary_metrics`` — the end-of-run statistics of
   ``run_classical.py:513-535`` (and the identical block of
   ``run_force_feedback.py``), returned as the dict ``set_meta`` receives.
+* ``accumulate_metrics`` / ``metrics_from_accumulators`` — the same
+  statistics for a fleet from per-instance running sums, maxima and counts,
+  one record per instance folded in per tick: the numpy restatement of the
+  device kernel behind ``ffddp_fleet_metrics_dev``, which lets
+  a sweep of any length report its summary without keeping the series.
 """
 from __future__ import annotations
 
@@ -27,7 +32,12 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-__all__ = ["RunLogger", "jsonable", "summary_metrics"]
+from ._abi import FLEET_METRICS_FIELDS, FLEET_METRICS_W
+
+__all__ = ["RunLogger", "jsonable", "summary_metrics", "metrics_accumulators", "accumulate_metrics",
+           "metrics_from_accumulators"]
+
+_F = {k: i for i, k in enumerate(FLEET_METRICS_FIELDS)}  # accumulator field -> row
 
 
 def jsonable(x: Any) -> Any:
@@ -178,3 +188,92 @@ def summary_metrics(t, err_tan, err_3d, fn_meas, contact, fn_des: float, t_conta
         "fn_mean_contact_phase": float(np.mean(fn_phase)) if fn_phase.size else nan,
         "contact_phase_start_s": float(t_contact_phase),
     }
+
+
+# -- the same statistics from running sums (include/ffddp.h: ffddp_fleet_metrics_dev) --------
+def metrics_accumulators(B: int, ld: Optional[int] = None) -> np.ndarray:
+    """Fresh accumulators (FLEET_METRICS_W, ld >= B), field-major: zero, max_fn at -inf."""
+    acc = np.zeros((FLEET_METRICS_W, int(B) if ld is None else int(ld)))
+    acc[_F["max_fn"]] = -np.inf
+    return acc
+
+
+def accumulate_metrics(acc: np.ndarray, obs, p_ref, ts, t_phase, fn_des: float, info=None, need=None,
+                       plant_fail=None) -> np.ndarray:
+    """One ffddp_fleet_metrics_dev call in numpy, term for term in the kernel's
+    (and so ``summary_metrics``' callers') order: fold one plant record per
+    instance into acc (FLEET_METRICS_W, ld >= B), in place.
+
+    obs (B, >= 48): the records after a tick's command ([28..30] site position,
+    [46] normal force, [47] contact flag); p_ref (3,) or (B, 3): the reference
+    position at the series time ts (scalar or (B,)); t_phase (B,): the start of
+    each instance's contact phase; info (B, FLEET_INFO_W) or None (the four
+    solver counters are left); need (B,) or None (every instance solved);
+    plant_fail (B,) or None.  Called once per tick the sums are sequential in
+    tick order, as the kernel's are."""
+    obs = np.asarray(obs, dtype=float)
+    B = obs.shape[0]
+    p_ref = np.broadcast_to(np.asarray(p_ref, dtype=float), (B, 3))
+    ts = np.broadcast_to(np.asarray(ts, dtype=float), (B,))
+    a = acc[:, :B]
+    with np.errstate(invalid="ignore"):
+        ex, ey, ez = (obs[:, 28 + i] - p_ref[:, i] for i in range(3))
+        s2 = ex * ex + ey * ey
+        et, e3 = np.sqrt(s2), np.sqrt(s2 + ez * ez)
+        fn = obs[:, 46] * (obs[:, 47] > 0.5)
+        contact = (fn > 0.5).astype(float)
+        phase = ts >= np.asarray(t_phase, dtype=float)
+        et2 = et * et
+        a[_F["n"]] += 1.0
+        a[_F["sum_tan2"]] += et2
+        a[_F["sum_3d2"]] += e3 * e3
+        a[_F["sum_abs_tan"]] += np.abs(et)
+        a[_F["sum_abs_fn_err"]] += np.abs(fn - float(fn_des))
+        a[_F["max_fn"]] = np.maximum(a[_F["max_fn"]], fn)  # propagates NaN, as np.max
+        a[_F["sum_contact"]] += contact
+        a[_F["max_err_3d"]] = np.maximum(a[_F["max_err_3d"]], e3)
+        a[_F["n_phase"], phase] += 1.0
+        a[_F["sum_tan2_phase"], phase] += et2[phase]
+        a[_F["sum_contact_phase"], phase] += contact[phase]
+        a[_F["sum_fn_phase"], phase] += fn[phase]
+    if info is not None:
+        info = np.asarray(info, dtype=float)
+        a[_F["unstable_ticks"]] += info[:, 4] != 0
+        a[_F["neg_accepted_ticks"]] += info[:, 7] > 0
+        a[_F["not_ok_ticks"]] += info[:, 0] == 0
+        a[_F["solved_ticks"]] += 1.0 if need is None else (np.asarray(need) != 0)
+    if plant_fail is not None:
+        a[_F["plant_fail"]] += np.asarray(plant_fail, dtype=float)
+    return acc
+
+
+def metrics_from_accumulators(acc) -> Dict[str, np.ndarray]:
+    """``summary_metrics``' statistics, per instance, from the accumulators
+    (FLEET_METRICS_W, B): every key the running sums determine -- the
+    tracking, force and contact figures by ``summary_metrics``' formulas
+    (sqrt(sum / n), (1 - mean) * 100), NaN where it gives NaN (no sample, or
+    none in the contact phase) -- plus ``max_err_3d`` and the sweep's counters
+    ``unstable_ticks``, ``neg_accepted_ticks``, ``solve_not_ok_ticks``,
+    ``solved_ticks`` as counted."""
+    acc = np.asarray(acc, dtype=float)
+    f = {k: acc[i] for k, i in _F.items()}
+    nan = np.full(acc.shape[1], np.nan)
+    has, has_p = f["n"] > 0, f["n_phase"] > 0
+    n, n_p = np.where(has, f["n"], 1.0), np.where(has_p, f["n_phase"], 1.0)
+    with np.errstate(invalid="ignore"):
+        return {
+            "avg_abs_position_err": np.where(has, f["sum_abs_tan"] / n, nan),
+            "avg_abs_force_err": np.where(has, f["sum_abs_fn_err"] / n, nan),
+            "rms_tangential_error": np.where(has, np.sqrt(f["sum_tan2"] / n), nan),
+            "rms_tangential_error_contact_phase": np.where(has_p, np.sqrt(f["sum_tan2_phase"] / n_p), nan),
+            "rms_3d_error": np.where(has, np.sqrt(f["sum_3d2"] / n), nan),
+            "max_fn": np.where(has, f["max_fn"], nan),
+            "contact_loss_pct": np.where(has, (1.0 - f["sum_contact"] / n) * 100.0, nan),
+            "contact_loss_contact_phase_pct": np.where(has_p, (1.0 - f["sum_contact_phase"] / n_p) * 100.0, nan),
+            "fn_mean_contact_phase": np.where(has_p, f["sum_fn_phase"] / n_p, nan),
+            "max_err_3d": np.where(has, f["max_err_3d"], nan),
+            "unstable_ticks": f["unstable_ticks"].copy(),
+            "neg_accepted_ticks": f["neg_accepted_ticks"].copy(),
+            "solve_not_ok_ticks": f["not_ok_ticks"].copy(),
+            "solved_ticks": f["solved_ticks"].copy(),
+        }

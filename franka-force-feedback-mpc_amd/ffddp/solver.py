@@ -383,6 +383,34 @@ class BatchedBoxFDDP:
         )
         self._check(rc, "ffddp_fleet_task_refs_dev")
 
+    def fleet_metrics_dev(self, acc, obs, t_phase, fn_des: float, tasks: _abi.FleetTasks = None, dt: float = 0.0,
+                          rows: int = None, p_ref=None, ts: float = 0.0, info=None, need=None, plant_fail=None,
+                          stream=None):
+        """Fold one plant record per instance into the task-metric accumulators
+        (ffddp_fleet_metrics_dev; runlog.accumulate_metrics is the same step in
+        numpy).  acc (_abi.FLEET_METRICS_W, ld >= B) float64, field-major; obs
+        (B, >= 48) float64 rows laid out as the plant's records (a strided view
+        will do); t_phase (B,) float64.  The reference position: tasks
+        (fleet_tasks; instance b's own record at (tasks.t - its delay) + dt,
+        `rows` records, by default B) or p_ref (3,) float64 on the device with
+        the series time ts.  info (B, FLEET_INFO_W), need (B,) uint8 and
+        plant_fail (B,) int32 are optional.  Asynchronous on `stream`."""
+        B = int(obs.shape[0])
+        assert acc.dim() == 2 and acc.shape[0] == _abi.FLEET_METRICS_W and acc.is_contiguous() and acc.shape[1] >= B
+        assert obs.stride(1) == 1 and obs.shape[1] >= 48 and tuple(t_phase.shape) == (B,) and t_phase.is_contiguous()
+        assert str(acc.dtype) == str(obs.dtype) == str(t_phase.dtype) == "torch.float64"
+        assert info is None or (tuple(info.shape) == (B, _abi.FLEET_INFO_W) and info.is_contiguous())
+        assert need is None or (tuple(need.shape) == (B,) and need.is_contiguous())
+        assert plant_fail is None or (tuple(plant_fail.shape) == (B,) and plant_fail.is_contiguous())
+        assert p_ref is None or (p_ref.numel() == 3 and p_ref.is_contiguous())
+        p = lambda a: C.c_void_p(int(a.data_ptr()) if a is not None else 0)  # noqa: E731
+        rc = self._lib.ffddp_fleet_metrics_dev(
+            self._h, B, int(acc.shape[1]), p(obs), int(obs.stride(0)), tasks if tasks is not None else _abi.FleetTasks(),
+            B if rows is None else int(rows), float(dt), p(p_ref), float(ts), p(t_phase), float(fn_des), p(info),
+            p(need), p(plant_fail), p(acc), C.c_void_p(stream if stream else 0),
+        )
+        self._check(rc, "ffddp_fleet_metrics_dev")
+
     def fleet_pre_dev(self, t, params: _abi.FleetParams, hint: bool = False, stream=None, sched: _abi.FleetSched = None,
                       tasks: _abi.FleetTasks = None):
         """Everything a fleet tick does before the solve, for B instances in one

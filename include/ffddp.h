@@ -668,6 +668,76 @@ int ffddp_fleet_pre_task_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p
                              double* inst_ref, double* node_ref, double* xs_init, double* us_init,
                              const ffddp_fleet_sched* sched, void* stream);
 
+/* The sweep's task metrics accumulated on the device: one call folds one plant
+ * record per instance -- the observation after a tick's command -- into
+ * per-instance running sums, maxima and counts, everything the sweep's summary
+ * (ffddp/runlog.py summary_metrics, the solver-health counters of
+ * ffddp/fleet.py) is made of, so a run of any length returns
+ * FFDDP_FLEET_METRICS_W doubles per instance instead of its per-tick logs.
+ *
+ * acc [FFDDP_FLEET_METRICS_W][ld] is field-major with ld >= B (instance b's
+ * field f at acc[f * ld + b]; columns b >= B are not touched).  The caller
+ * zeroes it before the first call, MAX_FN to -inf.  obs: rows with stride
+ * ld_obs (>= 48) laid out as the plant's records; [28..30] the site position,
+ * [46] the normal force, [47] the contact flag are read.  Per call and instance
+ *   fn = obs[46] * (obs[47] > 0.5), contact = fn > 0.5,
+ *   e = obs[28..30] - p_ref, err_tan = sqrt(ex^2 + ey^2),
+ *   err_3d = sqrt((ex^2 + ey^2) + ez^2), in_phase = ts >= t_phase[b]
+ * and the fields take
+ *   N += 1, SUM_TAN2 += err_tan^2, SUM_3D2 += err_3d^2 (the squares of the
+ *   rounded norms), SUM_ABS_TAN += |err_tan|, SUM_ABS_FN_ERR += |fn - fn_des|,
+ *   MAX_FN = max(MAX_FN, fn), SUM_CONTACT += contact,
+ *   MAX_ERR_3D = max(MAX_ERR_3D, err_3d); when in_phase: N_PHASE += 1,
+ *   SUM_TAN2_PHASE += err_tan^2, SUM_CONTACT_PHASE += contact,
+ *   SUM_FN_PHASE += fn;
+ *   with info (the tick's [B][FFDDP_FLEET_INFO_W] row of ffddp_fleet_post_dev;
+ *   NULL: these four are not touched): UNSTABLE_TICKS += info[4] != 0,
+ *   NEG_ACCEPTED_TICKS += info[7] > 0, NOT_OK_TICKS += info[0] == 0,
+ *   SOLVED_TICKS += need[b] != 0 (need [B], the scheduled tick's mask; NULL:
+ *   every instance solved);
+ *   with plant_fail (ffddp_plant_step_dev's [B] flags of the step that wrote
+ *   obs; may be NULL): PLANT_FAIL += plant_fail[b].
+ * The reference position p_ref (MuJoCo world) and the series time ts come from
+ * one of two sources.  tasks.rec non-NULL: instance b's own record, ts =
+ * (tasks.t - rec[b].delay) + dt in that order, p_ref the sampler's knot 0 at
+ * ts (the code ffddp_fleet_pre_task_dev inlines, the frame map undone, which
+ * is exact); `rows` is the number of records, an instance b >= rows has no
+ * reference (NaN: its error fields turn NaN, its force fields go on) and no
+ * record is read beyond them; p_ref and ts are ignored.  tasks.rec NULL: the
+ * shared device row p_ref [3] and the scalar ts (rows, dt, tasks.t ignored).
+ * t_phase [B]: the start of each instance's contact phase in its series time.
+ * The terms are compiled without contraction in the host summary's order and
+ * grouping (IEEE add, multiply, square root: numpy's bits, given the same
+ * reference); NaN propagates into the sums and, as in numpy.max, into both
+ * maxima.  Every sum is sequential in call order: reproducible run to run.
+ * One lane per instance, no shared memory, no atomics.
+ *
+ * Device pointers, asynchronous on `stream`.  FFDDP_E_INVALID for a null
+ * handle, a null obs / t_phase / acc, neither a record pointer nor p_ref,
+ * ld < B, ld_obs < 48, rows < 0 or B <= 0; FFDDP_E_CAPACITY for B > max_batch. */
+#define FFDDP_FLEET_METRICS_W 17
+#define FFDDP_FLEET_METRICS_N 0
+#define FFDDP_FLEET_METRICS_N_PHASE 1
+#define FFDDP_FLEET_METRICS_SUM_TAN2 2
+#define FFDDP_FLEET_METRICS_SUM_TAN2_PHASE 3
+#define FFDDP_FLEET_METRICS_SUM_3D2 4
+#define FFDDP_FLEET_METRICS_SUM_ABS_TAN 5
+#define FFDDP_FLEET_METRICS_SUM_ABS_FN_ERR 6
+#define FFDDP_FLEET_METRICS_MAX_FN 7
+#define FFDDP_FLEET_METRICS_SUM_CONTACT 8
+#define FFDDP_FLEET_METRICS_SUM_CONTACT_PHASE 9
+#define FFDDP_FLEET_METRICS_SUM_FN_PHASE 10
+#define FFDDP_FLEET_METRICS_UNSTABLE_TICKS 11
+#define FFDDP_FLEET_METRICS_NEG_ACCEPTED_TICKS 12
+#define FFDDP_FLEET_METRICS_NOT_OK_TICKS 13
+#define FFDDP_FLEET_METRICS_SOLVED_TICKS 14
+#define FFDDP_FLEET_METRICS_MAX_ERR_3D 15
+#define FFDDP_FLEET_METRICS_PLANT_FAIL 16
+int ffddp_fleet_metrics_dev(ffddp_handle* h, int B, int ld, const double* obs, int ld_obs, ffddp_fleet_tasks tasks,
+                            int rows, double dt, const double* p_ref, double ts, const double* t_phase, double fn_des,
+                            const double* info, const uint8_t* need, const int32_t* plant_fail, double* acc,
+                            void* stream);
+
 /* ---------------------------------------------------------------------------
  * Closed-loop plant stand-in: the MuJoCo plant of the
  * reference's closed loop, FrankaMujocoSim.step() in torque mode

@@ -17,6 +17,8 @@ wall time, closed-loop ticks/s).
   python tools/sweep_c4.py --device-loop 1 --device-refs 1      # references sampled on the device from task records
   python tools/sweep_c4.py --device-loop 1 --device-refs 1 --task-spread 0.3 0.3   # radius and speed vary per instance
   python tools/sweep_c4.py --device-loop 1 --device-refs 1 --solve-period 4 --stagger 4   # start delays (b mod 4) dt
+  python tools/sweep_c4.py --device-loop 1 --device-refs 1 --device-summary 1 --keep-logs 0   # the summary's sums on the
+                                                               # device, no per-tick logs: any --time in constant memory
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/sweep_c4.py
 """
 import argparse
@@ -63,6 +65,10 @@ def main():
                     help="with --device-refs 1: per-instance radius 0.10 (1 + DR u1) and omega 1.5 (1 + DW u2), u in [-1, 1]")
     ap.add_argument("--stagger", type=int, default=0,
                     help="with --device-refs 1: instance b starts its task (b mod S) ticks late")
+    ap.add_argument("--device-summary", type=int, choices=(0, 1), default=0,
+                    help="with --device-loop 1: accumulate the summary's sums on the device, one more launch per tick")
+    ap.add_argument("--keep-logs", type=int, choices=(0, 1), default=1,
+                    help="with --device-summary 1: 0 keeps no per-tick logs (memory no longer grows with --time)")
     ap.add_argument("--scenarios", nargs="+", default=list(ALL_SCENARIOS), help="scenarios to sweep (default: all 5)")
     a = ap.parse_args()
     import torch
@@ -79,7 +85,8 @@ def main():
                            device=local, verbose=(rank == 0), neg_step_rule=a.neg_step_rule, variant=a.variant, device_tick=bool(a.device_tick),
                            device_loop=bool(a.device_loop), device_noise=a.device_noise,
                            solve_period=a.solve_period, command_filter=bool(a.command_filter),
-                           device_refs=bool(a.device_refs), task_spread=a.task_spread, stagger=a.stagger)
+                           device_refs=bool(a.device_refs), task_spread=a.task_spread, stagger=a.stagger,
+                           device_summary=bool(a.device_summary), keep_logs=bool(a.keep_logs))
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -98,6 +105,8 @@ def main():
                 "rank0_controller_s": res["controller_s"], "scenarios": fleet.scenario_table(names, m)}
         line.update(device_refs=int(a.device_refs), task_spread=a.task_spread, stagger=a.stagger,
                     loop_ms_per_tick=1.0e3 * res["wall_s"] / max(1, res["ticks"]))
+        line.update(device_summary=int(a.device_summary), keep_logs=int(a.keep_logs),
+                    wall_ms_per_tick=1.0e3 * wall / max(1, res["ticks"]), rank0_device_memory=dict(fleet.DEVICE_MEMORY) or None)
         if "solved" in res:  # the share of instances that solve per tick, once every instance has switched to contact
             surf, share = res["surface"], res["solved"].mean(1)
             k0 = int(np.max(np.argmax(surf, 0))) + 1 if surf.any(0).all() else len(share)
