@@ -58,11 +58,31 @@ __device__ __forceinline__ void inject_philox_normals(uint64_t seed, int k, int 
   inject_box_muller(w[2], w[3], zn[2], zn[3]);
 }
 
-// observation_for_controller
+// A row's delay for a ring of `depth` + 1 slots: the scalar when no array is given, else the row's entry
+// clamped into [0, depth], so that no value can index outside the ring.
+__device__ __forceinline__ int inject_row_delay(const int32_t* __restrict__ d, int r, int depth) {
+  if (!d) return depth;
+  const int x = d[r];
+  return x < 0 ? 0 : (x > depth ? depth : x);
+}
+
+// A row's delays and sigmas (ffddp_fleet_inject_rows) over the scalars of ffddp_fleet_inject: the ring moduli
+// no, nc and the sigma triple sg.  An instance with the delay d uses the slots 0..d of its ring column.
+__device__ __forceinline__ void inject_row_profile(const ffddp_fleet_inject& I, int r, int& no, int& nc, double sg[3],
+                                                   const ffddp_fleet_inject_rows& W) {
+  no = inject_row_delay(W.d_obs, r, I.d_obs) + 1;
+  nc = inject_row_delay(W.d_cmd, r, I.d_cmd) + 1;
+  if (W.sigma) sg[0] = W.sigma[3 * r], sg[1] = W.sigma[3 * r + 1], sg[2] = W.sigma[3 * r + 2];
+}
+
+// observation_for_controller.  k_fleet_inject_obs<false>: the scalars of I for every instance;
+// k_fleet_inject_obs<true, ffddp_fleet_inject_rows>: the trailing argument carries each row's own delays and
+// sigmas.  The pack keeps the first instantiation's arguments, and so its code, what they were.
+template <bool ROWS, class... RowArgs>
 __global__ __launch_bounds__(INJECT_BLOCK) void k_fleet_inject_obs(
     int B, ffddp_fleet_inject I, int k, const double* __restrict__ z, const double* __restrict__ q,
     const double* __restrict__ v, long ld, const double* __restrict__ tau_filt, double* __restrict__ qv_ctrl,
-    double* __restrict__ tau_hat, double* __restrict__ tau_ctrl) {
+    double* __restrict__ tau_hat, double* __restrict__ tau_ctrl, RowArgs... row_args) {
 #pragma clang fp contract(off)
   const long t = (long)blockIdx.x * INJECT_BLOCK + threadIdx.x;
   if (t >= (long)B * NU) return;
@@ -82,7 +102,9 @@ __global__ __launch_bounds__(INJECT_BLOCK) void k_fleet_inject_obs(
     return;
   }
   // the delay line: deque(maxlen).append, the oldest slot takes the newest entry
-  const int no = I.d_obs + 1, nc = I.d_cmd + 1;
+  int no = I.d_obs + 1, nc = I.d_cmd + 1;
+  double sg[3] = {I.sigma_q, I.sigma_dq, I.sigma_tau};
+  if constexpr (ROWS) inject_row_profile(I, r, no, nc, sg, row_args...);
   const long so = (long)B * INJECT_QV;
   double* ring = I.obs_ring + b * INJECT_QV;
   if (k == 0) {
@@ -102,11 +124,11 @@ __global__ __launch_bounds__(INJECT_BLOCK) void k_fleet_inject_obs(
     const double* zr = z + (long)r * FFDDP_INJECT_NZ;
     for (int i = 0; i < 4; ++i) zn[i] = zr[i * NU + j];
   }
-  out[j] = qo + (0.0 + I.sigma_q * zn[0]);
-  out[NQ + j] = vo + (0.0 + I.sigma_dq * zn[1]);
+  out[j] = qo + (0.0 + sg[0] * zn[0]);
+  out[NQ + j] = vo + (0.0 + sg[1] * zn[1]);
   // the torque measurement and its filter (_tau_hat on the oldest command)
   const double cmd = I.cmd_ring[(long)(k % nc) * B * NU + t];
-  const double th = I.a[r] * cmd + I.b[r] + (0.0 + I.sigma_tau * zn[2]);
+  const double th = I.a[r] * cmd + I.b[r] + (0.0 + sg[2] * zn[2]);
   const double tf = (1.0 - I.lpf) * I.tau_hat_filt[t] + I.lpf * th;
   I.tau_hat_filt[t] = tf;
   I.z_cmd[t] = zn[3];
@@ -114,21 +136,24 @@ __global__ __launch_bounds__(INJECT_BLOCK) void k_fleet_inject_obs(
   if (tau_ctrl) tau_ctrl[t] = tf;
 }
 
-// command_for_plant
+// command_for_plant; the instantiations as k_fleet_inject_obs's
+template <bool ROWS, class... RowArgs>
 __global__ __launch_bounds__(INJECT_BLOCK) void k_fleet_inject_cmd(int B, ffddp_fleet_inject I, int k,
                                                                    const double* __restrict__ tau_cmd,
-                                                                   double* __restrict__ tau_app) {
+                                                                   double* __restrict__ tau_app, RowArgs... row_args) {
 #pragma clang fp contract(off)
   const long t = (long)blockIdx.x * INJECT_BLOCK + threadIdx.x;
   if (t >= (long)B * NU) return;
   const long b = t / NU;
   const int r = I.row[b];
   if (r < 0 || r >= I.rows) return;  // post's scale * tau_cmd stays
-  const int nc = I.d_cmd + 1;
+  int no = 1, nc = I.d_cmd + 1;
+  double sg[3] = {I.sigma_q, I.sigma_dq, I.sigma_tau};
+  if constexpr (ROWS) inject_row_profile(I, r, no, nc, sg, row_args...);
   const long sc = (long)B * NU;
   I.cmd_ring[(long)(k % nc) * sc + t] = tau_cmd[t];
   const double cmd = I.cmd_ring[(long)((k + 1) % nc) * sc + t];
-  tau_app[t] = I.a[r] * cmd + I.b[r] + (0.0 + I.sigma_tau * I.z_cmd[t]);
+  tau_app[t] = I.a[r] * cmd + I.b[r] + (0.0 + sg[2] * I.z_cmd[t]);
 }
 
 // the Philox source alone: z [B][28] and, when asked for, the raw blocks [B][7][4]

@@ -2384,11 +2384,29 @@ __global__ __launch_bounds__(64) void k_finalize(const DevConsts* __restrict__ C
   fn_pred[(long)b * 2 + knot] = (NC == 1) ? P.lam[0] : P.lam[2];
 }
 
-// closed-loop plant stand-in: one thread per instance (ffddp_plant.hpp)
+// A lane's physics row (ffddp_plant_set_instance_params) over a copy of the handle's struct: rows is field-major
+// [FFDDP_PLANT_ROW_W][ld], so the wave's loads of one field are consecutive doubles.
+__device__ __forceinline__ void plant_load_row(ffddp_plant_params& P, int b, const double* __restrict__ rows, long ld) {
+  const double* r = rows + b;
+  for (int i = 0; i < NQ; ++i) {
+    P.armature[i] = r[(FFDDP_PLANT_ROW_ARMATURE + i) * ld];
+    P.damping[i] = r[(FFDDP_PLANT_ROW_DAMPING + i) * ld];
+  }
+  P.r_tool = r[FFDDP_PLANT_ROW_R_TOOL * ld];
+  P.margin = r[FFDDP_PLANT_ROW_MARGIN * ld];
+  for (int i = 0; i < 2; ++i) P.solref[i] = r[(FFDDP_PLANT_ROW_SOLREF + i) * ld];
+  for (int i = 0; i < 5; ++i) P.solimp[i] = r[(FFDDP_PLANT_ROW_SOLIMP + i) * ld];
+}
+
+// closed-loop plant stand-in: one thread per instance (ffddp_plant.hpp).  k_plant<false>: every lane steps with
+// the handle's struct; k_plant<true, const double*, long>: the trailing arguments are (rows, ld) and the lane
+// steps with its own row.  The pack keeps the first instantiation's arguments, and so its code, what they were.
+template <bool ROWS, class... RowArgs>
 __global__ __launch_bounds__(64) void k_plant(const ffddp_robot* __restrict__ rb, const ffddp_plant_params* __restrict__ pp,
                                               int B, double* __restrict__ q, double* __restrict__ v,
                                               const double* __restrict__ tau, const double* __restrict__ plane,
-                                              int integrate, double* __restrict__ obs, int32_t* __restrict__ fail) {
+                                              int integrate, double* __restrict__ obs, int32_t* __restrict__ fail,
+                                              RowArgs... row_args) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   double qb[NQ], vb[NQ], tb[NQ], ob[PO_WORDS];
@@ -2398,7 +2416,14 @@ __global__ __launch_bounds__(64) void k_plant(const ffddp_robot* __restrict__ rb
     tb[i] = tau[(long)b * NQ + i];
   }
   const double* pl = plane + (long)b * 6;
-  const bool ok = plant_step(*rb, *pp, qb, vb, tb, pl, pl + 3, integrate, ob);
+  bool ok;
+  if constexpr (ROWS) {
+    ffddp_plant_params P = *pp;  // timestep, n_substeps and site_R stay the handle's
+    plant_load_row(P, b, row_args...);
+    ok = plant_step(*rb, P, qb, vb, tb, pl, pl + 3, integrate, ob);
+  } else {
+    ok = plant_step(*rb, *pp, qb, vb, tb, pl, pl + 3, integrate, ob);
+  }
   for (int i = 0; i < NQ; ++i) {
     q[(long)b * NQ + i] = qb[i];
     v[(long)b * NQ + i] = vb[i];
@@ -4593,7 +4618,7 @@ int ffddp_fleet_inject_obs_dev(ffddp_handle* h, int B, const ffddp_fleet_inject*
   if (ld_qv < NQ) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_inject_obs_dev: bad stride");
   HIPCHK(h, hipSetDevice(h->device));
   const int nb = (int)(((long)B * NU + INJECT_BLOCK - 1) / INJECT_BLOCK);
-  hipLaunchKernelGGL(k_fleet_inject_obs, dim3(nb), dim3(INJECT_BLOCK), 0, (hipStream_t)stream, B, *inj, k, z, q, v,
+  hipLaunchKernelGGL(k_fleet_inject_obs<false>, dim3(nb), dim3(INJECT_BLOCK), 0, (hipStream_t)stream, B, *inj, k, z, q, v,
                      (long)ld_qv, tau_filt, qv_ctrl, tau_hat, tau_ctrl);
   HIPCHK(h, hipGetLastError());
   return 0;
@@ -4606,8 +4631,44 @@ int ffddp_fleet_inject_cmd_dev(ffddp_handle* h, int B, const ffddp_fleet_inject*
   if (!tau_cmd || !tau_app) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_inject_cmd_dev: null pointer");
   HIPCHK(h, hipSetDevice(h->device));
   const int nb = (int)(((long)B * NU + INJECT_BLOCK - 1) / INJECT_BLOCK);
-  hipLaunchKernelGGL(k_fleet_inject_cmd, dim3(nb), dim3(INJECT_BLOCK), 0, (hipStream_t)stream, B, *inj, k, tau_cmd,
+  hipLaunchKernelGGL(k_fleet_inject_cmd<false>, dim3(nb), dim3(INJECT_BLOCK), 0, (hipStream_t)stream, B, *inj, k, tau_cmd,
                      tau_app);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// the same two calls with per-row delays and sigmas; without any row array they are the calls above
+int ffddp_fleet_inject_obs_rows_dev(ffddp_handle* h, int B, const ffddp_fleet_inject* inj, int k, const double* z,
+                                    const double* q, const double* v, int ld_qv, const double* tau_filt,
+                                    double* qv_ctrl, double* tau_hat, double* tau_ctrl,
+                                    const ffddp_fleet_inject_rows* rows, void* stream) {
+  if (!rows || (!rows->d_obs && !rows->d_cmd && !rows->sigma))
+    return ffddp_fleet_inject_obs_dev(h, B, inj, k, z, q, v, ld_qv, tau_filt, qv_ctrl, tau_hat, tau_ctrl, stream);
+  if (!h) return FFDDP_E_INVALID;
+  if (int rc = fleet_inject_check(h, B, inj, k, "ffddp_fleet_inject_obs_rows_dev")) return rc;
+  if (!q || !v || !qv_ctrl || (inj->noise == FFDDP_INJECT_NOISE_TABLE ? (inj->rows > 0 && !z) : !inj->seed))
+    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_inject_obs_rows_dev: null pointer");
+  if (ld_qv < NQ) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_inject_obs_rows_dev: bad stride");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int nb = (int)(((long)B * NU + INJECT_BLOCK - 1) / INJECT_BLOCK);
+  hipLaunchKernelGGL((k_fleet_inject_obs<true, ffddp_fleet_inject_rows>), dim3(nb), dim3(INJECT_BLOCK), 0,
+                     (hipStream_t)stream, B, *inj, k, z, q, v, (long)ld_qv, tau_filt, qv_ctrl, tau_hat, tau_ctrl, *rows);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int ffddp_fleet_inject_cmd_rows_dev(ffddp_handle* h, int B, const ffddp_fleet_inject* inj, int k,
+                                    const double* tau_cmd, double* tau_app, const ffddp_fleet_inject_rows* rows,
+                                    void* stream) {
+  if (!rows || (!rows->d_obs && !rows->d_cmd && !rows->sigma))
+    return ffddp_fleet_inject_cmd_dev(h, B, inj, k, tau_cmd, tau_app, stream);
+  if (!h) return FFDDP_E_INVALID;
+  if (int rc = fleet_inject_check(h, B, inj, k, "ffddp_fleet_inject_cmd_rows_dev")) return rc;
+  if (!tau_cmd || !tau_app) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_inject_cmd_rows_dev: null pointer");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int nb = (int)(((long)B * NU + INJECT_BLOCK - 1) / INJECT_BLOCK);
+  hipLaunchKernelGGL((k_fleet_inject_cmd<true, ffddp_fleet_inject_rows>), dim3(nb), dim3(INJECT_BLOCK), 0,
+                     (hipStream_t)stream, B, *inj, k, tau_cmd, tau_app, *rows);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -4636,6 +4697,10 @@ struct ffddp_plant {
   ffddp_plant_params* dpp = nullptr;
   double *q = nullptr, *v = nullptr, *tau = nullptr, *plane = nullptr, *obs = nullptr;
   int32_t* fail = nullptr;
+  // per-instance physics (ffddp_plant_set_instance_params): field-major [FFDDP_PLANT_ROW_W][max_batch], allocated
+  // by the first call; n_rows > 0: the rows are in force
+  double* rows = nullptr;
+  int n_rows = 0;
 };
 
 extern "C" {
@@ -4671,7 +4736,7 @@ int ffddp_plant_create(const ffddp_robot* robot, const ffddp_plant_params* p, in
 void ffddp_plant_destroy(ffddp_plant* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  void* ps[] = {h->drb, h->dpp, h->q, h->v, h->tau, h->plane, h->obs, h->fail};
+  void* ps[] = {h->drb, h->dpp, h->q, h->v, h->tau, h->plane, h->obs, h->fail, h->rows};
   for (void* p : ps)
     if (p) (void)hipFree(p);
   delete h;
@@ -4682,10 +4747,55 @@ int ffddp_plant_step_dev(ffddp_plant* h, int B, double* q, double* v, const doub
   if (!h || B < 0 || B > h->max_batch) return FFDDP_E_INVALID;
   if (B == 0) return 0;
   if (!q || !v || !tau || !plane || !obs) return FFDDP_E_INVALID;
+  if (h->n_rows > 0 && B > h->n_rows) return FFDDP_E_INVALID;
   if (hipSetDevice(h->device) != hipSuccess) return FFDDP_E_DEVICE;
-  hipLaunchKernelGGL(k_plant, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->drb, h->dpp, B, q, v, tau,
-                     plane, integrate, obs, fail);
+  if (h->n_rows > 0)
+    hipLaunchKernelGGL((k_plant<true, const double*, long>), dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream,
+                       h->drb, h->dpp, B, q, v, tau, plane, integrate, obs, fail, h->rows, (long)h->max_batch);
+  else
+    hipLaunchKernelGGL(k_plant<false>, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->drb, h->dpp, B, q, v,
+                       tau, plane, integrate, obs, fail);
   return hipGetLastError() == hipSuccess ? 0 : FFDDP_E_DEVICE;
+}
+
+// a physics row the plant can integrate with (include/ffddp.h: ffddp_plant_set_instance_params)
+static bool plant_row_valid(const double* r) {
+  for (int i = 0; i < FFDDP_PLANT_ROW_W; ++i)
+    if (!std::isfinite(r[i])) return false;
+  for (int i = 0; i < NQ; ++i)
+    if (r[FFDDP_PLANT_ROW_ARMATURE + i] < 0.0 || r[FFDDP_PLANT_ROW_DAMPING + i] < 0.0) return false;
+  const double* sr = r + FFDDP_PLANT_ROW_SOLREF;
+  const double* si = r + FFDDP_PLANT_ROW_SOLIMP;
+  if (r[FFDDP_PLANT_ROW_R_TOOL] <= 0.0 || sr[0] <= 0.0 || sr[1] <= 0.0) return false;
+  if (si[0] <= 0.0 || si[0] >= 1.0 || si[1] <= 0.0 || si[1] >= 1.0 || si[1] < si[0]) return false;
+  return si[3] > 0.0 && si[3] < 1.0 && si[4] >= 1.0;
+}
+
+int ffddp_plant_set_instance_params(ffddp_plant* h, int n, const double* rows) {
+  static_assert(FFDDP_PLANT_ROW_SOLIMP + 5 == FFDDP_PLANT_ROW_W, "plant physics row layout");
+  if (!h) return FFDDP_E_INVALID;
+  if (!rows) {  // back to the handle's struct; steps already enqueued keep the copy they were launched with
+    h->n_rows = 0;
+    return 0;
+  }
+  if (n < 1 || n > h->max_batch) return FFDDP_E_INVALID;
+  for (int b = 0; b < n; ++b)
+    if (!plant_row_valid(rows + (size_t)b * FFDDP_PLANT_ROW_W)) return FFDDP_E_INVALID;
+  const size_t ld = (size_t)h->max_batch;
+  std::vector<double> t(ld * FFDDP_PLANT_ROW_W, 0.0);  // row-major -> field-major
+  for (int b = 0; b < n; ++b)
+    for (int f = 0; f < FFDDP_PLANT_ROW_W; ++f) t[(size_t)f * ld + b] = rows[(size_t)b * FFDDP_PLANT_ROW_W + f];
+  if (hipSetDevice(h->device) != hipSuccess) return FFDDP_E_DEVICE;
+  if (!h->rows && hipMalloc((void**)&h->rows, t.size() * 8) != hipSuccess) {
+    h->rows = nullptr;
+    return FFDDP_E_OOM;
+  }
+  // steps in flight read the copy: wait for them, then replace it
+  if (hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(h->rows, t.data(), t.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
+    return FFDDP_E_DEVICE;
+  h->n_rows = n;
+  return 0;
 }
 
 int ffddp_plant_step(ffddp_plant* h, int B, double* q, double* v, const double* tau, const double* plane,

@@ -59,8 +59,15 @@ SYMBOLS = (
     "ffddp_fleet_task_refs_dev",
     "ffddp_fleet_pre_task_dev",
     "ffddp_fleet_metrics_dev",
+    "ffddp_plant_set_instance_params",
+    "ffddp_fleet_inject_obs_rows_dev",
+    "ffddp_fleet_inject_cmd_rows_dev",
 )
 PLANT_OBS = 69
+# FFDDP_PLANT_ROW_*: one instance's physics row (ffddp_plant_set_instance_params)
+PLANT_ROW_W = 23
+PLANT_ROW_ARMATURE, PLANT_ROW_DAMPING, PLANT_ROW_R_TOOL, PLANT_ROW_MARGIN = 0, 7, 14, 15
+PLANT_ROW_SOLREF, PLANT_ROW_SOLIMP = 16, 18
 NSTATS = 10
 TRACE_W = 10
 TRACE_FIELDS = ("iter", "cost", "stop", "grad", "preg", "dreg", "step", "ffeas", "dV", "dV_exp")
@@ -133,6 +140,12 @@ class FleetInject(C.Structure):
         ("sigma_tau", C.c_double),
         ("lpf", C.c_double),
     ] + [(n, C.c_void_p) for n in ("row", "a", "b", "seed", "obs_ring", "cmd_ring", "tau_hat_filt", "z_cmd")]
+
+
+class FleetInjectRows(C.Structure):
+    """ffddp_fleet_inject_rows: per-row delays and sigmas of the device injector (device pointers; null = the scalar)."""
+
+    _fields_ = [(n, C.c_void_p) for n in ("d_obs", "d_cmd", "sigma")]
 
 
 FLEET_TASK_W = 22  # FFDDP_FLEET_TASK_W: doubles per task record (trajectory.task_records fills them)
@@ -475,6 +488,15 @@ def load() -> C.CDLL:
     lib.ffddp_fleet_inject_obs_dev.restype = C.c_int
     lib.ffddp_fleet_inject_cmd_dev.argtypes = fi + [vp, vp] + [vp]
     lib.ffddp_fleet_inject_cmd_dev.restype = C.c_int
+    # per-row profiles: the same arguments, then const ffddp_fleet_inject_rows* (NULL = the calls above) before the stream
+    lib.ffddp_fleet_inject_obs_rows_dev.argtypes = (lib.ffddp_fleet_inject_obs_dev.argtypes[:-1]
+                                                    + [C.POINTER(FleetInjectRows), vp])
+    lib.ffddp_fleet_inject_obs_rows_dev.restype = C.c_int
+    lib.ffddp_fleet_inject_cmd_rows_dev.argtypes = (lib.ffddp_fleet_inject_cmd_dev.argtypes[:-1]
+                                                    + [C.POINTER(FleetInjectRows), vp])
+    lib.ffddp_fleet_inject_cmd_rows_dev.restype = C.c_int
+    lib.ffddp_plant_set_instance_params.argtypes = [C.c_void_p, C.c_int, dp]
+    lib.ffddp_plant_set_instance_params.restype = C.c_int
     lib.ffddp_fleet_noise_dev.argtypes = [C.c_void_p, C.c_int, vp, C.c_int, vp, vp] + [vp]
     lib.ffddp_fleet_noise_dev.restype = C.c_int
     # per-instance tasks: ffddp_fleet_tasks by value; pre_task takes it in place of node_ref1 / contact_hint

@@ -42,6 +42,7 @@ runs there too once ``device_noise`` names the source of its normals.
 """
 from __future__ import annotations
 
+import dataclasses
 import time
 from typing import Callable, Optional, Sequence, Tuple
 
@@ -52,12 +53,12 @@ from . import robot as R
 from .config import OcpConfig
 from .controller import (_OCP_FIELDS, _quat_wxyz_to_R, classical_benchmark_config, ff_benchmark_config,
                          ff_filter_alpha)
-from .plant import BatchedPlant, PandaTablePlant
+from .plant import JOINT_DAMPING, BatchedPlant, PandaTablePlant, PlantPhysics, plant_rows
 from .runlog import summary_metrics
 from .solver import BatchedBoxFDDP
 from .trajectory import (TABLE_CENTER, TABLE_HALF_Z, TOOL_RADIUS, FleetTask, make_approach_then_circle,
                          sample_records, task_records, with_contact_hold)
-from .uncertainty import BatchedUncertaintyInjector, config_for_scenario
+from .uncertainty import BatchedUncertaintyInjector, config_for_scenario, delay_steps
 
 Traj = Callable[[float], Tuple[np.ndarray, np.ndarray, bool]]
 
@@ -554,6 +555,47 @@ def _sweep_instances(scenarios: Sequence[str], seeds: int):
     return np.array(names), np.array(tilt), np.array(scale), np.array(seed)
 
 
+def sweep_plant_physics(seed, plant_spread) -> list:
+    """run_sweep's plant_spread = (ds, dd): one PlantPhysics per instance seed,
+    the contact time constant 0.02 (1 + ds u0) and every joint's damping
+    1.0 (1 + dd u1), u = default_rng([seed_b, 2]).uniform(-1, 1, 2)."""
+    ds, dd = plant_spread
+    out = []
+    for s in seed:
+        u = np.random.default_rng([int(s), 2]).uniform(-1.0, 1.0, 2)
+        out.append(PlantPhysics(damping=JOINT_DAMPING * (1.0 + dd * u[1]), solref=(0.02 * (1.0 + ds * u[0]), 1.0)))
+    return out
+
+
+def sweep_uncertainty_config(scenario: str, seed: int, dt: float, uncertainty_spread=None):
+    """The scenario's injector config (None without one) and, with run_sweep's
+    uncertainty_spread = (dn, D), its profile varied from g = default_rng(
+    [seed, 3]): the three sigmas scaled by 1 + dn g.uniform(-1, 1), then the
+    delays d_obs, d_cmd = g.integers(0, D + 1, 2) ticks of dt, written as
+    delta_obs_cycles / delta_cmd_s so that delay_steps returns them."""
+    cfg = config_for_scenario(str(scenario), seed=int(seed))
+    if cfg is None or uncertainty_spread is None:
+        return cfg
+    dn, D = uncertainty_spread
+    g = np.random.default_rng([int(seed), 3])
+    f = 1.0 + dn * g.uniform(-1.0, 1.0)
+    d_obs, d_cmd = (int(x) for x in g.integers(0, int(D) + 1, 2))
+    cfg = dataclasses.replace(cfg, sigma_q=cfg.sigma_q * f, sigma_dq=cfg.sigma_dq * f, sigma_tau=cfg.sigma_tau * f,
+                              delta_obs_cycles=int(round(d_obs * dt / 1.0e-3)), delta_cmd_s=d_cmd * dt)
+    if delay_steps(cfg, dt) != (d_obs, d_cmd):
+        raise ValueError(f"run_sweep: a delay of ({d_obs}, {d_cmd}) ticks of {dt} s is no whole number of 1 kHz cycles")
+    return cfg
+
+
+def _inject_profile(ucfgs, dt: float):
+    """(B, 2) delays in ticks and (B, 3) sigmas of a list of configs; -1 / NaN for None."""
+    delay, sigma = np.full((len(ucfgs), 2), -1, np.int64), np.full((len(ucfgs), 3), np.nan)
+    for b, c in enumerate(ucfgs):
+        if c is not None:
+            delay[b], sigma[b] = delay_steps(c, dt), (c.sigma_q, c.sigma_dq, c.sigma_tau)
+    return delay, sigma
+
+
 def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilted_15", "actuation_uncertainty"),
               seeds: int = 256, total_time: float = 4.0, rank: int = 0, world: int = 1, device: int = 0,
               q_sigma: float = 0.02, verbose: bool = True, record: Sequence[int] = (),
@@ -561,7 +603,9 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
               device_loop: bool = False, device_noise: Optional[str] = None, solve_period: int = 1,
               command_filter: bool = False, device_refs: bool = False,
               task_spread: Optional[Tuple[float, float]] = None, stagger: int = 0,
-              device_summary: bool = False, keep_logs: bool = True) -> dict:
+              device_summary: bool = False, keep_logs: bool = True,
+              plant_spread: Optional[Tuple[float, float]] = None,
+              uncertainty_spread: Optional[Tuple[float, int]] = None) -> dict:
     """Closed-loop sweep of len(scenarios) * seeds instances; this rank runs
     its contiguous shard.  Returns per-instance summary arrays (this shard).
     record: shard-local instance indices whose controller inputs (the plant
@@ -613,7 +657,19 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     summaries agree to summation rounding.  keep_logs = False (needs
     device_summary, ValueError otherwise) drops the per-tick logs altogether
     (logs=False): the run's memory no longer grows with its length and the
-    (ticks, B) outputs ``solved`` and ``surface`` are absent."""
+    (ticks, B) outputs ``solved`` and ``surface`` are absent.
+    plant_spread, uncertainty_spread (host and device path alike): the plant's
+    physics and the injectors' profiles per instance.  plant_spread = (ds, dd),
+    each in [0, 0.9]: the contact time constant 0.02 (1 + ds u0) -- the
+    table's stiffness; it stays at or above twice the 1 ms physics step,
+    MuJoCo's floor for solref -- and every joint's damping 1.0 (1 + dd u1),
+    u uniform in [-1, 1] from default_rng([seed_b, 2]).  uncertainty_spread =
+    (dn, D), dn in [0, 1), D an integer 0..16, for the instances whose scenario
+    has an injector: the three sigmas scaled by 1 + dn g.uniform(-1, 1), then
+    the delays d_obs, d_cmd = g.integers(0, D + 1, 2) control ticks, g =
+    default_rng([seed_b, 3]).  The q0 and task draws do not move.  The
+    summary carries ``plant_rows`` (B, PLANT_ROW_W), ``inject_delay`` (B, 2)
+    and ``inject_sigma`` (B, 3) (-1 / NaN without an injector)."""
     variant = str(variant).strip().lower()
     if variant not in ("classical", "ff"):
         raise ValueError(f"run_sweep: unknown variant {variant!r}")
@@ -629,6 +685,21 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
         task_spread = tuple(float(x) for x in task_spread)
         if len(task_spread) != 2 or not all(0.0 <= x < 1.0 for x in task_spread):
             raise ValueError(f"run_sweep: task_spread is (dr, dw), each in [0, 1), not {task_spread!r}")
+    if plant_spread is not None:
+        plant_spread = tuple(float(x) for x in plant_spread)
+        if len(plant_spread) != 2 or not all(0.0 <= x <= 0.9 for x in plant_spread):
+            raise ValueError(f"run_sweep: plant_spread is (ds, dd), each in [0, 0.9], not {plant_spread!r}")
+    if uncertainty_spread is not None:
+        uncertainty_spread = tuple(uncertainty_spread)
+        ok = len(uncertainty_spread) == 2
+        if ok:
+            dn, D = uncertainty_spread
+            ok = (not isinstance(D, (bool, np.bool_)) and isinstance(D, (int, np.integer)) and 0 <= int(D) <= 16
+                  and isinstance(dn, (int, float, np.integer, np.floating)) and 0.0 <= float(dn) < 1.0)
+        if not ok:
+            raise ValueError("run_sweep: uncertainty_spread is (dn, D), dn in [0, 1) and D an integer 0..16, "
+                             f"not {uncertainty_spread!r}")
+        uncertainty_spread = (float(dn), int(D))
     device_refs = bool(device_refs) or task_spread is not None or stagger > 0
     if device_refs and not device_loop:
         raise NotImplementedError("run_sweep: device_refs, task_spread and stagger need device_loop=True "
@@ -672,10 +743,13 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     R_site_from_pin_ee, p_off = site_calibration(obs0)
     nominal.close()
     q0 = np.stack([R.Q_NEUTRAL + np.random.default_rng(int(s)).normal(0.0, q_sigma, 7) for s in seed])
+    dt_ctrl = 0.001 * 5  # BatchedPlant.dt
+    physics = sweep_plant_physics(seed, plant_spread) if plant_spread is not None else None
+    sweep_cfgs = [sweep_uncertainty_config(str(names[b]), int(seed[b]), dt_ctrl, uncertainty_spread) for b in range(B)]
     if device_loop:
         ucfgs = None
         if device_noise is not None:  # per instance, as the host path below
-            ucfgs = [config_for_scenario(str(names[b]), seed=int(seed[b])) for b in range(B)]
+            ucfgs = sweep_cfgs
         tasks = None
         if device_refs:
             dr, dw = task_spread if task_spread is not None else (0.0, 0.0)
@@ -688,10 +762,11 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
                                        delay=((lo + b) % stagger) * (0.001 * 5) if stagger else 0.0))  # BatchedPlant.dt
         out = _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, (R_site_from_pin_ee, p_off), total_time,
                                 neg_step_rule, device, t_cp, verbose, ucfgs, device_noise, solve_period,
-                                command_filter, tasks, device_summary, keep_logs)
+                                command_filter, tasks, device_summary, keep_logs, physics,
+                                allow_plant_fail=plant_spread is not None or uncertainty_spread is not None)
         out.update(names=names, seed=seed, shard=(lo, hi), n_all=n_all)
         return out
-    plant = BatchedPlant(B, timestep=0.001, n_substeps=5, device=device)
+    plant = BatchedPlant(B, timestep=0.001, n_substeps=5, device=device, physics=physics)
     plant.q = q0.copy()
     plant.v = np.zeros((B, 7))
     plant.set_tilt(0.0)
@@ -711,7 +786,7 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     plant.step(tau0 * 0.0, integrate=False)
     # the scenarios' uncertainty injectors, batched (BatchedUncertaintyInjector:
     # draw for draw the per-instance ScenarioUncertaintyInjector)
-    ucfg = {b: config_for_scenario(str(names[b]), seed=int(seed[b])) for b in range(B)}
+    ucfg = dict(enumerate(sweep_cfgs))
     inj_idx = np.array([b for b in range(B) if ucfg[b] is not None], dtype=np.int64)
     inj = BatchedUncertaintyInjector(dt=plant.dt, nu=7, configs=[ucfg[b] for b in inj_idx]) if inj_idx.size else None
     steps = int(total_time / plant.dt)
@@ -800,6 +875,9 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     per_inst["solve_not_ok_ticks"] = not_ok_ticks
     out = dict(names=names, seed=seed, per_instance=per_inst, ticks=steps, wall_s=wall, controller_s=ctrl_s,
                instances=B, shard=(lo, hi), n_all=n_all, variant=variant, solved_ticks=solved_ticks)
+    inject_delay, inject_sigma = _inject_profile(sweep_cfgs, dt_ctrl)
+    out.update(plant_rows=plant_rows(physics if physics is not None else [PlantPhysics()] * B),
+               inject_delay=inject_delay, inject_sigma=inject_sigma)
     if rec_idx:
         out["record"] = dict(index=np.array(rec_idx), t=rec_t, obs=rec_obs, tau=rec_tau, q0=q0[rec_idx], traj=traj,
                              config=cfg, dt=plant.dt, calibration_obs=obs0)
@@ -808,18 +886,32 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     return out
 
 
+def _mismatch_outputs(loop, r: dict, ucfgs, B: int, with_fail: bool) -> dict:
+    """The device loop's per-instance physics rows and injector constants for the sweep's summary; with_fail:
+    also ``plant_fail`` (B,), each instance's failed plant steps."""
+    out = dict(plant_rows=loop.plant_rows.copy(), inject_delay=np.full((B, 2), -1, np.int64),
+               inject_sigma=np.full((B, 3), np.nan))
+    if ucfgs is not None:
+        out.update(inject_a=r["inject_a"], inject_b=r["inject_b"], inject_delay=loop.inject_delay.copy(),
+                   inject_sigma=loop.inject_sigma.copy())
+    if with_fail:
+        out["plant_fail"] = np.asarray(r["plant_fail"])
+    return out
+
+
 DEVICE_MEMORY: dict = {}  # the last device-loop sweep's memory figures (tools/sweep_c4.py reports them)
 
 
 def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, total_time, neg_step_rule, device, t_cp,
                       verbose, ucfgs=None, noise=None, solve_period=1, command_filter=False, tasks=None,
-                      device_summary=False, keep_logs=True) -> dict:
+                      device_summary=False, keep_logs=True, plant_physics=None, allow_plant_fail=False) -> dict:
     """run_sweep's loop on the device (fleet_loop.DeviceFleetLoop) and the
     host path's summary from the downloaded logs.  tasks: per-instance
     FleetTasks in place of traj; the summary's reference position and its
     contact phase are then each instance's own, in its task time.
     device_summary: the summary from the loop's device accumulators instead;
-    keep_logs=False: the loop keeps no per-tick logs."""
+    keep_logs=False: the loop keeps no per-tick logs.  plant_physics: one
+    PlantPhysics per instance (None: the scene's constants)."""
     import torch
 
     from .fleet_loop import DeviceFleetLoop
@@ -836,7 +928,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
                            calibration=calibration, timestep=timestep, n_substeps=n_substeps, uncertainty=ucfgs,
                            noise=noise or "numpy", solve_period=int(solve_period), tasks=tasks,
                            metrics=bool(device_summary), logs=bool(keep_logs),
-                           t_contact_phase=float(t_cp) if device_summary and tasks is None else None)
+                           t_contact_phase=float(t_cp) if device_summary and tasks is None else None,
+                           plant_physics=plant_physics)
     wall0 = time.perf_counter()
     loop.run(steps)
     torch.cuda.synchronize(loop.dev)
@@ -849,7 +942,9 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     DEVICE_MEMORY.update(torch_peak_bytes=int(torch.cuda.max_memory_allocated(loop.dev)),
                          device_used_bytes=int(total_b - free_b))
     loop.close()
-    if np.any(r["plant_fail"]):
+    # a failed plant step (non-SPD mass matrix) is an error in the plain sweep; under per-instance physics or
+    # profiles an instance may diverge, which is a result: its count is reported (``plant_fail``)
+    if np.any(r["plant_fail"]) and not allow_plant_fail:
         raise RuntimeError("run_sweep(device_loop=True): a plant step failed (non-SPD mass matrix)")
     if device_summary:  # B x FLEET_METRICS_W doubles came down; no series is built
         s = r["summary"]
@@ -859,8 +954,7 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
                   f"ok={1.0 - float(np.sum(s['solve_not_ok_ticks'])) / max(B * steps, 1):.3f}", flush=True)
         out = dict(per_instance={k: np.asarray(s[k], float) for k in SUMMARY_KEYS}, ticks=steps, wall_s=wall,
                    controller_s=None, instances=B, variant=variant, solved_ticks=np.asarray(s["solved_ticks"], float))
-        if ucfgs is not None:
-            out.update(inject_a=r["inject_a"], inject_b=r["inject_b"])
+        out.update(_mismatch_outputs(loop, r, ucfgs, B, allow_plant_fail))
         if tasks is not None and keep_logs:
             out.update(solved=r["solved"], surface=r["surface"] != 0)
         return out
@@ -893,8 +987,7 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     per_inst["solve_not_ok_ticks"] = (r["ok"] == 0).sum(0).astype(float)
     out = dict(per_instance=per_inst, ticks=steps, wall_s=wall, controller_s=None, instances=B, variant=variant,
                solved_ticks=r["solved"].sum(0).astype(float))
-    if ucfgs is not None:
-        out.update(inject_a=r["inject_a"], inject_b=r["inject_b"])
+    out.update(_mismatch_outputs(loop, r, ucfgs, B, allow_plant_fail))
     if tasks is not None:
         out.update(solved=r["solved"], surface=r["surface"] != 0)  # (ticks, B): the per-tick solve share
     return out

@@ -59,13 +59,20 @@ and, when neither a reference table nor a noise table is sized by ``steps``
 (``tasks`` given; no injector, or ``noise="philox"``), the loop runs for any
 number of ticks in constant memory.
 
+With ``plant_physics`` every instance integrates with its own physics row
+(plant.PlantPhysics: armature, damping, tool radius, contact margin, solref,
+solimp; ffddp_plant_set_instance_params) from the start sequence on, and the
+``uncertainty`` configs may be any mix: each injected instance keeps its own
+delays and sigmas (ffddp_fleet_inject_*_rows_dev), the rings as deep as the
+largest delay.  Neither adds a launch; configs that differ by seed only, and
+a loop without ``plant_physics``, enqueue exactly the calls they did before.
+
 Not on the device, and so not supported here: ``run_sweep``'s ``record`` and
 any per-tick host callback; ``tick()`` lets a caller look between ticks at the price of its own
 synchronisation.
 """
 from __future__ import annotations
 
-import dataclasses
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -170,7 +177,10 @@ class DeviceFleetLoop:
     (R_site_from_pin_ee, p_site_minus_frame_pin), by default taken from the
     nominal plant at the "neutral" keyframe as run_sweep does.
     uncertainty: None, or one Optional[UncertaintyProfileConfig] per instance
-    (None: no injector); the configs may differ by seed only.  noise: where
+    (None: no injector); the configs may be any mix (delays, sigmas, a / b
+    ranges per instance; the rings take the largest delays).  plant_physics:
+    None (the scene's constants), one plant.PlantPhysics per instance, or one
+    for all.  noise: where
     the injector's normals come from, "numpy" (uncertainty.predraw's table of
     `steps` ticks, uploaded once; at most max_table_bytes) or "philox".
     metrics: accumulate the summary's sums on the device (``acc``
@@ -194,7 +204,7 @@ class DeviceFleetLoop:
                  uncertainty: Optional[Sequence[Optional[UncertaintyProfileConfig]]] = None, noise: str = "numpy",
                  max_table_bytes: int = 1 << 30, solve_period: Optional[int] = None,
                  tasks: Optional[Sequence[FleetTask]] = None, metrics: bool = False, logs: bool = True,
-                 t_contact_phase=None):
+                 t_contact_phase=None, plant_physics=None):
         variant = str(variant).strip().lower()
         if variant not in ("classical", "ff"):
             raise ValueError(f"DeviceFleetLoop: unknown variant {variant!r}")
@@ -217,14 +227,13 @@ class DeviceFleetLoop:
             ucfgs = list(uncertainty)
             if len(ucfgs) != int(B):
                 raise ValueError("DeviceFleetLoop: uncertainty takes one entry (a config or None) per instance")
-            given = [c for c in ucfgs if c is not None]
-            if any(dataclasses.replace(c, seed=0) != dataclasses.replace(given[0], seed=0) for c in given):
-                raise ValueError("DeviceFleetLoop: the uncertainty configs may differ by seed only")
+            if not all(c is None or isinstance(c, UncertaintyProfileConfig) for c in ucfgs):
+                raise ValueError("DeviceFleetLoop: uncertainty entries are UncertaintyProfileConfig or None")
         cfg = config
         self.period = resolve_solve_period(cfg, solve_period)
         import torch
 
-        from .plant import BatchedPlant, PandaTablePlant, table_plane
+        from .plant import BatchedPlant, PandaTablePlant, PlantPhysics, plant_rows, table_plane
         from .solver import BatchedBoxFDDP
 
         self.torch = torch
@@ -240,7 +249,16 @@ class DeviceFleetLoop:
             nominal.close()
         R_site, p_off = (np.asarray(a, float) for a in calibration)
         self.R_des = R.R_MJ_FROM_PIN.T @ R.vertical_down_rotation_mj() @ R_site.T
-        self.plant = BatchedPlant(self.B, timestep=timestep, n_substeps=n_substeps, device=device)
+        # the physics rows are in force from the start sequence on (the level table's forward pass included)
+        if plant_physics is not None:
+            phys = [plant_physics] * self.B if isinstance(plant_physics, PlantPhysics) else list(plant_physics)
+            if len(phys) != self.B or not all(isinstance(p, PlantPhysics) for p in phys):
+                raise ValueError("DeviceFleetLoop: plant_physics takes one PlantPhysics per instance, or one for all")
+            plant_physics = plant_rows(phys)
+        self.plant = BatchedPlant(self.B, timestep=timestep, n_substeps=n_substeps, device=device,
+                                  physics=plant_physics)
+        self.plant_rows = plant_rows([PlantPhysics()] * self.B) if plant_physics is None else plant_physics.copy()
+        self._has_physics = plant_physics is not None
         self.dt = self.plant.dt
         self.metrics, self.logs, self.t0 = metrics, logs, float(t0)
         # without logs nothing is sized by `steps` unless a table is: the references' or the injector's normals
@@ -288,9 +306,11 @@ class DeviceFleetLoop:
             scale=up(np.broadcast_to(np.asarray(torque_scale, float), (B, 7))), **self.S)
         if variant == "ff":
             self.T.update(tau_hat=self.P["tau_filt"], tau_filt=self.P["tau_filt"])
-        self.J = self.inject = self.inject_a = self.inject_b = None
+        self.J = self.inject = self.inject_rows = self.inject_a = self.inject_b = None
+        self.inject_delay = self.inject_sigma = None
         if ucfgs is not None:
             self.inject_a, self.inject_b = np.full(B, np.nan), np.full(B, np.nan)
+            self.inject_delay, self.inject_sigma = np.full((B, 2), -1, np.int64), np.full((B, 3), np.nan)
             if any(c is not None for c in ucfgs):  # else the plain loop
                 self._init_inject(ucfgs, noise, max_table_bytes)
         # the scheduled tick: its counters, and one row of `need` per tick (the log `solved`)
@@ -347,7 +367,13 @@ class DeviceFleetLoop:
         row = np.full(B, -1, np.int32)
         row[idx] = np.arange(len(idx), dtype=np.int32)
         c0 = given[0]
-        d_obs, d_cmd = delay_steps(c0, self.dt)
+        delay = np.array([delay_steps(c, self.dt) for c in given], dtype=np.int32).reshape(len(given), 2)
+        sigma = np.array([(c.sigma_q, c.sigma_dq, c.sigma_tau) for c in given], dtype=np.float64)
+        d_obs, d_cmd = int(delay[:, 0].max()), int(delay[:, 1].max())  # the ring depths
+        self.inject_delay[idx], self.inject_sigma[idx] = delay, sigma
+        # the per-row arrays only when the profiles differ: configs that differ by seed (and a / b range: drawn
+        # on the host) only take the scalar calls, as before
+        mixed = bool(np.any(delay != delay[0]) or np.any(sigma != sigma[0]))
         self.noise, self.z_table = noise, None
         if noise == "numpy":
             a, b, zt = predraw(given, self.steps, max_table_bytes=max_table_bytes)
@@ -366,6 +392,11 @@ class DeviceFleetLoop:
             self.J["tau_filt"] = self.P["tau_filt"]
         self.inject = self.solver.fleet_inject(self.J, d_obs, d_cmd, (c0.sigma_q, c0.sigma_dq, c0.sigma_tau),
                                                float(np.clip(LPF_ALPHA, 0.0, 1.0)), noise)
+        if mixed:
+            self.J.update(d_obs=torch.from_numpy(delay[:, 0].copy()).to(self.dev),
+                          d_cmd=torch.from_numpy(delay[:, 1].copy()).to(self.dev),
+                          sigma=torch.from_numpy(sigma).to(self.dev))
+            self.inject_rows = self.solver.fleet_inject_rows(self.J)
         self.T.update(q=self.J["qv_ctrl"][:, 0:7], v=self.J["qv_ctrl"][:, 7:14])
         if self.variant == "ff":
             self.T["tau_hat"] = self.J["tau_ctrl"]
@@ -425,7 +456,7 @@ class DeviceFleetLoop:
             self.ktasks.t, hint = self._tick_time(k), False
         if self.inject is not None:
             self.solver.fleet_inject_obs_dev(self.J, self.inject, k, z=None if self.z_table is None else self.z_table[k],
-                                             stream=self._stream)
+                                             stream=self._stream, rows=self.inject_rows)
         if self.sched is None:
             self.solver.fleet_pre_dev(T, self.params, hint, stream=self._stream, tasks=self.ktasks)
             self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream)
@@ -437,7 +468,7 @@ class DeviceFleetLoop:
                                   active=T["need"])
             self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream, sched=self.sched)
         if self.inject is not None:
-            self.solver.fleet_inject_cmd_dev(self.J, self.inject, k, stream=self._stream)
+            self.solver.fleet_inject_cmd_dev(self.J, self.inject, k, stream=self._stream, rows=self.inject_rows)
         self._stepped = False
         self.k = k + 1
 
@@ -507,12 +538,20 @@ class DeviceFleetLoop:
         ``tasks`` also ``t_task`` (k, B): each instance's task time per tick
         (t minus its delay, the subtraction the pre kernel does); with
         ``uncertainty`` also ``inject_a``, ``inject_b`` (B,): the injectors'
-        actuation gain and bias, NaN where there is none.  With ``metrics``
+        actuation gain and bias, NaN where there is none, ``inject_delay``
+        (B, 2) their (observation, command) delays in ticks and
+        ``inject_sigma`` (B, 3) their sigmas, -1 / NaN where there is none;
+        and ``plant_rows`` (B, PLANT_ROW_W): the physics each instance
+        integrates with (all three are attributes of the loop as well).  With
+        ``metrics``
         also ``metrics`` (FLEET_METRICS_W, B): the accumulators over the k
         ticks (the closing plant step's record is folded in here, once), and
         ``summary``: runlog.metrics_from_accumulators of them.  With
         ``logs=False`` only ``ticks`` (k), ``plant_fail``, ``metrics``,
-        ``summary`` and the injectors' constants: no per-tick array exists."""
+        ``summary`` and the injectors' gain and bias: no per-tick array
+        exists; ``plant_rows`` with ``plant_physics`` and ``inject_delay`` /
+        ``inject_sigma`` with profiles that differ are added, so a loop
+        without either returns the keys it did."""
         torch, k = self.torch, self.k
         if not self._stepped and k > 0:
             self._plant_step()
@@ -530,6 +569,11 @@ class DeviceFleetLoop:
             out = dict(ticks=k, plant_fail=fails, **m)
             if self.inject_a is not None:
                 out.update(inject_a=self.inject_a.copy(), inject_b=self.inject_b.copy())
+            # the rows and profiles only where they were given: a loop without them returns the keys it did
+            if self._has_physics:
+                out["plant_rows"] = self.plant_rows.copy()
+            if self.inject_rows is not None:
+                out.update(inject_delay=self.inject_delay.copy(), inject_sigma=self.inject_sigma.copy())
             return out
         info = self.log_info[:k].cpu().numpy()
         out = dict(info=info, obs=self.log_obs[: k + 1].cpu().numpy(), t=self.times[:k].copy(),
@@ -537,8 +581,10 @@ class DeviceFleetLoop:
                    solved=(self.log_need[:k].cpu().numpy() != 0) if self.sched is not None else np.ones((k, self.B), bool))
         for i, name in enumerate(_abi.FLEET_INFO_FIELDS):
             out[name] = info[:, :, i]
+        out["plant_rows"] = self.plant_rows.copy()
         if self.inject_a is not None:
-            out.update(inject_a=self.inject_a.copy(), inject_b=self.inject_b.copy())
+            out.update(inject_a=self.inject_a.copy(), inject_b=self.inject_b.copy(),
+                       inject_delay=self.inject_delay.copy(), inject_sigma=self.inject_sigma.copy())
         if self.task_delay is not None:
             out["t_task"] = self.times[:k, None] - self.task_delay[None, :]
         if self.metrics:

@@ -112,6 +112,63 @@ def plant_params(timestep: float = DEFAULT_TIMESTEP, n_substeps: int = 1) -> _ab
     return p
 
 
+@dataclass
+class PlantPhysics:
+    """One instance's plant physics (a row of ffddp_plant_set_instance_params):
+    what ffddp_plant_params holds apart from timestep, n_substeps and site_R.
+    The defaults are the scene's constants (plant_params).  armature and
+    damping: a scalar for every joint, or seven values."""
+
+    armature: object = JOINT_ARMATURE
+    damping: object = JOINT_DAMPING
+    r_tool: float = R_TOOL
+    margin: float = CONTACT_MARGIN
+    solref: tuple = (0.02, 1.0)  # contact time constant (the table's stiffness), damping ratio
+    solimp: tuple = (0.9, 0.95, 0.001, 0.5, 2.0)  # d0, dmax, width, mid, power
+
+    def row(self) -> np.ndarray:
+        r = np.zeros(_abi.PLANT_ROW_W)
+        r[_abi.PLANT_ROW_ARMATURE:_abi.PLANT_ROW_ARMATURE + 7] = np.broadcast_to(np.asarray(self.armature, float), (7,))
+        r[_abi.PLANT_ROW_DAMPING:_abi.PLANT_ROW_DAMPING + 7] = np.broadcast_to(np.asarray(self.damping, float), (7,))
+        r[_abi.PLANT_ROW_R_TOOL], r[_abi.PLANT_ROW_MARGIN] = float(self.r_tool), float(self.margin)
+        r[_abi.PLANT_ROW_SOLREF:_abi.PLANT_ROW_SOLREF + 2] = np.asarray(self.solref, float).reshape(2)
+        r[_abi.PLANT_ROW_SOLIMP:_abi.PLANT_ROW_SOLIMP + 5] = np.asarray(self.solimp, float).reshape(5)
+        return r
+
+
+def check_plant_rows(rows) -> np.ndarray:
+    """(n, PLANT_ROW_W) float64 rows, refused (ValueError) where
+    ffddp_plant_set_instance_params refuses them: a non-finite entry, armature
+    or damping below 0, r_tool <= 0, solref[0] or solref[1] <= 0, d0 or dmax
+    outside (0, 1) or dmax < d0, mid outside (0, 1), power < 1."""
+    rows = np.ascontiguousarray(np.asarray(rows, dtype=np.float64))
+    if rows.ndim != 2 or rows.shape[1] != _abi.PLANT_ROW_W or rows.shape[0] < 1:
+        raise ValueError(f"plant rows: expected (n, {_abi.PLANT_ROW_W}) with n >= 1, got {rows.shape}")
+    A, D, SR, SI = _abi.PLANT_ROW_ARMATURE, _abi.PLANT_ROW_DAMPING, _abi.PLANT_ROW_SOLREF, _abi.PLANT_ROW_SOLIMP
+    d0, dmax, mid, power = rows[:, SI], rows[:, SI + 1], rows[:, SI + 3], rows[:, SI + 4]
+    checks = (("a non-finite entry", ~np.all(np.isfinite(rows), axis=1)),
+              ("armature < 0", np.any(rows[:, A:A + 7] < 0.0, axis=1)),
+              ("damping < 0", np.any(rows[:, D:D + 7] < 0.0, axis=1)),
+              ("r_tool <= 0", rows[:, _abi.PLANT_ROW_R_TOOL] <= 0.0),
+              ("solref <= 0", (rows[:, SR] <= 0.0) | (rows[:, SR + 1] <= 0.0)),
+              ("solimp d0 / dmax outside (0, 1) or dmax < d0",
+               (d0 <= 0.0) | (d0 >= 1.0) | (dmax <= 0.0) | (dmax >= 1.0) | (dmax < d0)),
+              ("solimp mid outside (0, 1)", (mid <= 0.0) | (mid >= 1.0)),
+              ("solimp power < 1", power < 1.0))
+    for what, bad in checks:
+        if np.any(bad):
+            raise ValueError(f"plant rows: {what} (row {int(np.argmax(bad))})")
+    return rows
+
+
+def plant_rows(seq) -> np.ndarray:
+    """(B, PLANT_ROW_W) rows of a sequence of PlantPhysics, checked (check_plant_rows)."""
+    seq = list(seq)
+    if not seq or not all(isinstance(p, PlantPhysics) for p in seq):
+        raise ValueError("plant_rows: a non-empty sequence of PlantPhysics")
+    return check_plant_rows(np.stack([p.row() for p in seq]))
+
+
 def observation_from_record(rec, tau_cmd=None, tilt_deg: float = 0.0) -> Observation:
     """Observation of one FFDDP_PLANT_OBS record (no torque filters: the
     tau_meas* fields hold the unfiltered tau_total)."""
@@ -135,9 +192,12 @@ def observation_from_record(rec, tau_cmd=None, tilt_deg: float = 0.0) -> Observa
 
 class BatchedPlant:
     """B plant instances on one device; host-array stepping (one launch per
-    control step).  ``obs`` rows follow FFDDP_PLANT_OBS (ffddp_plant.hpp)."""
+    control step).  ``obs`` rows follow FFDDP_PLANT_OBS (ffddp_plant.hpp).
+    physics: None (every instance integrates with ``params``), or what
+    ``set_physics`` takes."""
 
-    def __init__(self, B: int, timestep: float = DEFAULT_TIMESTEP, n_substeps: int = 1, device: int = 0):
+    def __init__(self, B: int, timestep: float = DEFAULT_TIMESTEP, n_substeps: int = 1, device: int = 0,
+                 physics=None):
         self.lib = _abi.load()
         self.B = int(B)
         self.params = plant_params(timestep, n_substeps)
@@ -151,6 +211,31 @@ class BatchedPlant:
         self.v = np.zeros((self.B, 7))
         self.plane = np.tile(np.concatenate(table_plane(0.0)), (self.B, 1))
         self.obs = np.zeros((self.B, _abi.PLANT_OBS))
+        self.physics = None  # the (B, PLANT_ROW_W) rows in force, or None: the handle's struct
+        if physics is not None:
+            self.set_physics(physics)
+
+    def set_physics(self, rows):
+        """Per-instance physics (ffddp_plant_set_instance_params): a sequence
+        of B PlantPhysics or a (B, PLANT_ROW_W) array, instance b integrating
+        with row b from the next step on (``step`` and ``step_dev`` alike);
+        None: back to ``params`` for all.  Invalid rows are a ValueError and
+        leave what was in force."""
+        if rows is None:
+            rc = self.lib.ffddp_plant_set_instance_params(self._h, 0, None)
+            if rc:
+                raise RuntimeError(f"ffddp_plant_set_instance_params failed ({rc})")
+            self.physics = None
+            return
+        if not isinstance(rows, np.ndarray) and len(rows) and isinstance(rows[0], PlantPhysics):
+            rows = plant_rows(rows)
+        rows = check_plant_rows(rows)
+        if rows.shape[0] != self.B:
+            raise ValueError(f"BatchedPlant.set_physics: {rows.shape[0]} rows for {self.B} instances")
+        rc = self.lib.ffddp_plant_set_instance_params(self._h, self.B, _abi.dptr(rows))
+        if rc:
+            raise RuntimeError(f"ffddp_plant_set_instance_params failed ({rc})")
+        self.physics = rows.copy()
 
     @property
     def dt(self) -> float:

@@ -502,7 +502,33 @@ class BatchedBoxFDDP:
             setattr(inj, k, int(t[k].data_ptr()) if t.get(k) is not None else 0)
         return inj
 
-    def fleet_inject_obs_dev(self, t, inj: _abi.FleetInject, k: int, z=None, stream=None):
+    @staticmethod
+    def fleet_inject_rows(t) -> _abi.FleetInjectRows:
+        """ffddp_fleet_inject_rows from the device tensors t["d_obs"], t["d_cmd"]
+        (rows,) int32 -- each row's delays in ticks, at most the ring depths of
+        the ffddp_fleet_inject they go with -- and t["sigma"] (rows, 3)
+        float64; a missing one leaves that member null (the scalar holds).
+        The delays are read back once and checked against the depths of
+        t["obs_ring"] / t["cmd_ring"] (ValueError; the kernels would clamp
+        them).  The struct holds the pointers: keep the tensors alive."""
+        import torch
+
+        w = _abi.FleetInjectRows()
+        n = int(t["a"].shape[0]) if t.get("a") is not None else None
+        for k, dt, tail in (("d_obs", torch.int32, ()), ("d_cmd", torch.int32, ()), ("sigma", torch.float64, (3,))):
+            a = t.get(k)
+            if a is not None:
+                assert a.dtype == dt and a.is_contiguous() and tuple(a.shape[1:]) == tail and n in (None, int(a.shape[0]))
+            setattr(w, k, int(a.data_ptr()) if a is not None else 0)
+        for k, ring in (("d_obs", "obs_ring"), ("d_cmd", "cmd_ring")):
+            if t.get(k) is not None and t.get(ring) is not None and t[k].numel():
+                d, depth = t[k].cpu().numpy(), int(t[ring].shape[0]) - 1
+                if d.min() < 0 or d.max() > depth:
+                    raise ValueError(f"fleet_inject_rows: {k} must lie in 0..{depth} (the depth of {ring}), "
+                                     f"got {int(d.min())}..{int(d.max())}")
+        return w
+
+    def fleet_inject_obs_dev(self, t, inj: _abi.FleetInject, k: int, z=None, stream=None, rows=None):
         """Tick k's observation_for_controller for B instances in one launch,
         enqueued after the plant step and before fleet_pre_dev.  t["q"], t["v"]
         (B, 7): the plant's true state (strided views of its records); z
@@ -510,28 +536,35 @@ class BatchedBoxFDDP:
         Writes t["qv_ctrl"] (B, 14), optionally t["tau_hat"] and t["tau_ctrl"]
         (B, 7: the raw and the filtered torque measurement), and the injector
         state in `inj`; instances with row -1 pass (q, v) and, when given,
-        t["tau_filt"] (B, 7) through.  Asynchronous on `stream`."""
+        t["tau_filt"] (B, 7) through.  rows: fleet_inject_rows' struct, each
+        instance's own delays and sigmas (ffddp_fleet_inject_obs_rows_dev);
+        None: the scalars of `inj`.  Asynchronous on `stream`."""
         B = int(t["qv_ctrl"].shape[0])
         p = lambda k_: C.c_void_p(int(t[k_].data_ptr()) if t.get(k_) is not None else 0)
         assert t["q"].stride(0) == t["v"].stride(0) and t["qv_ctrl"].is_contiguous()
         assert z is None or (z.is_contiguous() and tuple(z.shape) == (inj.rows, _abi.INJECT_NZ))
-        rc = self._lib.ffddp_fleet_inject_obs_dev(
-            self._h, B, C.byref(inj), int(k), C.c_void_p(int(z.data_ptr()) if z is not None else 0), p("q"), p("v"),
-            int(t["q"].stride(0)), p("tau_filt"), p("qv_ctrl"), p("tau_hat"), p("tau_ctrl"),
-            C.c_void_p(stream if stream else 0),
-        )
+        args = (self._h, B, C.byref(inj), int(k), C.c_void_p(int(z.data_ptr()) if z is not None else 0), p("q"), p("v"),
+                int(t["q"].stride(0)), p("tau_filt"), p("qv_ctrl"), p("tau_hat"), p("tau_ctrl"))
+        if rows is not None:
+            rc = self._lib.ffddp_fleet_inject_obs_rows_dev(*args, C.byref(rows), C.c_void_p(stream if stream else 0))
+            self._check(rc, "ffddp_fleet_inject_obs_rows_dev")
+            return
+        rc = self._lib.ffddp_fleet_inject_obs_dev(*args, C.c_void_p(stream if stream else 0))
         self._check(rc, "ffddp_fleet_inject_obs_dev")
 
-    def fleet_inject_cmd_dev(self, t, inj: _abi.FleetInject, k: int, stream=None):
+    def fleet_inject_cmd_dev(self, t, inj: _abi.FleetInject, k: int, stream=None, rows=None):
         """Tick k's command_for_plant, enqueued after fleet_post_dev and before
         the next plant step: t["tau_app"] (B, 7) of the injected instances
         becomes a * (delayed t["tau_cmd"]) + b + noise; the others keep what
-        post wrote.  Asynchronous on `stream`."""
+        post wrote.  rows: as fleet_inject_obs_dev's.  Asynchronous on `stream`."""
         B = int(t["tau_cmd"].shape[0])
-        rc = self._lib.ffddp_fleet_inject_cmd_dev(
-            self._h, B, C.byref(inj), int(k), C.c_void_p(int(t["tau_cmd"].data_ptr())),
-            C.c_void_p(int(t["tau_app"].data_ptr())), C.c_void_p(stream if stream else 0),
-        )
+        args = (self._h, B, C.byref(inj), int(k), C.c_void_p(int(t["tau_cmd"].data_ptr())),
+                C.c_void_p(int(t["tau_app"].data_ptr())))
+        if rows is not None:
+            rc = self._lib.ffddp_fleet_inject_cmd_rows_dev(*args, C.byref(rows), C.c_void_p(stream if stream else 0))
+            self._check(rc, "ffddp_fleet_inject_cmd_rows_dev")
+            return
+        rc = self._lib.ffddp_fleet_inject_cmd_dev(*args, C.c_void_p(stream if stream else 0))
         self._check(rc, "ffddp_fleet_inject_cmd_dev")
 
     def fleet_noise_dev(self, seed, k: int, z, words=None, stream=None):

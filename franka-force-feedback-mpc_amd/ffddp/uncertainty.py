@@ -123,31 +123,52 @@ class BatchedUncertaintyInjector:
     measurement ``tau_hat`` (the scalar tau_meas_act) and its first-order
     filter ``tau_hat_filt`` (tau_meas_act_filt), both (B, nu).  Bit-identical
     to per-instance ScenarioUncertaintyInjector calls
-    (tests/test_closed_loop.py, tests/test_fleet_ff_cpu.py)."""
+    (tests/test_closed_loop.py, tests/test_fleet_ff_cpu.py).
+
+    The configs may be any mix: instance i keeps its own delays
+    (``delay[i]`` = delay_steps(cfg_i, dt), in ticks), its own sigma triple
+    (``sigma[i]``) and its own a / b ranges.  The rings are as deep as the
+    largest delay, [d_max + 1][B][.]; instance i uses slots 0..d_i of its
+    column with its own modulus, so its slot sequence is the one a ring of its
+    own depth would give.  ``delay`` (B, 2) and ``sigma`` (B, 3) may also be
+    given explicitly, in place of the configs' values.  ``obs_delay_steps`` /
+    ``cmd_delay_steps`` are the ring depths (the largest delays: every
+    instance's when they agree) and ``sig`` the common sigma triple, or None
+    when the instances' sigmas differ."""
 
     CHUNK = 256  # ticks of normals drawn per Generator call
 
-    def __init__(self, dt: float, nu: int, configs, tau_lpf_alpha: float = 0.2):
+    def __init__(self, dt: float, nu: int, configs, tau_lpf_alpha: float = 0.2, delay=None, sigma=None):
         self.nu = int(nu)
         self.dt = float(max(dt, 1.0e-9))
         self.cfgs = list(configs)
         self.B = len(self.cfgs)
         c0 = self.cfgs[0] if self.cfgs else UncertaintyProfileConfig()
-        for c in self.cfgs:  # one delay / noise model (they differ by seed only)
-            if dataclasses.replace(c, seed=0) != dataclasses.replace(c0, seed=0):
-                raise ValueError("BatchedUncertaintyInjector: configs may differ by seed only")
         self.rngs = [np.random.default_rng(int(c.seed)) for c in self.cfgs]
         ab = [(float(r.uniform(float(c.a_min), float(c.a_max))), float(r.uniform(float(c.b_min), float(c.b_max))))
               for r, c in zip(self.rngs, self.cfgs)]
         self.a = np.array([x[0] for x in ab])
         self.b = np.array([x[1] for x in ab])
-        self.obs_delay_steps = int(max(np.round(int(max(c0.delta_obs_cycles, 0)) * 1.0e-3 / self.dt), 0))
-        self.cmd_delay_steps = int(max(np.round(float(c0.delta_cmd_s) / self.dt), 0))
+        if delay is None:
+            delay = [delay_steps(c, self.dt) for c in self.cfgs]
+        if sigma is None:
+            sigma = [(float(c.sigma_q), float(c.sigma_dq), float(c.sigma_tau)) for c in self.cfgs]
+        self.delay = np.array(delay, dtype=np.int64).reshape(self.B, 2)
+        self.sigma = np.array(sigma, dtype=float).reshape(self.B, 3)
+        if np.any(self.delay < 0):
+            raise ValueError("BatchedUncertaintyInjector: a delay below 0")
+        d0 = delay_steps(c0, self.dt)
+        self.obs_delay_steps = int(self.delay[:, 0].max()) if self.B else d0[0]
+        self.cmd_delay_steps = int(self.delay[:, 1].max()) if self.B else d0[1]
         self.sig = (float(c0.sigma_q), float(c0.sigma_dq), float(c0.sigma_tau))
-        self._obs = None  # [D+1][B][14] ring of (q, dq); slot _oi is the oldest
-        self._oi = 0
+        if self.B:
+            self.sig = tuple(float(x) for x in self.sigma[0]) if np.all(self.sigma == self.sigma[0]) else None
+        self._all = np.arange(self.B)
+        self._no, self._nc = self.delay[:, 0] + 1, self.delay[:, 1] + 1  # each instance's ring moduli
+        self._obs = None  # [D+1][B][14] ring of (q, dq); instance i's slot _oi[i] is its oldest
+        self._oi = np.zeros(self.B, dtype=np.int64)
         self._cmd = np.zeros((self.cmd_delay_steps + 1, self.B, self.nu))
-        self._ci = 0
+        self._ci = np.zeros(self.B, dtype=np.int64)
         self._z = np.zeros((self.B, 0, 4 * self.nu))
         self._zi = 0
         self._tau_lpf_alpha = float(np.clip(tau_lpf_alpha, 0.0, 1.0))
@@ -165,7 +186,8 @@ class BatchedUncertaintyInjector:
         return z
 
     def _tau_hat(self, z7):
-        return self.a[:, None] * self._cmd[self._ci] + self.b[:, None] + (0.0 + self.sig[2] * z7)
+        return (self.a[:, None] * self._cmd[self._ci, self._all] + self.b[:, None]
+                + (0.0 + self.sigma[:, 2:3] * z7))
 
     def observation_for_controller(self, q, dq):
         """(q, dq) [B][nu] -> the delayed, noisy (q, dq) the controllers see."""
@@ -173,14 +195,14 @@ class BatchedUncertaintyInjector:
         cur = np.concatenate([np.asarray(q, float), np.asarray(dq, float)], 1)
         if self._obs is None:
             self._obs = np.repeat(cur[None], self.obs_delay_steps + 1, 0)
-            self._oi = 0
+            self._oi[:] = 0
         else:  # deque(maxlen).append: the oldest slot takes the newest entry
-            self._obs[self._oi] = cur
-            self._oi = (self._oi + 1) % (self.obs_delay_steps + 1)
-        old = self._obs[self._oi]
+            self._obs[self._oi, self._all] = cur
+            self._oi = (self._oi + 1) % self._no
+        old = self._obs[self._oi, self._all]
         self._z_tick = z = self._normals()
-        qo = old[:, :nu] + (0.0 + self.sig[0] * z[:, :nu])
-        dqo = old[:, nu:] + (0.0 + self.sig[1] * z[:, nu:2 * nu])
+        qo = old[:, :nu] + (0.0 + self.sigma[:, 0:1] * z[:, :nu])
+        dqo = old[:, nu:] + (0.0 + self.sigma[:, 1:2] * z[:, nu:2 * nu])
         # the torque measurement and its filter, as ScenarioUncertaintyInjector.observation_for_controller
         self.tau_hat = self._tau_hat(z[:, 2 * nu:3 * nu])
         a = self._tau_lpf_alpha
@@ -189,8 +211,8 @@ class BatchedUncertaintyInjector:
 
     def command_for_plant(self, tau_cmd):
         """tau_cmd [B][nu] -> the applied torques a * (delayed command) + b + noise."""
-        self._cmd[self._ci] = np.asarray(tau_cmd, float)
-        self._ci = (self._ci + 1) % (self.cmd_delay_steps + 1)
+        self._cmd[self._ci, self._all] = np.asarray(tau_cmd, float)
+        self._ci = (self._ci + 1) % self._nc
         return self._tau_hat(self._z_tick[:, 3 * self.nu:])
 
 

@@ -607,6 +607,40 @@ int ffddp_fleet_inject_cmd_dev(ffddp_handle* h, int B, const ffddp_fleet_inject*
 int ffddp_fleet_noise_dev(ffddp_handle* h, int B, const uint64_t* seed, int k, double* z, uint64_t* words,
                           void* stream);
 
+/* Per-instance uncertainty profiles: the two injector calls with each injected
+ * instance's own delays and noise levels.  ffddp_fleet_inject keeps its layout
+ * and its meaning: inj->d_obs / inj->d_cmd are the ring depths (the rings are
+ * [d_obs+1][B][14] and [d_cmd+1][B][7] as before), inj->sigma_* the levels of
+ * a row whose array below is NULL.  The arrays are device memory indexed like
+ * a / b / seed, by row[b].
+ *
+ * Slot rule per injected instance with row r, no = d_obs[r] + 1: the
+ * observation ring is written at (k - 1) mod no and read at k mod no; at k = 0
+ * slots 0 .. d_obs[r] take the first observation.  The command ring, nc =
+ * d_cmd[r] + 1: written at k mod nc, read at (k + 1) mod nc.  An instance
+ * never touches a slot above its own delay; its slot sequence is that of a
+ * ring of its own depth.  The kernels clamp a delay into [0, depth], so no
+ * value indexes outside a ring (the caller validates; a clamped delay is not
+ * the profile that was asked for).  The arithmetic per element is that of
+ * ffddp_fleet_inject_obs_dev / _cmd_dev with the row's sigma in place of the
+ * scalar: no contraction, numpy's bits.
+ *
+ * rows == NULL, or all three members NULL: exactly ffddp_fleet_inject_obs_dev
+ * / ffddp_fleet_inject_cmd_dev (the same kernels are launched).  Error codes
+ * as for those calls. */
+typedef struct ffddp_fleet_inject_rows {   /* per row of a / b / seed; a NULL member = the scalar of ffddp_fleet_inject */
+  const int32_t* d_obs;   /* [rows] observation delay in ticks, 0 .. inj->d_obs (the ring depth) */
+  const int32_t* d_cmd;   /* [rows] command delay in ticks, 0 .. inj->d_cmd */
+  const double* sigma;    /* [rows][3] sigma_q, sigma_dq, sigma_tau */
+} ffddp_fleet_inject_rows;
+int ffddp_fleet_inject_obs_rows_dev(ffddp_handle* h, int B, const ffddp_fleet_inject* inj, int k, const double* z,
+                                    const double* q, const double* v, int ld_qv, const double* tau_filt,
+                                    double* qv_ctrl, double* tau_hat, double* tau_ctrl,
+                                    const ffddp_fleet_inject_rows* rows, void* stream);
+int ffddp_fleet_inject_cmd_rows_dev(ffddp_handle* h, int B, const ffddp_fleet_inject* inj, int k,
+                                    const double* tau_cmd, double* tau_app, const ffddp_fleet_inject_rows* rows,
+                                    void* stream);
+
 /* Per-instance tasks and start delays: every instance carries a record of its
  * own approach-then-circle task (ffddp/trajectory.py FleetTask, task_records)
  * and the pre kernel samples that instance's N+1 node references and its
@@ -774,6 +808,27 @@ int ffddp_plant_step(ffddp_plant* h, int B, double* q, double* v, const double* 
 /* Same on device pointers, asynchronous on `stream` (per-instance failure flags in fail[B], may be NULL). */
 int ffddp_plant_step_dev(ffddp_plant* h, int B, double* q, double* v, const double* tau, const double* plane,
                          int integrate, double* obs, int32_t* fail, void* stream);
+
+/* Per-instance physics: one row per instance of what ffddp_plant_params holds
+ * apart from timestep, n_substeps and site_R, which stay the handle's.  rows:
+ * host memory, [n][FFDDP_PLANT_ROW_W], row-major; the handle keeps its own
+ * device copy (field-major, so a wave's loads of one field are consecutive
+ * doubles).  From the next ffddp_plant_step / ffddp_plant_step_dev on, with
+ * B <= n, instance b integrates with row b; B > n is FFDDP_E_INVALID.  rows
+ * == NULL (n is ignored): back to the handle's struct for all.  The call
+ * waits for the device's work before it replaces the copy.
+ * FFDDP_E_INVALID with nothing changed for a null handle, n < 1 or n >
+ * max_batch, or any row with a non-finite entry, armature < 0 or damping < 0,
+ * r_tool <= 0, solref[0] <= 0 or solref[1] <= 0, solimp d0 or dmax outside
+ * (0, 1) or dmax < d0, mid outside (0, 1), power < 1. */
+#define FFDDP_PLANT_ROW_W 23
+#define FFDDP_PLANT_ROW_ARMATURE 0 /* [7] */
+#define FFDDP_PLANT_ROW_DAMPING 7  /* [7] */
+#define FFDDP_PLANT_ROW_R_TOOL 14
+#define FFDDP_PLANT_ROW_MARGIN 15
+#define FFDDP_PLANT_ROW_SOLREF 16  /* [2] timeconst, dampratio */
+#define FFDDP_PLANT_ROW_SOLIMP 18  /* [5] d0, dmax, width, mid, power */
+int ffddp_plant_set_instance_params(ffddp_plant* h, int n, const double* rows);
 
 #ifdef __cplusplus
 }

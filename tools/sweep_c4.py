@@ -19,6 +19,9 @@ wall time, closed-loop ticks/s).
   python tools/sweep_c4.py --device-loop 1 --device-refs 1 --solve-period 4 --stagger 4   # start delays (b mod 4) dt
   python tools/sweep_c4.py --device-loop 1 --device-refs 1 --device-summary 1 --keep-logs 0   # the summary's sums on the
                                                                # device, no per-tick logs: any --time in constant memory
+  python tools/sweep_c4.py --device-loop 1 --device-noise philox --plant-spread 0.5 0.5 --uncertainty-spread 0.5 3
+                                                               # table stiffness, joint damping, noise levels and
+                                                               # delays vary per instance (host path too)
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/sweep_c4.py
 """
 import argparse
@@ -69,12 +72,23 @@ def main():
                     help="with --device-loop 1: accumulate the summary's sums on the device, one more launch per tick")
     ap.add_argument("--keep-logs", type=int, choices=(0, 1), default=1,
                     help="with --device-summary 1: 0 keeps no per-tick logs (memory no longer grows with --time)")
+    ap.add_argument("--plant-spread", type=float, nargs=2, default=None, metavar=("DS", "DD"),
+                    help="per-instance plant physics: contact time constant 0.02 (1 + DS u0), joint damping "
+                         "1.0 (1 + DD u1), u in [-1, 1]; each spread in [0, 0.9]")
+    ap.add_argument("--uncertainty-spread", type=float, nargs=2, default=None, metavar=("DN", "D"),
+                    help="per-instance injector profile: sigmas scaled by 1 + DN u, u in [-1, 1], DN in [0, 1); "
+                         "observation and command delay each 0..D ticks, D an integer 0..16")
     ap.add_argument("--scenarios", nargs="+", default=list(ALL_SCENARIOS), help="scenarios to sweep (default: all 5)")
     a = ap.parse_args()
     import torch
     import torch.distributed as dist
     from ffddp import fleet, shard
 
+    uspread = None
+    if a.uncertainty_spread is not None:
+        if a.uncertainty_spread[1] != int(a.uncertainty_spread[1]):
+            ap.error("--uncertainty-spread: D is an integer number of ticks")
+        uspread = (a.uncertainty_spread[0], int(a.uncertainty_spread[1]))
     rank, world, local = shard.env_ranks()
     shard.init("nccl", local, world)
     torch.cuda.set_device(local)
@@ -86,7 +100,8 @@ def main():
                            device_loop=bool(a.device_loop), device_noise=a.device_noise,
                            solve_period=a.solve_period, command_filter=bool(a.command_filter),
                            device_refs=bool(a.device_refs), task_spread=a.task_spread, stagger=a.stagger,
-                           device_summary=bool(a.device_summary), keep_logs=bool(a.keep_logs))
+                           device_summary=bool(a.device_summary), keep_logs=bool(a.keep_logs),
+                           plant_spread=a.plant_spread, uncertainty_spread=uspread)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -107,6 +122,21 @@ def main():
                     loop_ms_per_tick=1.0e3 * res["wall_s"] / max(1, res["ticks"]))
         line.update(device_summary=int(a.device_summary), keep_logs=int(a.keep_logs),
                     wall_ms_per_tick=1.0e3 * wall / max(1, res["ticks"]), rank0_device_memory=dict(fleet.DEVICE_MEMORY) or None)
+        # the mismatch axes as run (this rank's shard): the ranges of the contact time constant, the joint damping,
+        # the injectors' delays and torque-noise level, and the instances lost to a failed plant step
+        rows, dly, sig = res["plant_rows"], res["inject_delay"], res["inject_sigma"]
+        inj = dly[:, 0] >= 0
+        line.update(plant_spread=a.plant_spread, uncertainty_spread=a.uncertainty_spread,
+                    rank0_timeconst_range=[float(rows[:, 16].min()), float(rows[:, 16].max())],
+                    rank0_damping_range=[float(rows[:, 7].min()), float(rows[:, 7].max())],
+                    rank0_inject_delay_max=[int(x) for x in dly[inj].max(0)] if inj.any() else None,
+                    rank0_sigma_tau_range=[float(sig[inj, 2].min()), float(sig[inj, 2].max())] if inj.any() else None,
+                    rank0_plant_fail_instances=int(np.count_nonzero(res.get("plant_fail", 0))))
+        # instances that left the nominal regime, per scenario: any tick on the unstable fallback; a non-finite summary
+        ui, ri = fleet.SUMMARY_KEYS.index("unstable_ticks"), fleet.SUMMARY_KEYS.index("rms_3d_error")
+        line["diverged"] = {str(s): {"unstable_instances": int(np.sum(m[names == s, ui] > 0)),
+                                     "nonfinite_instances": int(np.sum(~np.isfinite(m[names == s, ri])))}
+                            for s in dict.fromkeys(names)}
         if "solved" in res:  # the share of instances that solve per tick, once every instance has switched to contact
             surf, share = res["surface"], res["solved"].mean(1)
             k0 = int(np.max(np.argmax(surf, 0))) + 1 if surf.any(0).all() else len(share)
