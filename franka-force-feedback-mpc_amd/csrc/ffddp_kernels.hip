@@ -116,6 +116,8 @@ struct Dev {
                      //         needed more step lengths than the host's first pass (first_width)
   double* trace;     // [B][trace_it][FFDDP_TRACE_W] per-iteration records (CallbackVerbose), or null
   int trace_it;
+  const double* fref;  // [B][N+1] desired normal contact force per instance and node (ffddp_solve_batch_fref_dev),
+                       //          read by the FR instantiations of k_node / k_forward_g8 only; null: C.fn_ref
 };
 
 // Active-instance compaction.  Iteration it reads list (it & 1): the
@@ -270,7 +272,7 @@ struct NodeShared {
 // The calc of one node on an 8-lane group (lanes = joints + EE): dynamics,
 // costs with their Gauss-Newton weights, gaps; Primal and link record to P /
 // lk (the node group's LDS in k_node).
-template <int NC, bool FF>
+template <int NC, bool FF, bool FR>
 __device__ __forceinline__ void primal_group(const DevConsts& C, const Dev& d, const double* __restrict__ x0,
                                              const double* __restrict__ node_ref, const double* __restrict__ inst_ref,
                                              const uint8_t* __restrict__ surface, int b, int t, Primal* P,
@@ -308,8 +310,8 @@ __device__ __forceinline__ void primal_group(const DevConsts& C, const Dev& d, c
     }
   }
   double lam[3];
-  const double pc = node_primal_g8<NC>(C, mode, surf, q, v, u, xreg[ji], xreg[7 + ji], xreg[14 + ji], ref,
-                                       P, lk, lam);
+  const double pc = node_primal_g8<NC, FR>(C, mode, surf, q, v, u, xreg[ji], xreg[7 + ji], xreg[14 + ji], ref,
+                                           P, lk, lam, FR ? d.fref + ((long)b * (N + 1) + t) : nullptr);
   double* rec = d.rec_buf + ((long)b * (N + 1) + t) * d.rec;
   // node cost (IAM scaling, FF augmentation terms): per-lane shares summed over the group
   double c = FF ? C.dt * pc : (terminal ? pc : C.dt * pc);
@@ -388,7 +390,9 @@ __device__ __forceinline__ double fquad(const double* a, const double* Dd, const
 // group's LDS, so the Primal / link records (~4 KB per node) never round-trip
 // through HBM: a separate calc kernel writing them and this one reading them
 // back was 129 + 366 us per launch at B=4096; fused, 255 us.
-template <int NC, bool FF>
+// FR: the fn_track cost reads d.fref[b][t] instead of C.fn_ref (a solve with
+// a force_ref); FR = false is the kernel as it was.
+template <int NC, bool FF, bool FR = false>
 __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE_WAVES))) void k_node(const DevConsts* __restrict__ Cg, Dev d,
                                                       const double* __restrict__ x0,
                                                       const double* __restrict__ node_ref,
@@ -427,7 +431,7 @@ __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE
   const double* ref = node_ref + ((long)b * (N + 1) + t) * 6;
   NodeGroupShared& G = S.g[grp];
   Primal& P = G.P;
-  if (active && lane < G8) primal_group<NC, FF>(C, d, x0, node_ref, inst_ref, surface, b, t, &P, G.lk, xsrc, usrc);
+  if (active && lane < G8) primal_group<NC, FF, FR>(C, d, x0, node_ref, inst_ref, surface, b, t, &P, G.lk, xsrc, usrc);
   __syncthreads();
   const bool need_u = mode != MODE_TERMINAL_X;
   // control directions first, their results stored at once (neither touches
@@ -1982,7 +1986,9 @@ __device__ __forceinline__ int ls_row_bcast0(int v) {  // lane 0 of the row into
 #ifndef FW_WPE
 #define FW_WPE 1  // waves per SIMD of the two-groups-per-row layout's register budget
 #endif
-template <int NC, bool FF, bool ROW>
+// FR: d.fref[b][t] is the node's force reference, prefetched with its
+// position / velocity references one node ahead.
+template <int NC, bool FF, bool ROW, bool FR = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW_WPE))) void k_forward_g8(const DevConsts* __restrict__ Cg, Dev d,
                                                    const double* __restrict__ x0,
                                                    const double* __restrict__ node_ref,
@@ -2063,10 +2069,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
   // node inputs of the rollout, prefetched one node ahead (joint lane ji)
   constexpr int NCX = FF ? 3 : 2;  // state components per joint lane
   double pxs[3] = {0, 0, 0}, pfs[3] = {0, 0, 0}, pw[3] = {0, 0, 0}, pK[21], pus = 0.0, pk = 0.0, pref[6];
+  double pfr = 0.0;
   auto fetch = [&](int t) {
     const long nb = (long)b * (N + 1) + t;
 #pragma unroll
     for (int c = 0; c < 6; ++c) pref[c] = node_ref[nb * 6 + c];
+    if constexpr (FR) pfr = d.fref[nb];
 #pragma unroll
     for (int c = 0; c < NCX; ++c) {
       pxs[c] = J ? d.xs[nb * nx + 7 * c + ji] : 0.0;
@@ -2104,6 +2112,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
     double ref[6];
 #pragma unroll
     for (int c = 0; c < 6; ++c) ref[c] = pref[c];
+    const double fnr = pfr;
     if (t < N) {
       // u_i = us_i - alpha k_i - K_i (x - xs)  (crocoddyl order: x components q, v, tau)
       double u = 0.0;
@@ -2125,7 +2134,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
       double qn, vn, cp, lam[3];
       const double uin = FF ? xt_t : u;
       PP(8);
-      ls_node_calc<NC, ROW>(C, fl, K, MODE_RUNNING, surf, xq_t, xv_t, uin, xq, xv, tref, ref, qn, vn, cp, lam
+      ls_node_calc<NC, ROW, FR>(C, fl, K, MODE_RUNNING, surf, xq_t, xv_t, uin, xq, xv, tref, ref, fnr, qn, vn, cp, lam
 #ifdef FFDDP_PHASE_PROF
                             , pp_acc, pp_last
 #endif
@@ -2158,7 +2167,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
       double qn, vn, cp, lam[3];
       const int mode = FF ? MODE_TERMINAL_U : MODE_TERMINAL_X;
       PP(8);
-      ls_node_calc<NC, ROW>(C, fl, K, mode, surf, xq_t, xv_t, FF ? xt_t : 0.0, xq, xv, tref, ref, qn, vn, cp, lam
+      ls_node_calc<NC, ROW, FR>(C, fl, K, mode, surf, xq_t, xv_t, FF ? xt_t : 0.0, xq, xv, tref, ref, fnr, qn, vn, cp, lam
 #ifdef FFDDP_PHASE_PROF
                             , pp_acc, pp_last
 #endif
@@ -3193,14 +3202,15 @@ Dev dev_slice(const Dev& d0, int b0, int Bk, int k) {
   d.alist += 2L * b0;
   d.acnt += 4 * k;
   if (d.trace) d.trace += (long)b0 * d0.trace_it * FFDDP_TRACE_W;
+  if (d.fref) d.fref += (long)b0 * (N + 1);
   return d;
 }
 
-template <int NC, bool FF>
+template <int NC, bool FF, bool FR = false>
 int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref, const double* iref,
                  const uint8_t* surf, const double* xs_init, const double* us_init, int maxiter, int is_feasible,
                  double* xs, double* us, double* K, double* cost, int32_t* iters, uint8_t* ok, double* fn_pred,
-                 int32_t* stats, hipStream_t s, HostIO* io, const uint8_t* active) {
+                 int32_t* stats, hipStream_t s, HostIO* io, const uint8_t* active, const double* fref = nullptr) {
   const int N = h->hc.N, nx = h->hc.nx;
   int S = h->nstreams;
   if (B < 64 * S) S = 1;
@@ -3233,6 +3243,7 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
   // buffers), so no copy of the solution follows the last kernel; the host
   // entry point keeps the handle's buffers (its outputs are host memory)
   Dev dbase = h->d;
+  dbase.fref = FR ? fref : nullptr;
   if (!io) {
     dbase.xs = xs;
     dbase.us = us;
@@ -3296,7 +3307,7 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
     if (it == 0 && stagger == 2 && k + 1 < S) HIPCHK(h, hipEventRecord(h->stg[k], ss));
     {
       ProfScope p(h, ss, KC_NODE);
-      hipLaunchKernelGGL((k_node<NC, FF>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, ss,
+      hipLaunchKernelGGL((k_node<NC, FF, FR>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, ss,
                          h->dc, d, x0k, nrefk, irefk, surfk, 0, it & 1);
     }
     if (it == 0 && stagger == 1 && k + 1 < S) HIPCHK(h, hipEventRecord(h->stg[k], ss));
@@ -3367,13 +3378,13 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
         const long groups = more ? (long)Bk * ntr : g1;
         if (!row_only) {
           const dim3 grid((unsigned)((groups * G8 + 63) / 64));
-          hipLaunchKernelGGL((k_forward_g8<NC, FF, false>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
+          hipLaunchKernelGGL((k_forward_g8<NC, FF, false, FR>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
                              surfk, tr0, ntr, more, it & 1, wide, row_max);
         }
         if (row_max > 0) {
           const long rg = std::min(groups, (long)row_max);  // the row layout runs only when they fit
           const dim3 grid((unsigned)((rg * 16 + 63) / 64));
-          hipLaunchKernelGGL((k_forward_g8<NC, FF, true>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
+          hipLaunchKernelGGL((k_forward_g8<NC, FF, true, FR>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
                              surfk, tr0, ntr, more, it & 1, wide, row_max);
         }
       };
@@ -3475,20 +3486,26 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
 int launch_solve(ffddp_handle* h, int B, const double* x0, const double* nref, const double* iref,
                  const uint8_t* surf, const double* xs_init, const double* us_init, int maxiter, int is_feasible,
                  double* xs, double* us, double* K, double* cost, int32_t* iters, uint8_t* ok, double* fn_pred,
-                 int32_t* stats, hipStream_t s, HostIO* io = nullptr, const uint8_t* active = nullptr) {
+                 int32_t* stats, hipStream_t s, HostIO* io = nullptr, const uint8_t* active = nullptr,
+                 const double* fref = nullptr) {
   const bool ff = h->hc.variant == FFDDP_FORCE_FEEDBACK;
   const int nc = h->hc.nc;
-#define FFDDP_LS(NC_, FF_) \
-  launch_solve_t<NC_, FF_>(h, B, x0, nref, iref, surf, xs_init, us_init, maxiter, is_feasible, xs, us, K, cost, iters, ok, fn_pred, stats, s, io, active)
-  if (nc == 1) return ff ? FFDDP_LS(1, true) : FFDDP_LS(1, false);
-  return ff ? FFDDP_LS(3, true) : FFDDP_LS(3, false);
+  // fref: the solve's force reference; without one the kernels are the FR = false instantiations, as before
+#define FFDDP_LS(NC_, FF_, FR_) \
+  launch_solve_t<NC_, FF_, FR_>(h, B, x0, nref, iref, surf, xs_init, us_init, maxiter, is_feasible, xs, us, K, cost, iters, ok, fn_pred, stats, s, io, active, fref)
+  if (fref) {
+    if (nc == 1) return ff ? FFDDP_LS(1, true, true) : FFDDP_LS(1, false, true);
+    return ff ? FFDDP_LS(3, true, true) : FFDDP_LS(3, false, true);
+  }
+  if (nc == 1) return ff ? FFDDP_LS(1, true, false) : FFDDP_LS(1, false, false);
+  return ff ? FFDDP_LS(3, true, false) : FFDDP_LS(3, false, false);
 #undef FFDDP_LS
 }
 
-template <int NC, bool FF>
+template <int NC, bool FF, bool FR = false>
 void launch_node(ffddp_handle* h, Dev d, int B, hipStream_t s, int force_all) {
   const long nodes = (long)B * (h->hc.N + 1);
-  hipLaunchKernelGGL((k_node<NC, FF>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, s, h->dc,
+  hipLaunchKernelGGL((k_node<NC, FF, FR>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, s, h->dc,
                      d, h->in_x0, h->in_nref, h->in_iref, h->in_surf, force_all, 0);
 }
 
@@ -3745,12 +3762,14 @@ static int mark_solve_done(ffddp_handle* h, hipStream_t s) {
   return 0;
 }
 
-int ffddp_solve_batch_sel_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
-                              const double* inst_ref, const uint8_t* surface, const double* xs_init,
-                              const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
-                              double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
-                              const uint8_t* active, void* stream) {
+int ffddp_solve_batch_fref_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                               const double* inst_ref, const uint8_t* surface, const double* xs_init,
+                               const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
+                               double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
+                               const uint8_t* active, const double* force_ref, void* stream) {
   if (!h) return FFDDP_E_INVALID;
+  if (force_ref && !(h->hc.w_fn > 0.0))
+    return fail(h, FFDDP_E_INVALID, "force_ref given but the handle has no fn_track cost (w_fn <= 0)");
   if (B < 0 || maxiter < 0) return fail(h, FFDDP_E_INVALID, "negative B or maxiter");
   if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
   if (B == 0) return 0;
@@ -3761,9 +3780,18 @@ int ffddp_solve_batch_sel_dev(ffddp_handle* h, int B, const double* x0, const do
   // another (possibly non-blocking) stream must finish before this one starts
   if (h->last_done_set) HIPCHK(h, hipStreamWaitEvent((hipStream_t)stream, h->last_done, 0));
   const int rc = launch_solve(h, B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs, us,
-                              K, cost, iters, ok, fn_pred, stats, (hipStream_t)stream, nullptr, active);
+                              K, cost, iters, ok, fn_pred, stats, (hipStream_t)stream, nullptr, active, force_ref);
   if (rc) return rc;
   return mark_solve_done(h, (hipStream_t)stream);
+}
+
+int ffddp_solve_batch_sel_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                              const double* inst_ref, const uint8_t* surface, const double* xs_init,
+                              const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
+                              double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
+                              const uint8_t* active, void* stream) {
+  return ffddp_solve_batch_fref_dev(h, B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs,
+                                    us, K, cost, iters, ok, fn_pred, stats, active, nullptr, stream);
 }
 
 int ffddp_solve_batch_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref, const double* inst_ref,
@@ -4258,13 +4286,35 @@ int ffddp_trace_read(ffddp_handle* h, int B, double* out) {
 int ffddp_calc_diff(ffddp_handle* h, int B, const double* x0, const double* node_ref, const double* inst_ref,
                     const uint8_t* surface, const double* xs, const double* us, double* Fx, double* Fu, double* Lx,
                     double* Lu, double* Lxx, double* Lxu, double* Luu, double* cost, double* xnext, double* lam) {
+  return ffddp_calc_diff_fref(h, B, x0, node_ref, inst_ref, surface, xs, us, nullptr, Fx, Fu, Lx, Lu, Lxx, Lxu, Luu,
+                              cost, xnext, lam);
+}
+
+int ffddp_calc_diff_fref(ffddp_handle* h, int B, const double* x0, const double* node_ref, const double* inst_ref,
+                         const uint8_t* surface, const double* xs, const double* us, const double* force_ref,
+                         double* Fx, double* Fu, double* Lx, double* Lu, double* Lxx, double* Lxu, double* Luu,
+                         double* cost, double* xnext, double* lam) {
   if (!h) return FFDDP_E_INVALID;
   if (B < 1 || B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "bad B");
+  if (force_ref && !(h->hc.w_fn > 0.0))
+    return fail(h, FFDDP_E_INVALID, "force_ref given but the handle has no fn_track cost (w_fn <= 0)");
   HIPCHK(h, hipSetDevice(h->device));
+  // diagnostic call: the force reference lives in a buffer of its own for the call
+  struct Tmp {
+    double* p = nullptr;
+    ~Tmp() {
+      if (p) (void)hipFree(p);
+    }
+  } fref;
+  if (force_ref) {
+    HIPCHK(h, hipMalloc((void**)&fref.p, (size_t)B * (h->hc.N + 1) * 8));
+    HIPCHK(h, hipMemcpy(fref.p, force_ref, (size_t)B * (h->hc.N + 1) * 8, hipMemcpyHostToDevice));
+  }
   const int N = h->hc.N, nx = h->hc.nx, R = h->d.rec;
   const bool ff = h->hc.variant == FFDDP_FORCE_FEEDBACK;
   Dev d = h->d;
   d.B = B;
+  d.fref = fref.p;
   HIPCHK(h, hipMemcpy(h->in_x0, x0, (size_t)B * nx * 8, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->in_nref, node_ref, (size_t)B * (N + 1) * 6 * 8, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->in_iref, inst_ref, (size_t)B * 21 * 8, hipMemcpyHostToDevice));
@@ -4273,7 +4323,12 @@ int ffddp_calc_diff(ffddp_handle* h, int B, const double* x0, const double* node
   HIPCHK(h, hipMemcpy(h->in_us, us, (size_t)B * N * NU * 8, hipMemcpyHostToDevice));
   // node kernel reads (xs, us) from the solver state: initialise it from the inputs
   hipLaunchKernelGGL(k_init<false>, dim3(1024), dim3(INIT_BLOCK), 0, nullptr, h->dc, d, h->in_xs, h->in_us, 0, nullptr);
-  if (h->hc.nc == 1)
+  if (force_ref) {
+    if (h->hc.nc == 1)
+      ff ? launch_node<1, true, true>(h, d, B, nullptr, 1) : launch_node<1, false, true>(h, d, B, nullptr, 1);
+    else
+      ff ? launch_node<3, true, true>(h, d, B, nullptr, 1) : launch_node<3, false, true>(h, d, B, nullptr, 1);
+  } else if (h->hc.nc == 1)
     ff ? launch_node<1, true>(h, d, B, nullptr, 1) : launch_node<1, false>(h, d, B, nullptr, 1);
   else
     ff ? launch_node<3, true>(h, d, B, nullptr, 1) : launch_node<3, false>(h, d, B, nullptr, 1);
@@ -4540,6 +4595,22 @@ int ffddp_fleet_task_refs_dev(ffddp_handle* h, int B, ffddp_fleet_tasks tasks, c
   return 0;
 }
 
+// per-instance force setpoint profiles (ffddp_force.hpp): the solve's force_ref for this tick
+int ffddp_fleet_force_refs_dev(ffddp_handle* h, int B, ffddp_fleet_tasks tasks, const double* force, int rows,
+                               double fn_default, double* force_ref, void* stream) {
+  if (!h) return FFDDP_E_INVALID;
+  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_force_refs_dev: B must be positive");
+  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  if (!force || !force_ref) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_force_refs_dev: null pointer");
+  if (rows < 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_force_refs_dev: rows below 0");
+  HIPCHK(h, hipSetDevice(h->device));
+  const long n = (long)B * (h->hc.N + 1);
+  hipLaunchKernelGGL(k_fleet_force_refs, dim3((unsigned)((n + FORCE_BLOCK - 1) / FORCE_BLOCK)), dim3(FORCE_BLOCK), 0,
+                     (hipStream_t)stream, B, h->hc.N, h->hc.dt, tasks, force, rows, fn_default, force_ref);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 int ffddp_fleet_pre_task_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
                              const double* q, const double* v, const double* fn_meas, const double* contact,
                              const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
@@ -4576,16 +4647,32 @@ int ffddp_fleet_pre_task_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p
 int ffddp_fleet_metrics_dev(ffddp_handle* h, int B, int ld, const double* obs, int ld_obs, ffddp_fleet_tasks tasks,
                             int rows, double dt, const double* p_ref, double ts, const double* t_phase, double fn_des,
                             const double* info, const uint8_t* need, const int32_t* plant_fail, double* acc, void* stream) {
+  return ffddp_fleet_metrics_fref_dev(h, B, ld, obs, ld_obs, tasks, rows, dt, p_ref, ts, t_phase, fn_des, info, need,
+                                      plant_fail, acc, nullptr, 0, stream);
+}
+
+int ffddp_fleet_metrics_fref_dev(ffddp_handle* h, int B, int ld, const double* obs, int ld_obs, ffddp_fleet_tasks tasks,
+                                 int rows, double dt, const double* p_ref, double ts, const double* t_phase,
+                                 double fn_des, const double* info, const uint8_t* need, const int32_t* plant_fail,
+                                 double* acc, const double* force, int rows_force, void* stream) {
   if (!h) return FFDDP_E_INVALID;
   if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_metrics_dev: B must be positive");
   if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
   if (!obs || !t_phase || !acc || (!tasks.rec && !p_ref))
     return fail(h, FFDDP_E_INVALID, "ffddp_fleet_metrics_dev: null pointer");
-  if (ld < B || ld_obs < 48 || (tasks.rec && rows < 0))
+  if (ld < B || ld_obs < 48 || (tasks.rec && rows < 0) || (force && rows_force < 0))
     return fail(h, FFDDP_E_INVALID, "ffddp_fleet_metrics_dev: bad stride or record count");
   HIPCHK(h, hipSetDevice(h->device));
   const dim3 grid((unsigned)((B + METRICS_BLOCK - 1) / METRICS_BLOCK)), block(METRICS_BLOCK);
-  if (tasks.rec)
+  if (force && tasks.rec)
+    hipLaunchKernelGGL((k_fleet_metrics<true, const double*, int>), grid, block, 0, (hipStream_t)stream, B, (long)ld, obs,
+                       (long)ld_obs, tasks, rows, dt, p_ref, ts, t_phase, fn_des, info, need, plant_fail, acc, force,
+                       rows_force);
+  else if (force)
+    hipLaunchKernelGGL((k_fleet_metrics<false, const double*, int>), grid, block, 0, (hipStream_t)stream, B, (long)ld, obs,
+                       (long)ld_obs, tasks, 0, dt, p_ref, ts, t_phase, fn_des, info, need, plant_fail, acc, force,
+                       rows_force);
+  else if (tasks.rec)
     hipLaunchKernelGGL(k_fleet_metrics<true>, grid, block, 0, (hipStream_t)stream, B, (long)ld, obs, (long)ld_obs, tasks,
                        rows, dt, p_ref, ts, t_phase, fn_des, info, need, plant_fail, acc);
   else

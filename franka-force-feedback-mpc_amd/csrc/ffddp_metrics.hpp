@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "ffddp_consts.hpp"
+#include "ffddp_force.hpp"
 #include "ffddp_task.hpp"
 
 namespace ffddp {
@@ -29,15 +30,27 @@ __device__ __forceinline__ double metrics_max(double m, double x) {
   return (m != m || x != x) ? __builtin_nan("") : fmax(m, x);
 }
 
+// the force reference of instance b at series time ts: the scalar, or its own record's
+__device__ __forceinline__ double metrics_force_ref(long, double, double fn_des) { return fn_des; }
+__device__ __forceinline__ double metrics_force_ref(long b, double ts, double fn_des, const double* __restrict__ frec,
+                                                    int frows) {
+  return b < frows ? fleet_force_at(frec + b * FFDDP_FLEET_FORCE_W, ts) : fn_des;
+}
+
 // TASK: instance b's reference is its own record's at (T.t - delay) + dt (rows
 // records; an instance beyond them has no reference: NaN); else the shared row
 // p_ref at ts.
-template <bool TASK>
+// k_fleet_metrics<TASK>: the force error is against the scalar fn_des;
+// k_fleet_metrics<TASK, const double*, int>: the trailing arguments are (force
+// records, their count) and instance b's reference is its own record's at ts
+// (ffddp_force.hpp), fn_des beyond the records.  The pack keeps the first
+// instantiation's arguments, and so its code, what they were.
+template <bool TASK, class... ForceArgs>
 __global__ __launch_bounds__(METRICS_BLOCK) void k_fleet_metrics(
     int B, long ld, const double* __restrict__ obs, long ld_obs, ffddp_fleet_tasks T, int rows, double dt,
     const double* __restrict__ p_ref, double ts1, const double* __restrict__ t_phase, double fn_des,
     const double* __restrict__ info, const uint8_t* __restrict__ need, const int32_t* __restrict__ fail,
-    double* __restrict__ acc) {
+    double* __restrict__ acc, ForceArgs... force_args) {
 #pragma clang fp contract(off)
   const long b = (long)blockIdx.x * METRICS_BLOCK + threadIdx.x;
   if (b >= B) return;
@@ -65,13 +78,14 @@ __global__ __launch_bounds__(METRICS_BLOCK) void k_fleet_metrics(
   const double fn = o[46] * (o[47] > 0.5 ? 1.0 : 0.0);
   const double contact = fn > 0.5 ? 1.0 : 0.0;
   const bool phase = ts >= t_phase[b];
+  const double fref = metrics_force_ref(b, ts, fn_des, force_args...);
   double* a = acc + b;
   const double et2 = et * et;
   a[FFDDP_FLEET_METRICS_N * ld] += 1.0;
   a[FFDDP_FLEET_METRICS_SUM_TAN2 * ld] += et2;
   a[FFDDP_FLEET_METRICS_SUM_3D2 * ld] += e3 * e3;
   a[FFDDP_FLEET_METRICS_SUM_ABS_TAN * ld] += fabs(et);
-  a[FFDDP_FLEET_METRICS_SUM_ABS_FN_ERR * ld] += fabs(fn - fn_des);
+  a[FFDDP_FLEET_METRICS_SUM_ABS_FN_ERR * ld] += fabs(fn - fref);
   a[FFDDP_FLEET_METRICS_MAX_FN * ld] = metrics_max(a[FFDDP_FLEET_METRICS_MAX_FN * ld], fn);
   a[FFDDP_FLEET_METRICS_SUM_CONTACT * ld] += contact;
   a[FFDDP_FLEET_METRICS_MAX_ERR_3D * ld] = metrics_max(a[FFDDP_FLEET_METRICS_MAX_ERR_3D * ld], e3);

@@ -259,7 +259,9 @@ template <int NC> FFD_HD void force_world(const double* lam, double* fw) {
 template <int NC>
 FFD_HD void node_primal(const DevConsts& C, int mode, bool surface, const double* x, const double* u,
                         const double* ref, const double* xreg, const double* tauref, Primal& P,
-                        Primal* gout = nullptr) {
+                        Primal* gout = nullptr, const double* fnr = nullptr) {
+  // fnr: this node's normal-force reference (the solve's force_ref entry) in
+  // place of C.fn_ref[NC - 1]; null: C's
   // gout: each block of fields is stored as soon as it is final, so the
   // registers holding it can be reused (a whole-struct copy at the end would
   // keep all ~225 words live to the last instruction).
@@ -564,7 +566,7 @@ FFD_HD void node_primal(const DevConsts& C, int mode, bool surface, const double
       double a = 0.0;
       #pragma unroll
       for (int r = 0; r < nc; ++r) {
-        const double rr = lam[r] - C.fn_ref[r];
+        const double rr = lam[r] - ((fnr && r == nc - 1) ? *fnr : C.fn_ref[r]);
         a += C.fn_w[r] * rr * rr;
         P.D[12 + r] += C.w_fn * C.fn_w[r];
         P.g[12 + r] += C.w_fn * C.fn_w[r] * rr;
@@ -953,9 +955,9 @@ FFD_HD void node_tangent_control(const DevConsts& C, bool surface, const Primal&
 template <int NC, bool FF>
 FFD_HD void node_calc(const DevConsts& C, bool terminal, bool surface, const double* y, const double* w,
                       const double* ref, const double* xreg, const double* tauref, const double* yref, Primal& P,
-                      double* ynext, double& cost) {
+                      double* ynext, double& cost, const double* fnr = nullptr) {
   if (!FF) {
-    node_primal<NC>(C, terminal ? MODE_TERMINAL_X : MODE_RUNNING, surface, y, w, ref, xreg, tauref, P);
+    node_primal<NC>(C, terminal ? MODE_TERMINAL_X : MODE_RUNNING, surface, y, w, ref, xreg, tauref, P, nullptr, fnr);
     for (int i = 0; i < 14; ++i) ynext[i] = P.xnext[i];
     cost = terminal ? P.cost : C.dt * P.cost;
     return;
@@ -963,7 +965,7 @@ FFD_HD void node_calc(const DevConsts& C, bool terminal, bool surface, const dou
   const double* tau = y + 14;
   double wz[7] = {0, 0, 0, 0, 0, 0, 0};
   const double* ww = terminal ? wz : w;
-  node_primal<NC>(C, terminal ? MODE_TERMINAL_U : MODE_RUNNING, surface, y, tau, ref, xreg, tauref, P);
+  node_primal<NC>(C, terminal ? MODE_TERMINAL_U : MODE_RUNNING, surface, y, tau, ref, xreg, tauref, P, nullptr, fnr);
   for (int i = 0; i < 14; ++i) ynext[i] = P.xnext[i];
   for (int i = 0; i < 7; ++i) ynext[14 + i] = C.alpha * tau[i] + C.beta * ww[i];
   double c = C.dt * P.cost;

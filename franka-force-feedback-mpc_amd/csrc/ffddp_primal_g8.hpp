@@ -22,10 +22,16 @@ namespace ffddp {
 
 // gp: this node's Primal in global memory; lk: its link record (LK_* layout).
 // Returns (group-uniform) the unscaled DAM cost and the contact force.
-template <int NC>
+// FR: the normal-force reference of this node is *fnp (the solve's per-instance,
+// per-node force_ref entry) instead of C.fn_ref[NC - 1]; the tangential ones
+// stay C's.  It is loaded where the cost needs it, not with the node's other
+// inputs: held across the calc it costs the force-feedback k_node, which is at
+// its register limit, 8 to 12 bytes of scratch per lane.
+template <int NC, bool FR = false>
 __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, bool surface, double q, double v, double u,
                                                  double xq, double xv, double tr, const double* ref,
-                                                 Primal* __restrict__ gp, double* __restrict__ lk, double (&lam)[3]) {
+                                                 Primal* __restrict__ gp, double* __restrict__ lk, double (&lam)[3],
+                                                 const double* __restrict__ fnp = nullptr) {
   const ffddp_robot& rb = C.rb;
   const int li = g8_lane();
   const bool J = li < NQ;
@@ -622,9 +628,11 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
     }
     if (C.has_fn) {
       double s = 0.0;
+      double fnr = 0.0;
+      if constexpr (FR) fnr = *fnp;
 #pragma unroll
       for (int r = 0; r < NC; ++r) {
-        const double e = lm[r] - C.fn_ref[r];
+        const double e = lm[r] - ((FR && r == NC - 1) ? fnr : C.fn_ref[r]);
         s += C.fn_w[r] * e * e;
         Dd[12 + r] += C.w_fn * C.fn_w[r];
         gd[12 + r] += C.w_fn * C.fn_w[r] * e;

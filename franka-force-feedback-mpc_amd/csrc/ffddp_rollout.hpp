@@ -239,10 +239,12 @@ template <bool ROW> __device__ __forceinline__ double ls_bwd(const double (&Lt)[
 // lambda' = S^-1 (gamma + Y' y1), S = Y'Y + eps (the KKT of
 // DifferentialActionModelContactFwdDynamics by its Schur complement; one
 // backward substitution instead of two full solves).
-template <int NC, bool ROW>
+// FR: the normal-force reference of this node is fnr (the solve's force_ref,
+// prefetched with ref) instead of C.fn_ref[NC - 1]; unused otherwise.
+template <int NC, bool ROW, bool FR = false>
 __device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, const LaneK& K, int mode, bool surface, double q,
                                              double v, double u, double xq, double xv, double tr, const double* ref,
-                                             double& qn, double& vn, double& cpart, double (&lam)[3]
+                                             double fnr, double& qn, double& vn, double& cpart, double (&lam)[3]
 #ifdef FFDDP_PHASE_PROF
                                              , unsigned long long (&pp_acc)[12], unsigned long long& pp_last
 #endif
@@ -622,7 +624,7 @@ __device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, co
     if (fl & RF_FN) {
 #pragma unroll
       for (int r = 0; r < NC; ++r) {
-        const double e = lm[r] - C.fn_ref[r];
+        const double e = lm[r] - ((FR && r == NC - 1) ? fnr : C.fn_ref[r]);
         cf = fma(C.w_fn, 0.5 * ((C.fn_w[r] * e) * e), cf);
       }
     }

@@ -62,6 +62,10 @@ SYMBOLS = (
     "ffddp_plant_set_instance_params",
     "ffddp_fleet_inject_obs_rows_dev",
     "ffddp_fleet_inject_cmd_rows_dev",
+    "ffddp_solve_batch_fref_dev",
+    "ffddp_calc_diff_fref",
+    "ffddp_fleet_force_refs_dev",
+    "ffddp_fleet_metrics_fref_dev",
 )
 PLANT_OBS = 69
 # FFDDP_PLANT_ROW_*: one instance's physics row (ffddp_plant_set_instance_params)
@@ -156,6 +160,8 @@ class FleetTasks(C.Structure):
 
     _fields_ = [("p_site_minus_frame", C.c_double * 3), ("t", C.c_double), ("rec", C.c_void_p)]
 
+
+FLEET_FORCE_W = 4  # FFDDP_FLEET_FORCE_W: doubles per force record, f0, f1, t_on, t_ramp (trajectory.force_records)
 
 FLEET_METRICS_W = 17  # FFDDP_FLEET_METRICS_W: accumulator fields per instance (FFDDP_FLEET_METRICS_*, in order)
 FLEET_METRICS_FIELDS = ("n", "n_phase", "sum_tan2", "sum_tan2_phase", "sum_3d2", "sum_abs_tan", "sum_abs_fn_err",
@@ -428,6 +434,10 @@ def load() -> C.CDLL:
     lib.ffddp_solve_batch_sel_dev.restype = C.c_int
     lib.ffddp_calc_diff.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, up, dp, dp] + [dp] * 10
     lib.ffddp_calc_diff.restype = C.c_int
+    lib.ffddp_solve_batch_fref_dev.argtypes = dev_args[:-1] + [vp, vp, vp]  # ..., stats, active, force_ref, stream
+    lib.ffddp_solve_batch_fref_dev.restype = C.c_int
+    lib.ffddp_calc_diff_fref.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, up, dp, dp, dp] + [dp] * 10
+    lib.ffddp_calc_diff_fref.restype = C.c_int
     lib.ffddp_frame_placement.argtypes = [C.POINTER(Robot), dp, dp, dp]
     lib.ffddp_frame_placement.restype = C.c_int
     lib.ffddp_gravity_torque.argtypes = [C.POINTER(Robot), C.c_int, dp, dp]
@@ -510,6 +520,13 @@ def load() -> C.CDLL:
     lib.ffddp_fleet_metrics_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, vp, C.c_int, FleetTasks, C.c_int, C.c_double,
                                             vp, C.c_double, vp, C.c_double, vp, vp, vp, vp] + [vp]
     lib.ffddp_fleet_metrics_dev.restype = C.c_int
+    # the force profiles: B, tasks, force, rows, fn_default, force_ref; the metrics with ..., acc, force, rows_force
+    lib.ffddp_fleet_force_refs_dev.argtypes = [C.c_void_p, C.c_int, FleetTasks, vp, C.c_int, C.c_double, vp] + [vp]
+    lib.ffddp_fleet_force_refs_dev.restype = C.c_int
+    lib.ffddp_fleet_metrics_fref_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, vp, C.c_int, FleetTasks, C.c_int,
+                                                 C.c_double, vp, C.c_double, vp, C.c_double, vp, vp, vp, vp, vp,
+                                                 C.c_int] + [vp]
+    lib.ffddp_fleet_metrics_fref_dev.restype = C.c_int
     _lib = lib
     return lib
 

@@ -56,8 +56,8 @@ from .controller import (_OCP_FIELDS, _quat_wxyz_to_R, classical_benchmark_confi
 from .plant import JOINT_DAMPING, BatchedPlant, PandaTablePlant, PlantPhysics, plant_rows
 from .runlog import summary_metrics
 from .solver import BatchedBoxFDDP
-from .trajectory import (TABLE_CENTER, TABLE_HALF_Z, TOOL_RADIUS, FleetTask, make_approach_then_circle,
-                         sample_records, task_records, with_contact_hold)
+from .trajectory import (TABLE_CENTER, TABLE_HALF_Z, TOOL_RADIUS, FleetTask, ForceProfile, make_approach_then_circle,
+                         sample_force, sample_records, task_records, with_contact_hold)
 from .uncertainty import BatchedUncertaintyInjector, config_for_scenario, delay_steps
 
 Traj = Callable[[float], Tuple[np.ndarray, np.ndarray, bool]]
@@ -605,7 +605,8 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
               task_spread: Optional[Tuple[float, float]] = None, stagger: int = 0,
               device_summary: bool = False, keep_logs: bool = True,
               plant_spread: Optional[Tuple[float, float]] = None,
-              uncertainty_spread: Optional[Tuple[float, int]] = None) -> dict:
+              uncertainty_spread: Optional[Tuple[float, int]] = None,
+              force_spread: Optional[Tuple[float, float]] = None, force_ramp: Optional[float] = None) -> dict:
     """Closed-loop sweep of len(scenarios) * seeds instances; this rank runs
     its contiguous shard.  Returns per-instance summary arrays (this shard).
     record: shard-local instance indices whose controller inputs (the plant
@@ -669,7 +670,19 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     the delays d_obs, d_cmd = g.integers(0, D + 1, 2) control ticks, g =
     default_rng([seed_b, 3]).  The q0 and task draws do not move.  The
     summary carries ``plant_rows`` (B, PLANT_ROW_W), ``inject_delay`` (B, 2)
-    and ``inject_sigma`` (B, 3) (-1 / NaN without an injector)."""
+    and ``inject_sigma`` (B, 3) (-1 / NaN without an injector).
+    force_spread, force_ramp (with device_loop only, NotImplementedError
+    otherwise: the host fleets track the configuration's fn_des): each
+    instance's own desired normal force (DeviceFleetLoop(force_profiles=...)).
+    force_spread = (f_lo, f_hi), 0 <= f_lo <= f_hi: instance b's setpoint f1 =
+    f_lo + (f_hi - f_lo) (1 + u) / 2, u uniform in [-1, 1] from
+    default_rng([seed_b, 4]) (the other draws do not move).  force_ramp = T > 0
+    (needs force_spread): the reference starts at f_lo and ramps to f1 over T
+    seconds from the end of the contact hold, in the instance's task time;
+    T = 0 or None: f1 from the start.  The summary's ``avg_abs_force_err`` is
+    then against each instance's own reference at every sample, from the logs
+    and from the device accumulators alike, and ``force_rec`` (B, 4) carries
+    the profiles (f0, f1, t_on, t_ramp)."""
     variant = str(variant).strip().lower()
     if variant not in ("classical", "ff"):
         raise ValueError(f"run_sweep: unknown variant {variant!r}")
@@ -700,6 +713,18 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
             raise ValueError("run_sweep: uncertainty_spread is (dn, D), dn in [0, 1) and D an integer 0..16, "
                              f"not {uncertainty_spread!r}")
         uncertainty_spread = (float(dn), int(D))
+    if force_ramp is not None and force_spread is None:
+        raise ValueError("run_sweep: force_ramp needs force_spread")
+    if force_spread is not None:
+        force_spread = tuple(float(x) for x in force_spread)
+        if len(force_spread) != 2 or not all(np.isfinite(force_spread)) or not 0.0 <= force_spread[0] <= force_spread[1]:
+            raise ValueError(f"run_sweep: force_spread is (f_lo, f_hi), 0 <= f_lo <= f_hi, not {force_spread!r}")
+        force_ramp = 0.0 if force_ramp is None else float(force_ramp)
+        if not (np.isfinite(force_ramp) and force_ramp >= 0.0):
+            raise ValueError(f"run_sweep: force_ramp must be >= 0, not {force_ramp!r}")
+        if not device_loop:
+            raise NotImplementedError("run_sweep: force_spread and force_ramp need device_loop=True "
+                                      "(the host fleets track the configuration's fn_des)")
     device_refs = bool(device_refs) or task_spread is not None or stagger > 0
     if device_refs and not device_loop:
         raise NotImplementedError("run_sweep: device_refs, task_spread and stagger need device_loop=True "
@@ -760,10 +785,20 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
                                        z_contact=z_contact, t_approach=0.55, t_pre=0.25, ee_start=obs0.ee_pos.copy(),
                                        z_pre=z_contact + 0.05, t_contact_phase=t_cp, t_hold=0.2,
                                        delay=((lo + b) % stagger) * (0.001 * 5) if stagger else 0.0))  # BatchedPlant.dt
+        profiles = None
+        if force_spread is not None:
+            f_lo, f_hi = force_spread
+            profiles = []
+            for b in range(B):
+                u = np.random.default_rng([int(seed[b]), 4]).uniform(-1.0, 1.0)
+                f1 = f_lo + (f_hi - f_lo) * (0.5 * (1.0 + u))
+                profiles.append(ForceProfile(f_lo, f1, t_on=t_cp + 0.2, t_ramp=force_ramp) if force_ramp > 0.0
+                                else ForceProfile(f1, f1))
         out = _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, (R_site_from_pin_ee, p_off), total_time,
                                 neg_step_rule, device, t_cp, verbose, ucfgs, device_noise, solve_period,
                                 command_filter, tasks, device_summary, keep_logs, physics,
-                                allow_plant_fail=plant_spread is not None or uncertainty_spread is not None)
+                                allow_plant_fail=plant_spread is not None or uncertainty_spread is not None,
+                                force_profiles=profiles)
         out.update(names=names, seed=seed, shard=(lo, hi), n_all=n_all)
         return out
     plant = BatchedPlant(B, timestep=0.001, n_substeps=5, device=device, physics=physics)
@@ -904,14 +939,17 @@ DEVICE_MEMORY: dict = {}  # the last device-loop sweep's memory figures (tools/s
 
 def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, total_time, neg_step_rule, device, t_cp,
                       verbose, ucfgs=None, noise=None, solve_period=1, command_filter=False, tasks=None,
-                      device_summary=False, keep_logs=True, plant_physics=None, allow_plant_fail=False) -> dict:
+                      device_summary=False, keep_logs=True, plant_physics=None, allow_plant_fail=False,
+                      force_profiles=None) -> dict:
     """run_sweep's loop on the device (fleet_loop.DeviceFleetLoop) and the
     host path's summary from the downloaded logs.  tasks: per-instance
     FleetTasks in place of traj; the summary's reference position and its
     contact phase are then each instance's own, in its task time.
     device_summary: the summary from the loop's device accumulators instead;
     keep_logs=False: the loop keeps no per-tick logs.  plant_physics: one
-    PlantPhysics per instance (None: the scene's constants)."""
+    PlantPhysics per instance (None: the scene's constants).  force_profiles:
+    one ForceProfile (or None) per instance; the force error is then against
+    each instance's own reference at the sample's series time."""
     import torch
 
     from .fleet_loop import DeviceFleetLoop
@@ -929,7 +967,7 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
                            noise=noise or "numpy", solve_period=int(solve_period), tasks=tasks,
                            metrics=bool(device_summary), logs=bool(keep_logs),
                            t_contact_phase=float(t_cp) if device_summary and tasks is None else None,
-                           plant_physics=plant_physics)
+                           plant_physics=plant_physics, force_profiles=force_profiles)
     wall0 = time.perf_counter()
     loop.run(steps)
     torch.cuda.synchronize(loop.dev)
@@ -955,6 +993,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
         out = dict(per_instance={k: np.asarray(s[k], float) for k in SUMMARY_KEYS}, ticks=steps, wall_s=wall,
                    controller_s=None, instances=B, variant=variant, solved_ticks=np.asarray(s["solved_ticks"], float))
         out.update(_mismatch_outputs(loop, r, ucfgs, B, allow_plant_fail))
+        if "force_rec" in r:
+            out["force_rec"] = r["force_rec"]
         if tasks is not None and keep_logs:
             out.update(solved=r["solved"], surface=r["surface"] != 0)
         return out
@@ -977,9 +1017,12 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
         print(f"device loop: B={B} ticks={steps} | final median |p-p_ref|={np.median(series['err_3d'][-1]):.4f} m | "
               f"median Fn={np.median(fnm[-1]):.2f} N | ok={np.mean(r['ok']):.3f}", flush=True)
     per_inst = {k: np.zeros(B) for k in SUMMARY_KEYS}
+    # the force reference of every sample: the scalar, or each instance's profile at the series time
+    f_ref = sample_force(r["force_rec"], t_series.T) if "force_rec" in r else None  # (B, steps)
     for b in range(B):
         s = summary_metrics(series["t"][:, b], series["err_tan"][:, b], series["err_3d"][:, b],
-                            series["fn_meas"][:, b], series["contact"][:, b], float(cfg.fn_des), float(t_cps[b]))
+                            series["fn_meas"][:, b], series["contact"][:, b],
+                            float(cfg.fn_des) if f_ref is None else f_ref[b], float(t_cps[b]))
         for k_ in SUMMARY_KEYS[:-3]:
             per_inst[k_][b] = s[k_]
     per_inst["unstable_ticks"] = (r["unstable"] != 0).sum(0).astype(float)
@@ -988,6 +1031,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     out = dict(per_instance=per_inst, ticks=steps, wall_s=wall, controller_s=None, instances=B, variant=variant,
                solved_ticks=r["solved"].sum(0).astype(float))
     out.update(_mismatch_outputs(loop, r, ucfgs, B, allow_plant_fail))
+    if "force_rec" in r:
+        out["force_rec"] = r["force_rec"]
     if tasks is not None:
         out.update(solved=r["solved"], surface=r["surface"] != 0)  # (ticks, B): the per-tick solve share
     return out

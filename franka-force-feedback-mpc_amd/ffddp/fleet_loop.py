@@ -67,6 +67,17 @@ delays and sigmas (ffddp_fleet_inject_*_rows_dev), the rings as deep as the
 largest delay.  Neither adds a launch; configs that differ by seed only, and
 a loop without ``plant_physics``, enqueue exactly the calls they did before.
 
+With ``force_profiles`` (one trajectory.ForceProfile or None per instance)
+the desired normal force is each instance's own function of its task time: one
+more launch per tick (ffddp_fleet_force_refs_dev, between pre and the solve)
+samples the N+1 knots of every instance's profile at the task sampler's knot
+times into ``force_ref`` (B, N+1), and the solve takes it
+(ffddp_solve_batch_fref_dev) in place of the configuration's ``fn_des``; the
+metrics score the force error against the same profile at the series time.
+A None entry is the constant ``fn_des``.  The sampler is a function of the
+tick's time, so ``state`` / ``load_state`` carry nothing for it.  Without the
+argument (or with every entry None) the loop enqueues exactly the calls it did.
+
 Not on the device, and so not supported here: ``run_sweep``'s ``record`` and
 any per-tick host callback; ``tick()`` lets a caller look between ticks at the price of its own
 synchronisation.
@@ -81,7 +92,7 @@ from . import _abi
 from . import robot as R
 from .controller import ff_filter_alpha
 from .fleet import Traj, fleet_ocp_config, node_ref, site_calibration
-from .trajectory import FleetTask, task_records
+from .trajectory import FleetTask, ForceProfile, force_records, task_records
 from .uncertainty import UncertaintyProfileConfig, delay_steps, draw_gain_bias, predraw
 
 LPF_ALPHA = 0.2  # PandaTablePlant's tau_meas_lpf_alpha: the ff sweep's torque measurement filter
@@ -190,6 +201,11 @@ class DeviceFleetLoop:
     logs: False (needs metrics, ValueError otherwise) keeps one row of each
     per-tick log, reused every tick; ``steps`` then bounds the run only where
     a table is sized by it (traj_fn, or the injector's numpy noise).
+    force_profiles: None, or one Optional[trajectory.ForceProfile] per instance
+    (None: the configuration's fn_des, as is a list of Nones): the desired
+    normal force over each instance's task time (the tick's time minus the
+    task's delay), sampled per tick and knot on the device (``force_ref``
+    (B, N+1), the solve's argument; ``force_rec`` the records).
 
     ``S``: the controller state, ``T``: the solve's arrays, ``P``: the plant's
     (q, v, obs, tau_app, tau_filt, plane), ``J``: the injector's (row, a, b,
@@ -204,7 +220,8 @@ class DeviceFleetLoop:
                  uncertainty: Optional[Sequence[Optional[UncertaintyProfileConfig]]] = None, noise: str = "numpy",
                  max_table_bytes: int = 1 << 30, solve_period: Optional[int] = None,
                  tasks: Optional[Sequence[FleetTask]] = None, metrics: bool = False, logs: bool = True,
-                 t_contact_phase=None, plant_physics=None):
+                 t_contact_phase=None, plant_physics=None,
+                 force_profiles: Optional[Sequence[Optional[ForceProfile]]] = None):
         variant = str(variant).strip().lower()
         if variant not in ("classical", "ff"):
             raise ValueError(f"DeviceFleetLoop: unknown variant {variant!r}")
@@ -230,6 +247,14 @@ class DeviceFleetLoop:
             if not all(c is None or isinstance(c, UncertaintyProfileConfig) for c in ucfgs):
                 raise ValueError("DeviceFleetLoop: uncertainty entries are UncertaintyProfileConfig or None")
         cfg = config
+        if force_profiles is not None:
+            force_profiles = list(force_profiles)
+            if len(force_profiles) != int(B) or not all(f is None or isinstance(f, ForceProfile) for f in force_profiles):
+                raise ValueError("DeviceFleetLoop: force_profiles takes one entry (a ForceProfile or None) per instance")
+            if all(f is None for f in force_profiles):
+                force_profiles = None  # the configuration's fn_des for all: the plain loop
+            elif not float(cfg.w_fn) > 0.0:
+                raise ValueError("DeviceFleetLoop: force_profiles need the fn_track cost (w_fn > 0)")
         self.period = resolve_solve_period(cfg, solve_period)
         import torch
 
@@ -328,6 +353,14 @@ class DeviceFleetLoop:
         else:
             self.rec = up(self.task_rec)
             self.ktasks = self.solver.fleet_tasks(self.rec, p_off)
+        # per-instance force setpoints (ffddp_fleet_force_refs_dev): the records and the solve's force_ref
+        self.force_rec = self.frec = self.force_ref = self.ftasks = None
+        if force_profiles is not None:
+            fn = float(cfg.fn_des)
+            self.force_rec = force_records([ForceProfile(fn, fn) if f is None else f for f in force_profiles])
+            self.frec = up(self.force_rec)
+            self.force_ref = z(B, N + 1)
+            self.ftasks = self.ktasks if self.ktasks is not None else _abi.FleetTasks()
         self.log_info = torch.full((rows, B, _abi.FLEET_INFO_W), float("nan"), **f64)
         self.log_obs = torch.full((rows + 1 if logs else 1, B, _abi.FLEET_LOG_W), float("nan"), **f64)
         self.log_fail = z(rows + 1, B, dtype=torch.int32)  # without logs: the start's row and the ticks'
@@ -439,6 +472,8 @@ class DeviceFleetLoop:
                 kw.update(tasks=self.mtasks, dt=self.dt)
             else:
                 kw.update(p_ref=self.p_tab[j], ts=float(self.times[j]) + self.dt)
+            if self.frec is not None:
+                kw.update(force=self.frec)
             self.solver.fleet_metrics_dev(self.acc, P["obs"], self.t_phase, float(self.cfg.fn_des), **kw)
             self.m_k = self.k
 
@@ -457,23 +492,36 @@ class DeviceFleetLoop:
         if self.inject is not None:
             self.solver.fleet_inject_obs_dev(self.J, self.inject, k, z=None if self.z_table is None else self.z_table[k],
                                              stream=self._stream, rows=self.inject_rows)
+        fkw = {}
+        if self.frec is not None:
+            self.ftasks.t = self._tick_time(k)
+            fkw = dict(force_ref=self.force_ref)
         if self.sched is None:
             self.solver.fleet_pre_dev(T, self.params, hint, stream=self._stream, tasks=self.ktasks)
-            self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream)
+            if fkw:
+                self._force_refs()
+            self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream, **fkw)
             self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream)
         else:
             T["need"] = self.log_need[r]
             self.solver.fleet_pre_dev(T, self.params, hint, stream=self._stream, sched=self.sched, tasks=self.ktasks)
+            if fkw:
+                self._force_refs()
             self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream,
-                                  active=T["need"])
+                                  active=T["need"], **fkw)
             self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream, sched=self.sched)
         if self.inject is not None:
             self.solver.fleet_inject_cmd_dev(self.J, self.inject, k, stream=self._stream, rows=self.inject_rows)
         self._stepped = False
         self.k = k + 1
 
+    def _force_refs(self):
+        """This tick's force_ref from the records, at ``ftasks.t`` (minus each task's delay)."""
+        self.solver.fleet_force_refs_dev(self.frec, self.force_ref, tasks=self.ftasks, fn_default=float(self.cfg.fn_des),
+                                         stream=self._stream)
+
     def run(self, steps: int):
-        """Enqueue `steps` ticks: plant step, (inject_obs,) pre, solve, post(, inject_cmd);
+        """Enqueue `steps` ticks: plant step, (inject_obs,) pre, (force_refs,) solve, post(, inject_cmd);
         scheduled: pre_sched, the selected-instance solve, post_sched.
         Returns without waiting for the device."""
         for _ in range(int(steps)):
@@ -542,7 +590,8 @@ class DeviceFleetLoop:
         (B, 2) their (observation, command) delays in ticks and
         ``inject_sigma`` (B, 3) their sigmas, -1 / NaN where there is none;
         and ``plant_rows`` (B, PLANT_ROW_W): the physics each instance
-        integrates with (all three are attributes of the loop as well).  With
+        integrates with (all three are attributes of the loop as well); with
+        ``force_profiles`` also ``force_rec`` (B, FLEET_FORCE_W).  With
         ``metrics``
         also ``metrics`` (FLEET_METRICS_W, B): the accumulators over the k
         ticks (the closing plant step's record is folded in here, once), and
@@ -574,6 +623,8 @@ class DeviceFleetLoop:
                 out["plant_rows"] = self.plant_rows.copy()
             if self.inject_rows is not None:
                 out.update(inject_delay=self.inject_delay.copy(), inject_sigma=self.inject_sigma.copy())
+            if self.force_rec is not None:
+                out["force_rec"] = self.force_rec.copy()
             return out
         info = self.log_info[:k].cpu().numpy()
         out = dict(info=info, obs=self.log_obs[: k + 1].cpu().numpy(), t=self.times[:k].copy(),
@@ -587,6 +638,8 @@ class DeviceFleetLoop:
                        inject_delay=self.inject_delay.copy(), inject_sigma=self.inject_sigma.copy())
         if self.task_delay is not None:
             out["t_task"] = self.times[:k, None] - self.task_delay[None, :]
+        if self.force_rec is not None:
+            out["force_rec"] = self.force_rec.copy()
         if self.metrics:
             out.update(m)
         return out

@@ -161,12 +161,21 @@ def _rms(a: np.ndarray) -> float:
     return float(np.sqrt(np.mean(a ** 2))) if a.size else float("nan")
 
 
-def summary_metrics(t, err_tan, err_3d, fn_meas, contact, fn_des: float, t_contact_phase: float) -> Dict[str, float]:
+def _force_ref(fn_des):
+    """fn_des as the force-error terms take it: the scalar as a float (the
+    arithmetic it always had), an array (one reference per sample or per
+    instance) as float64."""
+    return float(fn_des) if np.ndim(fn_des) == 0 else np.asarray(fn_des, dtype=float)
+
+
+def summary_metrics(t, err_tan, err_3d, fn_meas, contact, fn_des, t_contact_phase: float) -> Dict[str, float]:
     """End-of-run statistics of the closed loop (run_classical.py:513-535).
 
     Inputs are the per-tick series the runner collects (``summary`` dict,
     run_classical.py:452-457); ``contact`` is 1.0 where fn_meas > 0.5 N.
-    The contact phase is t >= t_contact_phase.
+    The contact phase is t >= t_contact_phase.  fn_des: the desired normal
+    force, a scalar or one value per sample (a setpoint that varies over the
+    run, trajectory.sample_force).
     """
     t = np.asarray(t, dtype=float)
     err_tan = np.asarray(err_tan, dtype=float)
@@ -178,7 +187,7 @@ def summary_metrics(t, err_tan, err_3d, fn_meas, contact, fn_des: float, t_conta
     c_phase, fn_phase, et_phase = contact[phase], fn_meas[phase], err_tan[phase]
     return {
         "avg_abs_position_err": float(np.mean(np.abs(err_tan))) if err_tan.size else nan,
-        "avg_abs_force_err": float(np.mean(np.abs(fn_meas - float(fn_des)))) if fn_meas.size else nan,
+        "avg_abs_force_err": float(np.mean(np.abs(fn_meas - _force_ref(fn_des)))) if fn_meas.size else nan,
         "rms_tangential_error": _rms(err_tan),
         "rms_tangential_error_contact_phase": _rms(et_phase),
         "rms_3d_error": _rms(err_3d),
@@ -198,7 +207,7 @@ def metrics_accumulators(B: int, ld: Optional[int] = None) -> np.ndarray:
     return acc
 
 
-def accumulate_metrics(acc: np.ndarray, obs, p_ref, ts, t_phase, fn_des: float, info=None, need=None,
+def accumulate_metrics(acc: np.ndarray, obs, p_ref, ts, t_phase, fn_des, info=None, need=None,
                        plant_fail=None) -> np.ndarray:
     """One ffddp_fleet_metrics_dev call in numpy, term for term in the kernel's
     (and so ``summary_metrics``' callers') order: fold one plant record per
@@ -207,7 +216,8 @@ def accumulate_metrics(acc: np.ndarray, obs, p_ref, ts, t_phase, fn_des: float, 
     obs (B, >= 48): the records after a tick's command ([28..30] site position,
     [46] normal force, [47] contact flag); p_ref (3,) or (B, 3): the reference
     position at the series time ts (scalar or (B,)); t_phase (B,): the start of
-    each instance's contact phase; info (B, FLEET_INFO_W) or None (the four
+    each instance's contact phase; fn_des: the desired normal force, a scalar or
+    (B,), each instance's own at ts; info (B, FLEET_INFO_W) or None (the four
     solver counters are left); need (B,) or None (every instance solved);
     plant_fail (B,) or None.  Called once per tick the sums are sequential in
     tick order, as the kernel's are."""
@@ -228,7 +238,7 @@ def accumulate_metrics(acc: np.ndarray, obs, p_ref, ts, t_phase, fn_des: float, 
         a[_F["sum_tan2"]] += et2
         a[_F["sum_3d2"]] += e3 * e3
         a[_F["sum_abs_tan"]] += np.abs(et)
-        a[_F["sum_abs_fn_err"]] += np.abs(fn - float(fn_des))
+        a[_F["sum_abs_fn_err"]] += np.abs(fn - _force_ref(fn_des))
         a[_F["max_fn"]] = np.maximum(a[_F["max_fn"]], fn)  # propagates NaN, as np.max
         a[_F["sum_contact"]] += contact
         a[_F["max_err_3d"]] = np.maximum(a[_F["max_err_3d"]], e3)

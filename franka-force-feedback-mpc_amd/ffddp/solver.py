@@ -284,13 +284,17 @@ class BatchedBoxFDDP:
         return plan
 
     # -- solve (device-resident torch tensors; bench path) ---------------------------
-    def solve_dev(self, t, maxiter: int = 10, is_feasible: bool = False, stream=None, active=None):
+    def solve_dev(self, t, maxiter: int = 10, is_feasible: bool = False, stream=None, active=None, force_ref=None):
         """t: dict of contiguous torch.cuda tensors with keys x0, node_ref, inst_ref,
         surface (uint8), xs_init, us_init and outputs xs, us, K, cost, iters (int32),
         ok (uint8), fn_pred, stats (int32).  Asynchronous on `stream` (hipStream_t int).
         active: optional (B,) uint8 device tensor, the instances that solve
         (ffddp_solve_batch_sel_dev); the others' input rows are not read and
-        their output rows not written."""
+        their output rows not written.
+        force_ref: optional (B, N+1) float64 device tensor, the desired normal
+        contact force of every instance and node in place of the
+        configuration's fn_des (ffddp_solve_batch_fref_dev); goes with or
+        without `active`."""
         B = int(t["x0"].shape[0])
         p = lambda k: C.c_void_p(int(t[k].data_ptr()))
         if active is not None:
@@ -299,6 +303,21 @@ class BatchedBoxFDDP:
             if (active.dtype != torch.uint8 or not active.is_cuda or not active.is_contiguous()
                     or tuple(active.shape) != (B,)):
                 raise ValueError("active must be a contiguous (B,) uint8 device tensor")
+        if force_ref is not None:
+            import torch
+
+            if (not isinstance(force_ref, torch.Tensor) or force_ref.dtype != torch.float64 or not force_ref.is_cuda
+                    or not force_ref.is_contiguous() or tuple(force_ref.shape) != (B, self.N + 1)):
+                raise ValueError("force_ref must be a contiguous (B, N+1) float64 device tensor")
+            rc = self._lib.ffddp_solve_batch_fref_dev(
+                self._h, B, p("x0"), p("node_ref"), p("inst_ref"), p("surface"), p("xs_init"), p("us_init"),
+                int(maxiter), int(bool(is_feasible)), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
+                p("fn_pred"), p("stats"), C.c_void_p(int(active.data_ptr()) if active is not None else 0),
+                C.c_void_p(int(force_ref.data_ptr())), C.c_void_p(stream if stream else 0),
+            )
+            self._check(rc, "ffddp_solve_batch_fref_dev")
+            return
+        if active is not None:
             rc = self._lib.ffddp_solve_batch_sel_dev(
                 self._h, B, p("x0"), p("node_ref"), p("inst_ref"), p("surface"), p("xs_init"), p("us_init"),
                 int(maxiter), int(bool(is_feasible)), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
@@ -383,9 +402,33 @@ class BatchedBoxFDDP:
         )
         self._check(rc, "ffddp_fleet_task_refs_dev")
 
+    def fleet_force_refs_dev(self, force, force_ref, t: float = 0.0, tasks: _abi.FleetTasks = None, rows: int = None,
+                             fn_default: float = 0.0, stream=None):
+        """The device force-profile sampler (ffddp_fleet_force_refs_dev): force
+        (rows, _abi.FLEET_FORCE_W) float64 on the device (trajectory.force_records,
+        uploaded) -> force_ref (B, N+1), solve_dev's argument: knot k of instance
+        b at (t - its task delay) + k dt_ocp.  tasks (fleet_tasks): its t and the
+        records' delays are used; None: tick time `t`, no delay.  Instances
+        beyond `rows` (by default the records given) take fn_default.
+        Asynchronous on `stream`."""
+        B = int(force_ref.shape[0])
+        assert force.is_cuda and force.is_contiguous() and force.dim() == 2 and force.shape[1] == _abi.FLEET_FORCE_W
+        assert tuple(force_ref.shape) == (B, self.N + 1) and force_ref.is_contiguous()
+        assert str(force.dtype) == str(force_ref.dtype) == "torch.float64"
+        rows = int(force.shape[0]) if rows is None else int(rows)
+        assert rows <= int(force.shape[0])
+        if tasks is None:
+            tasks = _abi.FleetTasks()
+            tasks.t = float(t)
+        rc = self._lib.ffddp_fleet_force_refs_dev(
+            self._h, B, tasks, C.c_void_p(int(force.data_ptr())), rows, float(fn_default),
+            C.c_void_p(int(force_ref.data_ptr())), C.c_void_p(stream if stream else 0),
+        )
+        self._check(rc, "ffddp_fleet_force_refs_dev")
+
     def fleet_metrics_dev(self, acc, obs, t_phase, fn_des: float, tasks: _abi.FleetTasks = None, dt: float = 0.0,
                           rows: int = None, p_ref=None, ts: float = 0.0, info=None, need=None, plant_fail=None,
-                          stream=None):
+                          stream=None, force=None, rows_force: int = None):
         """Fold one plant record per instance into the task-metric accumulators
         (ffddp_fleet_metrics_dev; runlog.accumulate_metrics is the same step in
         numpy).  acc (_abi.FLEET_METRICS_W, ld >= B) float64, field-major; obs
@@ -394,7 +437,10 @@ class BatchedBoxFDDP:
         (fleet_tasks; instance b's own record at (tasks.t - its delay) + dt,
         `rows` records, by default B) or p_ref (3,) float64 on the device with
         the series time ts.  info (B, FLEET_INFO_W), need (B,) uint8 and
-        plant_fail (B,) int32 are optional.  Asynchronous on `stream`."""
+        plant_fail (B,) int32 are optional.  force (rows_force, _abi.FLEET_FORCE_W)
+        float64 on the device: the force error is against each instance's own
+        record at the series time (ffddp_fleet_metrics_fref_dev), fn_des beyond
+        them.  Asynchronous on `stream`."""
         B = int(obs.shape[0])
         assert acc.dim() == 2 and acc.shape[0] == _abi.FLEET_METRICS_W and acc.is_contiguous() and acc.shape[1] >= B
         assert obs.stride(1) == 1 and obs.shape[1] >= 48 and tuple(t_phase.shape) == (B,) and t_phase.is_contiguous()
@@ -404,6 +450,19 @@ class BatchedBoxFDDP:
         assert plant_fail is None or (tuple(plant_fail.shape) == (B,) and plant_fail.is_contiguous())
         assert p_ref is None or (p_ref.numel() == 3 and p_ref.is_contiguous())
         p = lambda a: C.c_void_p(int(a.data_ptr()) if a is not None else 0)  # noqa: E731
+        if force is not None:
+            assert force.is_cuda and force.is_contiguous() and force.dim() == 2 and force.shape[1] == _abi.FLEET_FORCE_W
+            assert str(force.dtype) == "torch.float64"
+            rf = int(force.shape[0]) if rows_force is None else int(rows_force)
+            assert rf <= int(force.shape[0])
+            rc = self._lib.ffddp_fleet_metrics_fref_dev(
+                self._h, B, int(acc.shape[1]), p(obs), int(obs.stride(0)),
+                tasks if tasks is not None else _abi.FleetTasks(), B if rows is None else int(rows), float(dt), p(p_ref),
+                float(ts), p(t_phase), float(fn_des), p(info), p(need), p(plant_fail), p(acc), p(force), rf,
+                C.c_void_p(stream if stream else 0),
+            )
+            self._check(rc, "ffddp_fleet_metrics_fref_dev")
+            return
         rc = self._lib.ffddp_fleet_metrics_dev(
             self._h, B, int(acc.shape[1]), p(obs), int(obs.stride(0)), tasks if tasks is not None else _abi.FleetTasks(),
             B if rows is None else int(rows), float(dt), p(p_ref), float(ts), p(t_phase), float(fn_des), p(info),
@@ -619,7 +678,9 @@ class BatchedBoxFDDP:
         return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(_abi.KERNEL_CLASSES)}
 
     # -- problem.calcDiff(xs, us) -------------------------------------------------------
-    def calc_diff(self, batch, xs, us):
+    def calc_diff(self, batch, xs, us, force_ref=None):
+        """force_ref: optional (B, N+1) host array, the desired normal contact
+        force per instance and node (ffddp_calc_diff_fref)."""
         B = int(batch.x0.shape[0])
         N, nx = self.N, self.nx
         f = lambda a, shape: np.ascontiguousarray(np.asarray(a, np.float64).reshape(shape))
@@ -630,6 +691,20 @@ class BatchedBoxFDDP:
             lam=np.zeros((B, N + 1, 3)),
         )
         d = _abi.dptr
+        if force_ref is not None:
+            fr = np.asarray(force_ref, np.float64)
+            if fr.shape != (B, N + 1):
+                raise ValueError("force_ref must have shape (B, N+1)")
+            fr = np.ascontiguousarray(fr)
+            rc = self._lib.ffddp_calc_diff_fref(
+                self._h, B, d(f(batch.x0, (B, nx))), d(f(batch.node_ref, (B, N + 1, 6))),
+                d(f(batch.inst_ref, (B, 21))), _abi.uptr(np.ascontiguousarray(np.asarray(batch.surface, np.uint8))),
+                d(f(xs, (B, N + 1, nx))), d(f(us, (B, N, 7))), d(fr), d(out["Fx"]), d(out["Fu"]), d(out["Lx"]),
+                d(out["Lu"]), d(out["Lxx"]), d(out["Lxu"]), d(out["Luu"]), d(out["cost"]), d(out["xnext"]),
+                d(out["lam"]),
+            )
+            self._check(rc, "ffddp_calc_diff_fref")
+            return out
         rc = self._lib.ffddp_calc_diff(
             self._h, B, d(f(batch.x0, (B, nx))), d(f(batch.node_ref, (B, N + 1, 6))), d(f(batch.inst_ref, (B, 21))),
             _abi.uptr(np.ascontiguousarray(np.asarray(batch.surface, np.uint8))), d(f(xs, (B, N + 1, nx))),

@@ -13,7 +13,7 @@ from typing import Callable, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._abi import FLEET_TASK_W
+from ._abi import FLEET_FORCE_W, FLEET_TASK_W
 
 Traj = Callable[[float], Tuple[np.ndarray, np.ndarray, bool]]
 
@@ -255,6 +255,59 @@ def sample_records(rec: np.ndarray, t) -> Tuple[np.ndarray, np.ndarray, np.ndarr
     P[h] = rec[h, _R_P_HOLD:_R_P_HOLD + 3]
     V[h] = 0.0
     return P, V, m_cir.copy()
+
+
+@dataclasses.dataclass(frozen=True)
+class ForceProfile:
+    """One instance's desired normal contact force over its task time (a device
+    fleet's ``force_profiles``): f0 before t_on, then linearly to f1 over
+    t_ramp seconds; t_ramp = 0 steps at t_on.  ForceProfile(f, f) is the
+    constant setpoint f."""
+
+    f0: float
+    f1: float
+    t_on: float = 0.0
+    t_ramp: float = 0.0
+
+    def __post_init__(self):
+        vals = (float(self.f0), float(self.f1), float(self.t_on), float(self.t_ramp))
+        if not all(np.isfinite(v) for v in vals):
+            raise ValueError(f"ForceProfile: every field must be finite, not {vals!r}")
+        if vals[0] < 0.0 or vals[1] < 0.0:
+            raise ValueError(f"ForceProfile: forces must be >= 0, not f0={self.f0!r}, f1={self.f1!r}")
+        if vals[3] < 0.0:
+            raise ValueError(f"ForceProfile: t_ramp must be >= 0, not {self.t_ramp!r}")
+
+
+# a force record's layout: include/ffddp.h FFDDP_FLEET_FORCE_*
+_F_F0, _F_F1, _F_T_ON, _F_T_RAMP = 0, 1, 2, 3
+
+
+def force_records(profiles: Sequence[ForceProfile]) -> np.ndarray:
+    """(B, FLEET_FORCE_W) float64: f0, f1, t_on, t_ramp of each profile."""
+    rec = np.zeros((len(profiles), FLEET_FORCE_W))
+    for b, k in enumerate(profiles):
+        rec[b] = float(k.f0), float(k.f1), float(k.t_on), float(k.t_ramp)
+    return rec
+
+
+def sample_force(rec: np.ndarray, t) -> np.ndarray:
+    """The device force sampler (csrc/ffddp_force.hpp) in numpy: row b of the
+    records at task time t[b] (scalar, (B,) or (B, K); the caller subtracts
+    the delay, as on the device) -> the desired normal force, shaped as t
+    broadcast against the rows: f0 + (f1 - f0) s with
+    s = min(max((t - t_on) / t_ramp, 0), 1), or (t >= t_on) where t_ramp == 0.
+    min / max are fmin / fmax, as on the device."""
+    rec = np.asarray(rec, dtype=float).reshape(-1, FLEET_FORCE_W)
+    t = np.asarray(t, dtype=float)
+    col = (lambda i: rec[:, i]) if t.ndim < 2 else (lambda i: rec[:, i][:, None])
+    f0, f1, t_on, t_ramp = (col(i) for i in (_F_F0, _F_F1, _F_T_ON, _F_T_RAMP))
+    t = np.broadcast_to(t, np.broadcast_shapes(t.shape, f0.shape))
+    ramp = t_ramp > 0.0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        s_ramp = np.fmin(np.fmax((t - t_on) / np.where(ramp, t_ramp, 1.0), 0.0), 1.0)
+    s = np.where(ramp, s_ramp, (t >= t_on).astype(float))
+    return f0 + (f1 - f0) * s
 
 
 # Benchmark scene constants (assets/scenes/panda_table_scene.xml:17-29,

@@ -83,6 +83,9 @@ typedef struct ffddp_ocp_config {
   double w_q_soft_limits, q_soft_limit_margin;
   double q_lower[7], q_upper[7];
   double w_tangent_pos, w_tangent_vel, w_plane_z, w_vz;
+  /* fn_des: the desired normal contact force of the fn_track cost (weight w_fn),
+   * one scalar for every instance and node; ffddp_solve_batch_fref_dev replaces
+   * it per instance and node with its force_ref array */
   double w_unilateral, friction_margin, w_fn, fn_des;
   double w_wdamp;
   double w_wdamp_weights[3];
@@ -196,6 +199,27 @@ int ffddp_solve_batch_sel_dev(ffddp_handle* h, int B, const double* x0, const do
                               double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
                               const uint8_t* active, void* stream);
 
+/* ffddp_solve_batch_sel_dev with a desired normal contact force per instance
+ * and node: force_ref is [B][N+1] device doubles, entry [b][t] replaces the
+ * configuration's scalar fn_des in the fn_track cost of instance b at node t
+ * (the component r = 0 for normal_1d, r = 2 for point3d; the tangential
+ * references stay 0), in the node stage and in the line-search rollout alike.
+ * The classical terminal node, whose contact force is 0, keeps its constant
+ * term with force_ref[b][N].  A free-space instance (surface[b] == 0) has no
+ * such cost: its results do not depend on its row.  Rows of unselected
+ * instances are not read; `active` may be NULL.  The arithmetic is the scalar
+ * path's in order and grouping, so an array filled with fn_des gives the bits
+ * of the call without one.  force_ref == NULL is ffddp_solve_batch_sel_dev:
+ * same kernels, same bits.  FFDDP_E_INVALID (with a message) when force_ref is
+ * given and the handle's w_fn <= 0, which has no fn_track cost to steer; the
+ * other errors are ffddp_solve_batch_sel_dev's.  The host-pointer entry point
+ * and solve plans take no force reference. */
+int ffddp_solve_batch_fref_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                               const double* inst_ref, const uint8_t* surface, const double* xs_init,
+                               const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
+                               double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
+                               const uint8_t* active, const double* force_ref, void* stream);
+
 /* Solve plan for a receding-horizon loop: one solve of a fixed batch per
  * control tick (crocoddyl_classical.py:367 called every tick at
  * run_classical.py:412).  ffddp_plan_create captures the whole host-array
@@ -247,6 +271,14 @@ int ffddp_calc_diff(ffddp_handle* h, int B, const double* x0, const double* node
                     const double* inst_ref, const uint8_t* surface, const double* xs,
                     const double* us, double* Fx, double* Fu, double* Lx, double* Lu, double* Lxx,
                     double* Lxu, double* Luu, double* cost, double* xnext, double* lam);
+/* ffddp_calc_diff with a host force_ref [B][N+1] (ffddp_solve_batch_fref_dev's
+ * array; NULL: ffddp_calc_diff).  FFDDP_E_INVALID when it is given and the
+ * handle's w_fn <= 0. */
+int ffddp_calc_diff_fref(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                         const double* inst_ref, const uint8_t* surface, const double* xs,
+                         const double* us, const double* force_ref, double* Fx, double* Fu, double* Lx,
+                         double* Lu, double* Lxx, double* Lxu, double* Luu, double* cost, double* xnext,
+                         double* lam);
 
 /* Host-side setup helpers (CPU, same model code): frame placement of the EE
  * (pin.forwardKinematics + updateFramePlacements, crocoddyl_classical.py:199-225)
@@ -771,6 +803,43 @@ int ffddp_fleet_metrics_dev(ffddp_handle* h, int B, int ld, const double* obs, i
                             int rows, double dt, const double* p_ref, double ts, const double* t_phase, double fn_des,
                             const double* info, const uint8_t* need, const int32_t* plant_fail, double* acc,
                             void* stream);
+
+/* Per-instance force setpoint profiles (ffddp/trajectory.py ForceProfile,
+ * force_records).  A record is FFDDP_FLEET_FORCE_W doubles: f0, f1, t_on,
+ * t_ramp (>= 0).  At task time tau the desired normal force is
+ *   f0 + (f1 - f0) s,  s = min(max((tau - t_on) / t_ramp, 0), 1) for t_ramp > 0,
+ *                      s = (tau >= t_on) for t_ramp == 0
+ * (add, subtract, multiply, divide, min, max, compiled without contraction:
+ * numpy's bits, trajectory.sample_force).
+ *
+ * ffddp_fleet_force_refs_dev: the sampler, one launch per tick before the
+ * solve.  force_ref [B][N+1] (ffddp_solve_batch_fref_dev's argument): knot k of
+ * instance b at (tasks.t - rec[b].delay) + k dt_ocp, the task sampler's knot
+ * times (only tasks.t and the task records' delay are read; tasks.rec == NULL
+ * means no delay); force [rows][FFDDP_FLEET_FORCE_W] the device records, an
+ * instance b >= rows takes fn_default at every knot and no record is read
+ * beyond min(rows, B).  One lane per (instance, knot), no shared memory.
+ * FFDDP_E_INVALID for a null handle, force or force_ref, rows < 0 or B <= 0;
+ * FFDDP_E_CAPACITY for B > max_batch.
+ *
+ * ffddp_fleet_metrics_fref_dev: ffddp_fleet_metrics_dev with SUM_ABS_FN_ERR +=
+ * |fn - f(ts)|, f instance b's own force record at the series time ts the
+ * call forms (above); an instance b >= rows_force uses the scalar fn_des.
+ * force == NULL is ffddp_fleet_metrics_dev: same kernel, same bits (rows_force
+ * ignored).  Errors as there, and FFDDP_E_INVALID for rows_force < 0 with
+ * records. */
+#define FFDDP_FLEET_FORCE_W 4
+#define FFDDP_FLEET_FORCE_F0 0
+#define FFDDP_FLEET_FORCE_F1 1
+#define FFDDP_FLEET_FORCE_T_ON 2
+#define FFDDP_FLEET_FORCE_T_RAMP 3
+int ffddp_fleet_force_refs_dev(ffddp_handle* h, int B, ffddp_fleet_tasks tasks, const double* force, int rows,
+                               double fn_default, double* force_ref, void* stream);
+int ffddp_fleet_metrics_fref_dev(ffddp_handle* h, int B, int ld, const double* obs, int ld_obs,
+                                 ffddp_fleet_tasks tasks, int rows, double dt, const double* p_ref, double ts,
+                                 const double* t_phase, double fn_des, const double* info, const uint8_t* need,
+                                 const int32_t* plant_fail, double* acc, const double* force, int rows_force,
+                                 void* stream);
 
 /* ---------------------------------------------------------------------------
  * Closed-loop plant stand-in: the MuJoCo plant of the

@@ -22,6 +22,8 @@ wall time, closed-loop ticks/s).
   python tools/sweep_c4.py --device-loop 1 --device-noise philox --plant-spread 0.5 0.5 --uncertainty-spread 0.5 3
                                                                # table stiffness, joint damping, noise levels and
                                                                # delays vary per instance (host path too)
+  python tools/sweep_c4.py --device-loop 1 --device-refs 1 --force-spread 8 36 --force-ramp 0.5
+                                                               # a force setpoint per instance, ramped in after touchdown
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/sweep_c4.py
 """
 import argparse
@@ -78,6 +80,11 @@ def main():
     ap.add_argument("--uncertainty-spread", type=float, nargs=2, default=None, metavar=("DN", "D"),
                     help="per-instance injector profile: sigmas scaled by 1 + DN u, u in [-1, 1], DN in [0, 1); "
                          "observation and command delay each 0..D ticks, D an integer 0..16")
+    ap.add_argument("--force-spread", type=float, nargs=2, default=None, metavar=("F_LO", "F_HI"),
+                    help="with --device-loop 1: per-instance force setpoint F_LO + (F_HI - F_LO) (1 + u) / 2, u in [-1, 1]")
+    ap.add_argument("--force-ramp", type=float, default=None, metavar="T",
+                    help="with --force-spread: the reference ramps from F_LO to the setpoint over T seconds from the end "
+                         "of the contact hold (0: the setpoint from the start)")
     ap.add_argument("--scenarios", nargs="+", default=list(ALL_SCENARIOS), help="scenarios to sweep (default: all 5)")
     a = ap.parse_args()
     import torch
@@ -101,7 +108,8 @@ def main():
                            solve_period=a.solve_period, command_filter=bool(a.command_filter),
                            device_refs=bool(a.device_refs), task_spread=a.task_spread, stagger=a.stagger,
                            device_summary=bool(a.device_summary), keep_logs=bool(a.keep_logs),
-                           plant_spread=a.plant_spread, uncertainty_spread=uspread)
+                           plant_spread=a.plant_spread, uncertainty_spread=uspread,
+                           force_spread=a.force_spread, force_ramp=a.force_ramp)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -132,6 +140,18 @@ def main():
                     rank0_inject_delay_max=[int(x) for x in dly[inj].max(0)] if inj.any() else None,
                     rank0_sigma_tau_range=[float(sig[inj, 2].min()), float(sig[inj, 2].max())] if inj.any() else None,
                     rank0_plant_fail_instances=int(np.count_nonzero(res.get("plant_fail", 0))))
+        if "force_rec" in res:  # this rank's shard by setpoint: measured contact-phase force and force error
+            f1 = res["force_rec"][:, 1]
+            pi = res["per_instance"]
+            edges = np.linspace(a.force_spread[0], a.force_spread[1], 5)
+            which = np.clip(np.digitize(f1, edges) - 1, 0, 3)
+            line.update(force_spread=a.force_spread, force_ramp=a.force_ramp, rank0_force_bins=[
+                {"setpoint_lo": float(edges[i]), "setpoint_hi": float(edges[i + 1]), "instances": int(np.sum(which == i)),
+                 "setpoint_mean": float(np.mean(f1[which == i])),
+                 "fn_mean_contact_phase": float(np.nanmean(pi["fn_mean_contact_phase"][which == i])),
+                 "avg_abs_force_err": float(np.nanmean(pi["avg_abs_force_err"][which == i])),
+                 "contact_loss_contact_phase_pct": float(np.nanmean(pi["contact_loss_contact_phase_pct"][which == i]))}
+                for i in range(4) if np.any(which == i)])
         # instances that left the nominal regime, per scenario: any tick on the unstable fallback; a non-finite summary
         ui, ri = fleet.SUMMARY_KEYS.index("unstable_ticks"), fleet.SUMMARY_KEYS.index("rms_3d_error")
         line["diverged"] = {str(s): {"unstable_instances": int(np.sum(m[names == s, ui] > 0)),
