@@ -118,6 +118,8 @@ struct Dev {
   int trace_it;
   const double* fref;  // [B][N+1] desired normal contact force per instance and node (ffddp_solve_batch_fref_dev),
                        //          read by the FR instantiations of k_node / k_forward_g8 only; null: C.fn_ref
+  const double* cw;    // [B][FFDDP_COST_W] cost-weight rows (ffddp_solve_batch_wts_dev), read by the CW
+                       //          instantiations of k_node / k_forward_g8 only; null: C's weights
 };
 
 // Active-instance compaction.  Iteration it reads list (it & 1): the
@@ -272,7 +274,9 @@ struct NodeShared {
 // The calc of one node on an 8-lane group (lanes = joints + EE): dynamics,
 // costs with their Gauss-Newton weights, gaps; Primal and link record to P /
 // lk (the node group's LDS in k_node).
-template <int NC, bool FF, bool FR>
+// CW: the scalar cost weights come from the instance's row d.cw[b] (index
+// constants FFDDP_CW_* of ffddp.h) instead of C; which terms exist stays C's.
+template <int NC, bool FF, bool FR, bool CW>
 __device__ __forceinline__ void primal_group(const DevConsts& C, const Dev& d, const double* __restrict__ x0,
                                              const double* __restrict__ node_ref, const double* __restrict__ inst_ref,
                                              const uint8_t* __restrict__ surface, int b, int t, Primal* P,
@@ -310,8 +314,9 @@ __device__ __forceinline__ void primal_group(const DevConsts& C, const Dev& d, c
     }
   }
   double lam[3];
-  const double pc = node_primal_g8<NC, FR>(C, mode, surf, q, v, u, xreg[ji], xreg[7 + ji], xreg[14 + ji], ref,
-                                           P, lk, lam, FR ? d.fref + ((long)b * (N + 1) + t) : nullptr);
+  const double* cw = CW ? d.cw + (long)b * FFDDP_COST_W : nullptr;
+  const double pc = node_primal_g8<NC, FR, CW>(C, mode, surf, q, v, u, xreg[ji], xreg[7 + ji], xreg[14 + ji], ref,
+                                               P, lk, lam, FR ? d.fref + ((long)b * (N + 1) + t) : nullptr, cw);
   double* rec = d.rec_buf + ((long)b * (N + 1) + t) * d.rec;
   // node cost (IAM scaling, FF augmentation terms): per-lane shares summed over the group
   double c = FF ? C.dt * pc : (terminal ? pc : C.dt * pc);
@@ -325,15 +330,15 @@ __device__ __forceinline__ void primal_group(const DevConsts& C, const Dev& d, c
           const double dd = y[7 * k + li] - x0[(long)b * nx + 7 * k + li];
           a_ += C.Wy2[7 * k + li] * dd * dd;
         }
-        part += 0.5 * C.w_y * a_;
+        part += 0.5 * cw_get<CW>(cw, FFDDP_CW_Y, C.w_y) * a_;
       }
       if (!terminal) {
         const double ww = usrc[(long)t * NU + li];
-        if (C.w_w > 0.0) part += 0.5 * C.w_w * (ww * ww);
+        if (C.w_w > 0.0) part += 0.5 * cw_get<CW>(cw, FFDDP_CW_W, C.w_w) * (ww * ww);
         if (C.w_ws > 0.0) {
           const double ov = fabs(ww) - C.ws_lim[li];
           const double o = ov > 0.0 ? ov : 0.0;
-          part += C.w_ws * (0.5 * (o * o));
+          part += cw_get<CW>(cw, FFDDP_CW_W_SOFT_LIMITS, C.w_ws) * (0.5 * (o * o));
         }
       }
     }
@@ -392,7 +397,10 @@ __device__ __forceinline__ double fquad(const double* a, const double* Dd, const
 // back was 129 + 366 us per launch at B=4096; fused, 255 us.
 // FR: the fn_track cost reads d.fref[b][t] instead of C.fn_ref (a solve with
 // a force_ref); FR = false is the kernel as it was.
-template <int NC, bool FF, bool FR = false>
+// CW: the scalar cost weights are those of the instance's row d.cw[b] (a solve
+// with cost_w), each loaded where its term is evaluated; CW = false is the
+// kernel as it was.
+template <int NC, bool FF, bool FR = false, bool CW = false>
 __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE_WAVES))) void k_node(const DevConsts* __restrict__ Cg, Dev d,
                                                       const double* __restrict__ x0,
                                                       const double* __restrict__ node_ref,
@@ -431,7 +439,7 @@ __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE
   const double* ref = node_ref + ((long)b * (N + 1) + t) * 6;
   NodeGroupShared& G = S.g[grp];
   Primal& P = G.P;
-  if (active && lane < G8) primal_group<NC, FF, FR>(C, d, x0, node_ref, inst_ref, surface, b, t, &P, G.lk, xsrc, usrc);
+  if (active && lane < G8) primal_group<NC, FF, FR, CW>(C, d, x0, node_ref, inst_ref, surface, b, t, &P, G.lk, xsrc, usrc);
   __syncthreads();
   const bool need_u = mode != MODE_TERMINAL_X;
   // control directions first, their results stored at once (neither touches
@@ -473,7 +481,13 @@ __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE
       wy = C.w_y;
       wy2j = C.Wy2[lane < 14 ? lane : 0];
       wy2u = C.Wy2[14 + (lane < 7 ? lane : 0)];
-      asm volatile("" : "+s"(wy), "+v"(wy2j), "+v"(wy2u));
+      if constexpr (CW) {
+        // a term the handle does not build keeps C's (zero) weight: its row entry is not read
+        if (C.w_y > 0.0) wy = d.cw[(long)b * FFDDP_COST_W + FFDDP_CW_Y];
+        asm volatile("" : "+v"(wy2j), "+v"(wy2u));
+      } else {
+        asm volatile("" : "+s"(wy), "+v"(wy2j), "+v"(wy2u));
+      }
     }
     if (lane < 14) {
       const int j = lane;
@@ -543,9 +557,18 @@ __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE
         const double ov = fabs(wk) - C.ws_lim[kk];
         const bool act = ov > 0.0;
         const double gs = act ? ov * (wk > 0.0 ? 1.0 : (wk < 0.0 ? -1.0 : 0.0)) : 0.0;
-        rec[rec_off_Lu(nx) + kk] = C.w_w * wk + C.w_ws * gs;
-        for (int m = 0; m < NU; ++m)
-          rec[rec_off_Luu(nx) + m * NU + kk] = (m == kk) ? (C.w_w + C.w_ws * (act ? 1.0 : 0.0)) : 0.0;
+        if constexpr (CW) {
+          const double* cwb = d.cw + (long)b * FFDDP_COST_W;
+          const double w_w = C.w_w > 0.0 ? cwb[FFDDP_CW_W] : C.w_w;
+          const double w_ws = C.w_ws > 0.0 ? cwb[FFDDP_CW_W_SOFT_LIMITS] : C.w_ws;
+          rec[rec_off_Lu(nx) + kk] = w_w * wk + w_ws * gs;
+          for (int m = 0; m < NU; ++m)
+            rec[rec_off_Luu(nx) + m * NU + kk] = (m == kk) ? (w_w + w_ws * (act ? 1.0 : 0.0)) : 0.0;
+        } else {
+          rec[rec_off_Lu(nx) + kk] = C.w_w * wk + C.w_ws * gs;
+          for (int m = 0; m < NU; ++m)
+            rec[rec_off_Luu(nx) + m * NU + kk] = (m == kk) ? (C.w_w + C.w_ws * (act ? 1.0 : 0.0)) : 0.0;
+        }
         for (int i = 0; i < nx; ++i) rec[rec_off_Lxu(nx) + i * NU + kk] = 0.0;
       }
     }
@@ -1988,7 +2011,11 @@ __device__ __forceinline__ int ls_row_bcast0(int v) {  // lane 0 of the row into
 #endif
 // FR: d.fref[b][t] is the node's force reference, prefetched with its
 // position / velocity references one node ahead.
-template <int NC, bool FF, bool ROW, bool FR = false>
+// CW: the scalar cost weights are the instance's row d.cw[b].  A lane needs
+// only its role's block of the row (joint lanes the state / control weights,
+// the EE lane the frame / contact ones: LS_CW registers shared by both roles),
+// loaded once before the node loop: the row does not depend on the node.
+template <int NC, bool FF, bool ROW, bool FR = false, bool CW = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW_WPE))) void k_forward_g8(const DevConsts* __restrict__ Cg, Dev d,
                                                    const double* __restrict__ x0,
                                                    const double* __restrict__ node_ref,
@@ -2070,6 +2097,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
   constexpr int NCX = FF ? 3 : 2;  // state components per joint lane
   double pxs[3] = {0, 0, 0}, pfs[3] = {0, 0, 0}, pw[3] = {0, 0, 0}, pK[21], pus = 0.0, pk = 0.0, pref[6];
   double pfr = 0.0;
+  LsW W;
+  if constexpr (CW) {
+    const double* cwr = d.cw + (long)b * FFDDP_COST_W + (J ? FFDDP_CW_JOINT0 : 0);
+#pragma unroll
+    for (int k = 0; k < LS_CW; ++k) W.w[k] = cwr[k];
+  }
+  // FF augmentation weights (joint lanes) at their use: a term the handle does not build keeps C's zero
+  auto w_y = [&]() { return (CW && C.w_y > 0.0) ? W.w[FFDDP_CW_Y - FFDDP_CW_JOINT0] : C.w_y; };
+  auto w_w = [&]() { return (CW && C.w_w > 0.0) ? W.w[FFDDP_CW_W - FFDDP_CW_JOINT0] : C.w_w; };
+  auto w_ws = [&]() { return (CW && C.w_ws > 0.0) ? W.w[FFDDP_CW_W_SOFT_LIMITS - FFDDP_CW_JOINT0] : C.w_ws; };
   auto fetch = [&](int t) {
     const long nb = (long)b * (N + 1) + t;
 #pragma unroll
@@ -2134,7 +2171,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
       double qn, vn, cp, lam[3];
       const double uin = FF ? xt_t : u;
       PP(8);
-      ls_node_calc<NC, ROW, FR>(C, fl, K, MODE_RUNNING, surf, xq_t, xv_t, uin, xq, xv, tref, ref, fnr, qn, vn, cp, lam
+      ls_node_calc<NC, ROW, FR, CW>(C, fl, K, W, MODE_RUNNING, surf, xq_t, xv_t, uin, xq, xv, tref, ref, fnr, qn, vn, cp, lam
 #ifdef FFDDP_PHASE_PROF
                             , pp_acc, pp_last
 #endif
@@ -2145,11 +2182,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
         tn = fma(C.beta, u, C.alpha * xt_t);
         if (J) {
           const double e1 = xq_t - yq, e2 = xv_t - yv, e3 = xt_t - yt;
-          c = fma(0.5 * C.w_y, fma(K.wy2t * e3, e3, fma(K.wy2v * e2, e2, (K.wy2q * e1) * e1)), c);
-          c = fma(0.5 * C.w_w, u * u, c);
+          c = fma(0.5 * w_y(), fma(K.wy2t * e3, e3, fma(K.wy2v * e2, e2, (K.wy2q * e1) * e1)), c);
+          c = fma(0.5 * w_w(), u * u, c);
           const double ov = fabs(u) - K.wslim;
           const double oo = ov > 0.0 ? ov : 0.0;
-          c = fma(C.w_ws, 0.5 * (oo * oo), c);
+          c = fma(w_ws(), 0.5 * (oo * oo), c);
         }
       }
       cost += g8_sum(c);
@@ -2167,7 +2204,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
       double qn, vn, cp, lam[3];
       const int mode = FF ? MODE_TERMINAL_U : MODE_TERMINAL_X;
       PP(8);
-      ls_node_calc<NC, ROW, FR>(C, fl, K, mode, surf, xq_t, xv_t, FF ? xt_t : 0.0, xq, xv, tref, ref, fnr, qn, vn, cp, lam
+      ls_node_calc<NC, ROW, FR, CW>(C, fl, K, W, mode, surf, xq_t, xv_t, FF ? xt_t : 0.0, xq, xv, tref, ref, fnr, qn, vn, cp, lam
 #ifdef FFDDP_PHASE_PROF
                             , pp_acc, pp_last
 #endif
@@ -2175,7 +2212,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
       double c = FF ? C.dt * cp : cp;
       if (FF && J) {
         const double e1 = xq_t - yq, e2 = xv_t - yv, e3 = xt_t - yt;
-        c = fma(0.5 * C.w_y, fma(K.wy2t * e3, e3, fma(K.wy2v * e2, e2, (K.wy2q * e1) * e1)), c);
+        c = fma(0.5 * w_y(), fma(K.wy2t * e3, e3, fma(K.wy2v * e2, e2, (K.wy2q * e1) * e1)), c);
       }
       cost += g8_sum(c);
     }
@@ -3071,6 +3108,9 @@ struct ffddp_handle {
   std::vector<ffddp_plan*> plans;
   hipEvent_t last_done = nullptr;
   bool last_done_set = false;
+  // [max_batch][N+1] filled with fn_des: the force reference of a solve with cost weights
+  // and no force_ref of its own (first such solve)
+  double* fref_const = nullptr;
   // sub-batch streams: the batch is split into nstreams slices solved on their
   // own HIP streams, so latency-bound phases of one slice overlap with the
   // throughput-bound phases of another (FFDDP_STREAMS, default 4: three
@@ -3152,6 +3192,7 @@ void free_all(ffddp_handle* h) {
   for (void* p : ps)
     if (p) (void)hipFree(p);
   if (h->trace) (void)hipFree(h->trace);
+  if (h->fref_const) (void)hipFree(h->fref_const);
   if (h->stage) (void)hipHostFree(h->stage);
 }
 
@@ -3203,14 +3244,16 @@ Dev dev_slice(const Dev& d0, int b0, int Bk, int k) {
   d.acnt += 4 * k;
   if (d.trace) d.trace += (long)b0 * d0.trace_it * FFDDP_TRACE_W;
   if (d.fref) d.fref += (long)b0 * (N + 1);
+  if (d.cw) d.cw += (long)b0 * FFDDP_COST_W;
   return d;
 }
 
-template <int NC, bool FF, bool FR = false>
+template <int NC, bool FF, bool FR = false, bool CW = false>
 int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref, const double* iref,
                  const uint8_t* surf, const double* xs_init, const double* us_init, int maxiter, int is_feasible,
                  double* xs, double* us, double* K, double* cost, int32_t* iters, uint8_t* ok, double* fn_pred,
-                 int32_t* stats, hipStream_t s, HostIO* io, const uint8_t* active, const double* fref = nullptr) {
+                 int32_t* stats, hipStream_t s, HostIO* io, const uint8_t* active, const double* fref = nullptr,
+                 const double* cw = nullptr) {
   const int N = h->hc.N, nx = h->hc.nx;
   int S = h->nstreams;
   if (B < 64 * S) S = 1;
@@ -3244,6 +3287,7 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
   // entry point keeps the handle's buffers (its outputs are host memory)
   Dev dbase = h->d;
   dbase.fref = FR ? fref : nullptr;
+  dbase.cw = CW ? cw : nullptr;
   if (!io) {
     dbase.xs = xs;
     dbase.us = us;
@@ -3307,7 +3351,7 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
     if (it == 0 && stagger == 2 && k + 1 < S) HIPCHK(h, hipEventRecord(h->stg[k], ss));
     {
       ProfScope p(h, ss, KC_NODE);
-      hipLaunchKernelGGL((k_node<NC, FF, FR>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, ss,
+      hipLaunchKernelGGL((k_node<NC, FF, FR, CW>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, ss,
                          h->dc, d, x0k, nrefk, irefk, surfk, 0, it & 1);
     }
     if (it == 0 && stagger == 1 && k + 1 < S) HIPCHK(h, hipEventRecord(h->stg[k], ss));
@@ -3378,13 +3422,13 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
         const long groups = more ? (long)Bk * ntr : g1;
         if (!row_only) {
           const dim3 grid((unsigned)((groups * G8 + 63) / 64));
-          hipLaunchKernelGGL((k_forward_g8<NC, FF, false, FR>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
+          hipLaunchKernelGGL((k_forward_g8<NC, FF, false, FR, CW>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
                              surfk, tr0, ntr, more, it & 1, wide, row_max);
         }
         if (row_max > 0) {
           const long rg = std::min(groups, (long)row_max);  // the row layout runs only when they fit
           const dim3 grid((unsigned)((rg * 16 + 63) / 64));
-          hipLaunchKernelGGL((k_forward_g8<NC, FF, true, FR>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
+          hipLaunchKernelGGL((k_forward_g8<NC, FF, true, FR, CW>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
                              surfk, tr0, ntr, more, it & 1, wide, row_max);
         }
       };
@@ -3487,25 +3531,32 @@ int launch_solve(ffddp_handle* h, int B, const double* x0, const double* nref, c
                  const uint8_t* surf, const double* xs_init, const double* us_init, int maxiter, int is_feasible,
                  double* xs, double* us, double* K, double* cost, int32_t* iters, uint8_t* ok, double* fn_pred,
                  int32_t* stats, hipStream_t s, HostIO* io = nullptr, const uint8_t* active = nullptr,
-                 const double* fref = nullptr) {
+                 const double* fref = nullptr, const double* cw = nullptr) {
   const bool ff = h->hc.variant == FFDDP_FORCE_FEEDBACK;
   const int nc = h->hc.nc;
-  // fref: the solve's force reference; without one the kernels are the FR = false instantiations, as before
-#define FFDDP_LS(NC_, FF_, FR_) \
-  launch_solve_t<NC_, FF_, FR_>(h, B, x0, nref, iref, surf, xs_init, us_init, maxiter, is_feasible, xs, us, K, cost, iters, ok, fn_pred, stats, s, io, active, fref)
-  if (fref) {
-    if (nc == 1) return ff ? FFDDP_LS(1, true, true) : FFDDP_LS(1, false, true);
-    return ff ? FFDDP_LS(3, true, true) : FFDDP_LS(3, false, true);
+  // fref: the solve's force reference; without one the kernels are the FR = false instantiations, as before.
+  // cw: the solve's cost-weight rows.  The CW kernels exist with FR only (the caller supplies a
+  // force reference of fn_des where the user gave none: the same bits), so the build does not double.
+#define FFDDP_LS(NC_, FF_, FR_, CW_) \
+  launch_solve_t<NC_, FF_, FR_, CW_>(h, B, x0, nref, iref, surf, xs_init, us_init, maxiter, is_feasible, xs, us, K, cost, iters, ok, fn_pred, stats, s, io, active, fref, cw)
+  if (cw) {
+    if (!fref) return fail(h, FFDDP_E_INVALID, "cost weights without a force reference");
+    if (nc == 1) return ff ? FFDDP_LS(1, true, true, true) : FFDDP_LS(1, false, true, true);
+    return ff ? FFDDP_LS(3, true, true, true) : FFDDP_LS(3, false, true, true);
   }
-  if (nc == 1) return ff ? FFDDP_LS(1, true, false) : FFDDP_LS(1, false, false);
-  return ff ? FFDDP_LS(3, true, false) : FFDDP_LS(3, false, false);
+  if (fref) {
+    if (nc == 1) return ff ? FFDDP_LS(1, true, true, false) : FFDDP_LS(1, false, true, false);
+    return ff ? FFDDP_LS(3, true, true, false) : FFDDP_LS(3, false, true, false);
+  }
+  if (nc == 1) return ff ? FFDDP_LS(1, true, false, false) : FFDDP_LS(1, false, false, false);
+  return ff ? FFDDP_LS(3, true, false, false) : FFDDP_LS(3, false, false, false);
 #undef FFDDP_LS
 }
 
-template <int NC, bool FF, bool FR = false>
+template <int NC, bool FF, bool FR = false, bool CW = false>
 void launch_node(ffddp_handle* h, Dev d, int B, hipStream_t s, int force_all) {
   const long nodes = (long)B * (h->hc.N + 1);
-  hipLaunchKernelGGL((k_node<NC, FF, FR>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, s, h->dc,
+  hipLaunchKernelGGL((k_node<NC, FF, FR, CW>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, s, h->dc,
                      d, h->in_x0, h->in_nref, h->in_iref, h->in_surf, force_all, 0);
 }
 
@@ -3762,11 +3813,22 @@ static int mark_solve_done(ffddp_handle* h, hipStream_t s) {
   return 0;
 }
 
-int ffddp_solve_batch_fref_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
-                               const double* inst_ref, const uint8_t* surface, const double* xs_init,
-                               const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
-                               double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
-                               const uint8_t* active, const double* force_ref, void* stream) {
+// the handle's constant force reference (fn_des everywhere), made on first use: the CW kernels are
+// instantiated with FR only, and an array of fn_des reproduces the scalar path's bits
+static int const_force_ref(ffddp_handle* h) {
+  if (h->fref_const) return 0;
+  const size_t n = (size_t)h->max_batch * (h->hc.N + 1);
+  const std::vector<double> v(n, h->hc.fn_ref[h->hc.nc - 1]);
+  if (int rc = dalloc(h, &h->fref_const, n)) return rc;
+  HIPCHK(h, hipMemcpy(h->fref_const, v.data(), n * 8, hipMemcpyHostToDevice));
+  return 0;
+}
+
+int ffddp_solve_batch_wts_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                              const double* inst_ref, const uint8_t* surface, const double* xs_init,
+                              const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
+                              double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
+                              const uint8_t* active, const double* force_ref, const double* cost_w, void* stream) {
   if (!h) return FFDDP_E_INVALID;
   if (force_ref && !(h->hc.w_fn > 0.0))
     return fail(h, FFDDP_E_INVALID, "force_ref given but the handle has no fn_track cost (w_fn <= 0)");
@@ -3779,10 +3841,24 @@ int ffddp_solve_batch_fref_dev(ffddp_handle* h, int B, const double* x0, const d
   // the handle's workspace is shared by every solve: a solve enqueued on
   // another (possibly non-blocking) stream must finish before this one starts
   if (h->last_done_set) HIPCHK(h, hipStreamWaitEvent((hipStream_t)stream, h->last_done, 0));
+  if (cost_w && !force_ref) {
+    if (int rc = const_force_ref(h)) return rc;
+    force_ref = h->fref_const;
+  }
   const int rc = launch_solve(h, B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs, us,
-                              K, cost, iters, ok, fn_pred, stats, (hipStream_t)stream, nullptr, active, force_ref);
+                              K, cost, iters, ok, fn_pred, stats, (hipStream_t)stream, nullptr, active, force_ref,
+                              cost_w);
   if (rc) return rc;
   return mark_solve_done(h, (hipStream_t)stream);
+}
+
+int ffddp_solve_batch_fref_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                               const double* inst_ref, const uint8_t* surface, const double* xs_init,
+                               const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
+                               double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
+                               const uint8_t* active, const double* force_ref, void* stream) {
+  return ffddp_solve_batch_wts_dev(h, B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs,
+                                   us, K, cost, iters, ok, fn_pred, stats, active, force_ref, nullptr, stream);
 }
 
 int ffddp_solve_batch_sel_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
@@ -4286,14 +4362,22 @@ int ffddp_trace_read(ffddp_handle* h, int B, double* out) {
 int ffddp_calc_diff(ffddp_handle* h, int B, const double* x0, const double* node_ref, const double* inst_ref,
                     const uint8_t* surface, const double* xs, const double* us, double* Fx, double* Fu, double* Lx,
                     double* Lu, double* Lxx, double* Lxu, double* Luu, double* cost, double* xnext, double* lam) {
-  return ffddp_calc_diff_fref(h, B, x0, node_ref, inst_ref, surface, xs, us, nullptr, Fx, Fu, Lx, Lu, Lxx, Lxu, Luu,
-                              cost, xnext, lam);
+  return ffddp_calc_diff_wts(h, B, x0, node_ref, inst_ref, surface, xs, us, nullptr, nullptr, Fx, Fu, Lx, Lu, Lxx, Lxu,
+                             Luu, cost, xnext, lam);
 }
 
 int ffddp_calc_diff_fref(ffddp_handle* h, int B, const double* x0, const double* node_ref, const double* inst_ref,
                          const uint8_t* surface, const double* xs, const double* us, const double* force_ref,
                          double* Fx, double* Fu, double* Lx, double* Lu, double* Lxx, double* Lxu, double* Luu,
                          double* cost, double* xnext, double* lam) {
+  return ffddp_calc_diff_wts(h, B, x0, node_ref, inst_ref, surface, xs, us, force_ref, nullptr, Fx, Fu, Lx, Lu, Lxx,
+                             Lxu, Luu, cost, xnext, lam);
+}
+
+int ffddp_calc_diff_wts(ffddp_handle* h, int B, const double* x0, const double* node_ref, const double* inst_ref,
+                        const uint8_t* surface, const double* xs, const double* us, const double* force_ref,
+                        const double* cost_w, double* Fx, double* Fu, double* Lx, double* Lu, double* Lxx, double* Lxu,
+                        double* Luu, double* cost, double* xnext, double* lam) {
   if (!h) return FFDDP_E_INVALID;
   if (B < 1 || B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "bad B");
   if (force_ref && !(h->hc.w_fn > 0.0))
@@ -4305,16 +4389,23 @@ int ffddp_calc_diff_fref(ffddp_handle* h, int B, const double* x0, const double*
     ~Tmp() {
       if (p) (void)hipFree(p);
     }
-  } fref;
+  } fref, cw;
   if (force_ref) {
     HIPCHK(h, hipMalloc((void**)&fref.p, (size_t)B * (h->hc.N + 1) * 8));
     HIPCHK(h, hipMemcpy(fref.p, force_ref, (size_t)B * (h->hc.N + 1) * 8, hipMemcpyHostToDevice));
+  } else if (cost_w) {
+    if (int rc = const_force_ref(h)) return rc;
+  }
+  if (cost_w) {
+    HIPCHK(h, hipMalloc((void**)&cw.p, (size_t)B * FFDDP_COST_W * 8));
+    HIPCHK(h, hipMemcpy(cw.p, cost_w, (size_t)B * FFDDP_COST_W * 8, hipMemcpyHostToDevice));
   }
   const int N = h->hc.N, nx = h->hc.nx, R = h->d.rec;
   const bool ff = h->hc.variant == FFDDP_FORCE_FEEDBACK;
   Dev d = h->d;
   d.B = B;
-  d.fref = fref.p;
+  d.fref = fref.p ? fref.p : (cost_w ? h->fref_const : nullptr);
+  d.cw = cw.p;
   HIPCHK(h, hipMemcpy(h->in_x0, x0, (size_t)B * nx * 8, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->in_nref, node_ref, (size_t)B * (N + 1) * 6 * 8, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->in_iref, inst_ref, (size_t)B * 21 * 8, hipMemcpyHostToDevice));
@@ -4323,7 +4414,12 @@ int ffddp_calc_diff_fref(ffddp_handle* h, int B, const double* x0, const double*
   HIPCHK(h, hipMemcpy(h->in_us, us, (size_t)B * N * NU * 8, hipMemcpyHostToDevice));
   // node kernel reads (xs, us) from the solver state: initialise it from the inputs
   hipLaunchKernelGGL(k_init<false>, dim3(1024), dim3(INIT_BLOCK), 0, nullptr, h->dc, d, h->in_xs, h->in_us, 0, nullptr);
-  if (force_ref) {
+  if (cost_w) {
+    if (h->hc.nc == 1)
+      ff ? launch_node<1, true, true, true>(h, d, B, nullptr, 1) : launch_node<1, false, true, true>(h, d, B, nullptr, 1);
+    else
+      ff ? launch_node<3, true, true, true>(h, d, B, nullptr, 1) : launch_node<3, false, true, true>(h, d, B, nullptr, 1);
+  } else if (force_ref) {
     if (h->hc.nc == 1)
       ff ? launch_node<1, true, true>(h, d, B, nullptr, 1) : launch_node<1, false, true>(h, d, B, nullptr, 1);
     else

@@ -20,6 +20,52 @@
 
 namespace ffddp {
 
+// A scalar cost weight: entry i of the instance's row (CW) or the handle's c.
+template <bool CW>
+__device__ __forceinline__ double cw_get(const double* __restrict__ cw, int i, double c) {
+  if constexpr (CW)
+    return cw[i];
+  else
+    return c;
+}
+
+// friction_cone of ffddp_node.hpp with the weight *wp, loaded after the facet
+// sums, where it is first needed (same operations in the same order:
+// *wp = C.w_fc gives its bits)
+__device__ __forceinline__ double friction_cone_w(const DevConsts& C, const double* __restrict__ wp, const double* lam,
+                                                  double* gl, double* Hd, double* Ho) {
+  double c = 0.0;
+  double g0 = 0.0, g1 = 0.0, g2 = 0.0, h00 = 0.0, h11 = 0.0, h22 = 0.0, h10 = 0.0, h20 = 0.0, h21 = 0.0;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const double* A = C.fc_A[k];
+    const double r = A[0] * lam[0] + A[1] * lam[1] + A[2] * lam[2];
+    double ai, Ar, Arr;
+    barrier(r, C.fc_lb[k], C.fc_ub[k], ai, Ar, Arr);
+    c += ai;
+    g0 += A[0] * Ar;
+    g1 += A[1] * Ar;
+    g2 += A[2] * Ar;
+    h00 += A[0] * Arr * A[0];
+    h11 += A[1] * Arr * A[1];
+    h22 += A[2] * Arr * A[2];
+    h10 += A[1] * Arr * A[0];
+    h20 += A[2] * Arr * A[0];
+    h21 += A[2] * Arr * A[1];
+  }
+  const double w = *wp;
+  gl[0] = w * g0;
+  gl[1] = w * g1;
+  gl[2] = w * g2;
+  Hd[0] = w * h00;
+  Hd[1] = w * h11;
+  Hd[2] = w * h22;
+  Ho[0] = w * h10;
+  Ho[1] = w * h20;
+  Ho[2] = w * h21;
+  return w * c;
+}
+
 // gp: this node's Primal in global memory; lk: its link record (LK_* layout).
 // Returns (group-uniform) the unscaled DAM cost and the contact force.
 // FR: the normal-force reference of this node is *fnp (the solve's per-instance,
@@ -27,11 +73,16 @@ namespace ffddp {
 // stay C's.  It is loaded where the cost needs it, not with the node's other
 // inputs: held across the calc it costs the force-feedback k_node, which is at
 // its register limit, 8 to 12 bytes of scratch per lane.
-template <int NC, bool FR = false>
+// CW: the scalar cost weights are the entries of cwr (the instance's row,
+// FFDDP_CW_* of ffddp.h) instead of C's, each loaded inside the block of the
+// term that uses it, for the same reason; a term C does not build never
+// reads its entry.
+template <int NC, bool FR = false, bool CW = false>
 __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, bool surface, double q, double v, double u,
                                                  double xq, double xv, double tr, const double* ref,
                                                  Primal* __restrict__ gp, double* __restrict__ lk, double (&lam)[3],
-                                                 const double* __restrict__ fnp = nullptr) {
+                                                 const double* __restrict__ fnp = nullptr,
+                                                 const double* __restrict__ cwr = nullptr) {
   const ffddp_robot& rb = C.rb;
   const int li = g8_lane();
   const bool J = li < NQ;
@@ -472,43 +523,45 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
     }
   }
   // ---- costs (CostModelSum, _make_dam order) with their Gauss-Newton weights ----
+  // a scalar weight at its use: the row's entry (CW) or C's
+  auto wt = [&](int i, double c) { return cw_get<CW>(cwr, i, c); };
   double cj = 0.0;  // this lane's state / control costs
   {
     double dxq = 0.0, gxq = 0.0, dxv = 0.0, gxv = 0.0, du = 0.0, gu = 0.0;
     if (J) {
       if (C.variant == FFDDP_CLASSICAL || C.inner_state_reg) {
         const double rq = q - xq, rv = v - xv;
-        dxq += C.w_post;
-        gxq += C.w_post * rq;
-        dxv += C.w_post;
-        gxv += C.w_post * rv;
-        cj += C.w_post * (0.5 * (rq * rq + rv * rv));
+        dxq += wt(FFDDP_CW_POSTURE, C.w_post);
+        gxq += wt(FFDDP_CW_POSTURE, C.w_post) * rq;
+        dxv += wt(FFDDP_CW_POSTURE, C.w_post);
+        gxv += wt(FFDDP_CW_POSTURE, C.w_post) * rv;
+        cj += wt(FFDDP_CW_POSTURE, C.w_post) * (0.5 * (rq * rq + rv * rv));
         const double wi = C.vdw[ji];
-        dxv += C.w_v * wi;
-        gxv += C.w_v * wi * v;
-        cj += C.w_v * (0.5 * (wi * v * v));
+        dxv += wt(FFDDP_CW_V, C.w_v) * wi;
+        gxv += wt(FFDDP_CW_V, C.w_v) * wi * v;
+        cj += wt(FFDDP_CW_V, C.w_v) * (0.5 * (wi * v * v));
       }
       if (C.has_qsoft) {
         double ai, Ar, Arr, bi, Br, Brr;
         barrier(q - C.qs_xref[ji], C.qs_lb[ji], C.qs_ub[ji], ai, Ar, Arr);
         barrier(v - C.qs_xref[7 + ji], C.qs_lb[7 + ji], C.qs_ub[7 + ji], bi, Br, Brr);
-        dxq += C.w_qs * Arr;
-        gxq += C.w_qs * Ar;
-        dxv += C.w_qs * Brr;
-        gxv += C.w_qs * Br;
-        cj += C.w_qs * (ai + bi);
+        dxq += wt(FFDDP_CW_Q_SOFT_LIMITS, C.w_qs) * Arr;
+        gxq += wt(FFDDP_CW_Q_SOFT_LIMITS, C.w_qs) * Ar;
+        dxv += wt(FFDDP_CW_Q_SOFT_LIMITS, C.w_qs) * Brr;
+        gxv += wt(FFDDP_CW_Q_SOFT_LIMITS, C.w_qs) * Br;
+        cj += wt(FFDDP_CW_Q_SOFT_LIMITS, C.w_qs) * (ai + bi);
       }
       if (!terminal && (C.variant == FFDDP_CLASSICAL || C.inner_tau_reg)) {
         const double r = u - tr;
-        du += C.w_tau;
-        gu += C.w_tau * r;
-        cj += C.w_tau * (0.5 * r * r);
+        du += wt(FFDDP_CW_TAU, C.w_tau);
+        gu += wt(FFDDP_CW_TAU, C.w_tau) * r;
+        cj += wt(FFDDP_CW_TAU, C.w_tau) * (0.5 * r * r);
         if (C.has_tsoft) {
           double ai, Ar, Arr;
           barrier(u, C.ts_lb[ji], C.ts_ub[ji], ai, Ar, Arr);
-          du += C.w_ts * Arr;
-          gu += C.w_ts * Ar;
-          cj += C.w_ts * ai;
+          du += wt(FFDDP_CW_TAU_SOFT_LIMITS, C.w_ts) * Arr;
+          gu += wt(FFDDP_CW_TAU_SOFT_LIMITS, C.w_ts) * Ar;
+          cj += wt(FFDDP_CW_TAU_SOFT_LIMITS, C.w_ts) * ai;
         }
       }
       gp->Dx[li] = dxq;
@@ -539,20 +592,20 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       s += C.ori_w[i] * rr[i] * rr[i];
-      Dd[3 + i] += C.w_ori * C.ori_w[i];
-      gd[3 + i] += C.w_ori * C.ori_w[i] * rr[i];
+      Dd[3 + i] += wt(FFDDP_CW_EE_ORI, C.w_ori) * C.ori_w[i];
+      gd[3 + i] += wt(FFDDP_CW_EE_ORI, C.w_ori) * C.ori_w[i] * rr[i];
     }
-    cee += C.w_ori * (0.5 * s);
+    cee += wt(FFDDP_CW_EE_ORI, C.w_ori) * (0.5 * s);
   }
   {
     double s = 0.0;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       s += C.wd_w[i] * wee[i] * wee[i];
-      Dd[9 + i] += C.w_wd * C.wd_w[i];
-      gd[9 + i] += C.w_wd * C.wd_w[i] * wee[i];
+      Dd[9 + i] += wt(FFDDP_CW_WDAMP, C.w_wd) * C.wd_w[i];
+      gd[9 + i] += wt(FFDDP_CW_WDAMP, C.w_wd) * C.wd_w[i] * wee[i];
     }
-    cee += C.w_wd * (0.5 * s);
+    cee += wt(FFDDP_CW_WDAMP, C.w_wd) * (0.5 * s);
   }
   if (!surface) {
     double s = 0.0;
@@ -560,39 +613,39 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
     for (int i = 0; i < 3; ++i) {
       const double r = pee[i] - ref[i];
       s += C.ee_pos_w[i] * r * r;
-      Dd[i] += C.w_ee_pos * C.ee_pos_w[i];
-      gd[i] += C.w_ee_pos * C.ee_pos_w[i] * r;
+      Dd[i] += wt(FFDDP_CW_EE_POS, C.w_ee_pos) * C.ee_pos_w[i];
+      gd[i] += wt(FFDDP_CW_EE_POS, C.w_ee_pos) * C.ee_pos_w[i] * r;
     }
-    cee += C.w_ee_pos * (0.5 * s);
+    cee += wt(FFDDP_CW_EE_POS, C.w_ee_pos) * (0.5 * s);
   } else {
     const double pstar2 = ref[2] - C.z_press;
     {
       const double rx = pee[0] - ref[0], ry = pee[1] - ref[1], rz = pee[2] - ref[2];
       const double s = rx * rx + ry * ry + 0.0 * rz * rz;
-      Dd[0] += C.w_tp;
-      Dd[1] += C.w_tp;
-      gd[0] += C.w_tp * rx;
-      gd[1] += C.w_tp * ry;
-      cee += C.w_tp * (0.5 * s);
+      Dd[0] += wt(FFDDP_CW_TANGENT_POS, C.w_tp);
+      Dd[1] += wt(FFDDP_CW_TANGENT_POS, C.w_tp);
+      gd[0] += wt(FFDDP_CW_TANGENT_POS, C.w_tp) * rx;
+      gd[1] += wt(FFDDP_CW_TANGENT_POS, C.w_tp) * ry;
+      cee += wt(FFDDP_CW_TANGENT_POS, C.w_tp) * (0.5 * s);
     }
     {
       const double rx = vp[0] - ref[3], ry = vp[1] - ref[4];
-      Dd[6] += C.w_tv;
-      Dd[7] += C.w_tv;
-      gd[6] += C.w_tv * rx;
-      gd[7] += C.w_tv * ry;
-      cee += C.w_tv * (0.5 * (rx * rx + ry * ry));
+      Dd[6] += wt(FFDDP_CW_TANGENT_VEL, C.w_tv);
+      Dd[7] += wt(FFDDP_CW_TANGENT_VEL, C.w_tv);
+      gd[6] += wt(FFDDP_CW_TANGENT_VEL, C.w_tv) * rx;
+      gd[7] += wt(FFDDP_CW_TANGENT_VEL, C.w_tv) * ry;
+      cee += wt(FFDDP_CW_TANGENT_VEL, C.w_tv) * (0.5 * (rx * rx + ry * ry));
     }
     if (C.has_pz) {
       const double rz = pee[2] - pstar2;
-      Dd[2] += C.w_pz;
-      gd[2] += C.w_pz * rz;
-      cee += C.w_pz * (0.5 * rz * rz);
+      Dd[2] += wt(FFDDP_CW_PLANE_Z, C.w_pz);
+      gd[2] += wt(FFDDP_CW_PLANE_Z, C.w_pz) * rz;
+      cee += wt(FFDDP_CW_PLANE_Z, C.w_pz) * (0.5 * rz * rz);
     }
     if (C.has_vz) {
-      Dd[8] += C.w_vz;
-      gd[8] += C.w_vz * vp[2];
-      cee += C.w_vz * (0.5 * vp[2] * vp[2]);
+      Dd[8] += wt(FFDDP_CW_VZ, C.w_vz);
+      gd[8] += wt(FFDDP_CW_VZ, C.w_vz) * vp[2];
+      cee += wt(FFDDP_CW_VZ, C.w_vz) * (0.5 * vp[2] * vp[2]);
     }
     double lm[3] = {0, 0, 0};
     if (mode != MODE_TERMINAL_X)
@@ -600,7 +653,10 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
       for (int r = 0; r < NC; ++r) lm[r] = lam[r];
     if (NC == 3 && C.has_fc) {
       double gl[3], Hd[3], Ho[3];
-      cee += friction_cone(C, lm, gl, Hd, Ho);
+      if constexpr (CW)
+        cee += friction_cone_w(C, cwr + FFDDP_CW_FRICTION_CONE, lm, gl, Hd, Ho);
+      else
+        cee += friction_cone(C, lm, gl, Hd, Ho);
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
         Dd[12 + r] += Hd[r];
@@ -621,10 +677,10 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
         double ai, Ar, Arr;
         barrier(lm[r], C.uni_lb[r], C.uni_ub[r], ai, Ar, Arr);
         s += ai;
-        Dd[12 + r] += C.w_uni * Arr;
-        gd[12 + r] += C.w_uni * Ar;
+        Dd[12 + r] += wt(FFDDP_CW_UNILATERAL, C.w_uni) * Arr;
+        gd[12 + r] += wt(FFDDP_CW_UNILATERAL, C.w_uni) * Ar;
       }
-      cee += C.w_uni * s;
+      cee += wt(FFDDP_CW_UNILATERAL, C.w_uni) * s;
     }
     if (C.has_fn) {
       double s = 0.0;
@@ -634,10 +690,10 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
       for (int r = 0; r < NC; ++r) {
         const double e = lm[r] - ((FR && r == NC - 1) ? fnr : C.fn_ref[r]);
         s += C.fn_w[r] * e * e;
-        Dd[12 + r] += C.w_fn * C.fn_w[r];
-        gd[12 + r] += C.w_fn * C.fn_w[r] * e;
+        Dd[12 + r] += wt(FFDDP_CW_FN, C.w_fn) * C.fn_w[r];
+        gd[12 + r] += wt(FFDDP_CW_FN, C.w_fn) * C.fn_w[r] * e;
       }
-      cee += C.w_fn * (0.5 * s);
+      cee += wt(FFDDP_CW_FN, C.w_fn) * (0.5 * s);
     }
   }
   if (li == 0) {

@@ -152,15 +152,27 @@ __device__ __forceinline__ double ls_barrier(double r, double lb, double ub) {
   const double ru = du > 0.0 ? du : 0.0;
   return 0.5 * fma(ru, ru, rl * rl);
 }
-// friction-cone cost (ffddp_node.hpp friction_cone, value only)
-__device__ __forceinline__ double ls_friction_cone(const DevConsts& C, const double* lam) {
+// One lane's share of an instance's cost-weight row (ffddp.h FFDDP_CW_*): the
+// EE lane holds the row's frame / contact block (entries 0..9, at their
+// indices), a joint lane the state / control block (entries FFDDP_CW_JOINT0..,
+// at index - FFDDP_CW_JOINT0; the block's padding fills the rest).  The two
+// roles never read each other's terms, so they share the registers.
+constexpr int LS_CW = 10;
+static_assert(FFDDP_CW_FRICTION_CONE < LS_CW && FFDDP_CW_JOINT0 + LS_CW <= FFDDP_COST_W, "row blocks");
+struct LsW {
+  double w[LS_CW];
+};
+
+// friction-cone cost (ffddp_node.hpp friction_cone, value only); CW: the weight is W's entry
+template <bool CW>
+__device__ __forceinline__ double ls_friction_cone(const DevConsts& C, const LsW& W, const double* lam) {
   double c = 0.0;
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
     const double* A = C.fc_A[k];
     c += ls_barrier(ls_dot3(A[0], lam[0], A[1], lam[1], A[2], lam[2]), C.fc_lb[k], C.fc_ub[k]);
   }
-  return C.w_fc * c;
+  return (CW ? W.w[FFDDP_CW_FRICTION_CONE] : C.w_fc) * c;
 }
 
 // ---- group primitives per layout ----
@@ -241,8 +253,12 @@ template <bool ROW> __device__ __forceinline__ double ls_bwd(const double (&Lt)[
 // backward substitution instead of two full solves).
 // FR: the normal-force reference of this node is fnr (the solve's force_ref,
 // prefetched with ref) instead of C.fn_ref[NC - 1]; unused otherwise.
-template <int NC, bool ROW, bool FR = false>
-__device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, const LaneK& K, int mode, bool surface, double q,
+// CW: the scalar cost weights are W's (this lane's block of the instance's
+// row) instead of C's; W is unused otherwise.  On a joint lane the EE terms
+// (and on the EE lane the joint terms) are then formed with the other role's
+// entries and discarded, as they are discarded without CW.
+template <int NC, bool ROW, bool FR = false, bool CW = false>
+__device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, const LaneK& K, const LsW& W, int mode, bool surface, double q,
                                              double v, double u, double xq, double xv, double tr, const double* ref,
                                              double fnr, double& qn, double& vn, double& cpart, double (&lam)[3]
 #ifdef FFDDP_PHASE_PROF
@@ -362,6 +378,9 @@ __device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, co
   }
   PP(2);
   // ---- costs that do not depend on the dynamics (group-uniform operands) ----
+  // a scalar cost weight at its use: this lane's block entry (CW) or C's
+  auto we = [&](int i, double c) { return CW ? W.w[i] : c; };                    // EE lane's block
+  auto wj = [&](int i, double c) { return CW ? W.w[i - FFDDP_CW_JOINT0] : c; };  // joint lanes' block
   double cee;  // EE cost except the contact-force terms (uniform in the group)
   {
     double Rrel[9], rr[3];
@@ -372,33 +391,34 @@ __device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, co
         Rrel[3 * a_ + b_] = ls_dot3(C.Rdes[0 * 3 + a_], Ree[0 * 3 + b_], C.Rdes[1 * 3 + a_], Ree[1 * 3 + b_],
                                     C.Rdes[2 * 3 + a_], Ree[2 * 3 + b_]);
     ls_log3(Rrel, rr);
-    cee = C.w_ori * (0.5 * ls_dot3(C.ori_w[0] * rr[0], rr[0], C.ori_w[1] * rr[1], rr[1], C.ori_w[2] * rr[2], rr[2]));
-    cee = fma(C.w_wd, 0.5 * ls_dot3(C.wd_w[0] * wee[0], wee[0], C.wd_w[1] * wee[1], wee[1], C.wd_w[2] * wee[2], wee[2]),
+    cee = we(FFDDP_CW_EE_ORI, C.w_ori) * (0.5 * ls_dot3(C.ori_w[0] * rr[0], rr[0], C.ori_w[1] * rr[1], rr[1], C.ori_w[2] * rr[2], rr[2]));
+    cee = fma(we(FFDDP_CW_WDAMP, C.w_wd), 0.5 * ls_dot3(C.wd_w[0] * wee[0], wee[0], C.wd_w[1] * wee[1], wee[1], C.wd_w[2] * wee[2], wee[2]),
               cee);
     const double rx = pee[0] - ref[0], ry = pee[1] - ref[1], rz = pee[2] - ref[2];
     const double cfree =
-        C.w_ee_pos * (0.5 * ls_dot3(C.ee_pos_w[0] * rx, rx, C.ee_pos_w[1] * ry, ry, C.ee_pos_w[2] * rz, rz));
+        we(FFDDP_CW_EE_POS, C.w_ee_pos) * (0.5 * ls_dot3(C.ee_pos_w[0] * rx, rx, C.ee_pos_w[1] * ry, ry, C.ee_pos_w[2] * rz, rz));
     const double vx = vp[0] - ref[3], vy = vp[1] - ref[4];
-    double ccon = fma(C.w_tv, 0.5 * fma(vy, vy, vx * vx), C.w_tp * (0.5 * fma(ry, ry, rx * rx)));
+    double ccon = fma(we(FFDDP_CW_TANGENT_VEL, C.w_tv), 0.5 * fma(vy, vy, vx * vx),
+                      we(FFDDP_CW_TANGENT_POS, C.w_tp) * (0.5 * fma(ry, ry, rx * rx)));
     if (fl & RF_PZ) {
       const double pz = pee[2] - (ref[2] - C.z_press);
-      ccon = fma(C.w_pz, 0.5 * (pz * pz), ccon);
+      ccon = fma(we(FFDDP_CW_PLANE_Z, C.w_pz), 0.5 * (pz * pz), ccon);
     }
-    if (fl & RF_VZ) ccon = fma(C.w_vz, 0.5 * (vp[2] * vp[2]), ccon);
+    if (fl & RF_VZ) ccon = fma(we(FFDDP_CW_VZ, C.w_vz), 0.5 * (vp[2] * vp[2]), ccon);
     cee += surface ? ccon : cfree;
   }
   double cj = 0.0;  // this joint's state / control costs
   if (J) {
     if (fl & RF_STATE) {
       const double rq = q - xq, rv = v - xv;
-      cj = C.w_post * (0.5 * fma(rv, rv, rq * rq));
-      cj = fma(C.w_v, 0.5 * ((K.vdw * v) * v), cj);
+      cj = wj(FFDDP_CW_POSTURE, C.w_post) * (0.5 * fma(rv, rv, rq * rq));
+      cj = fma(wj(FFDDP_CW_V, C.w_v), 0.5 * ((K.vdw * v) * v), cj);
     }
-    if (fl & RF_QSOFT) cj = fma(C.w_qs, ls_barrier(q - K.qsx, K.qslb, K.qsub), cj);
+    if (fl & RF_QSOFT) cj = fma(wj(FFDDP_CW_Q_SOFT_LIMITS, C.w_qs), ls_barrier(q - K.qsx, K.qslb, K.qsub), cj);
     if (!terminal && (fl & RF_TAU)) {
       const double r = u - tr;
-      cj = fma(C.w_tau, 0.5 * (r * r), cj);
-      if (fl & RF_TSOFT) cj = fma(C.w_ts, ls_barrier(u, K.tslb, K.tsub), cj);
+      cj = fma(wj(FFDDP_CW_TAU, C.w_tau), 0.5 * (r * r), cj);
+      if (fl & RF_TSOFT) cj = fma(wj(FFDDP_CW_TAU_SOFT_LIMITS, C.w_ts), ls_barrier(u, K.tslb, K.tsub), cj);
     }
   }
   lam[0] = lam[1] = lam[2] = 0.0;
@@ -616,16 +636,16 @@ __device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, co
     if (mode != MODE_TERMINAL_X)
 #pragma unroll
       for (int r = 0; r < NC; ++r) lm[r] = lam[r];
-    if (NC == 3 && (fl & RF_FC)) cf += ls_friction_cone(C, lm);
+    if (NC == 3 && (fl & RF_FC)) cf += ls_friction_cone<CW>(C, W, lm);
     if (fl & RF_UNI) {
 #pragma unroll
-      for (int r = 0; r < NC; ++r) cf = fma(C.w_uni, ls_barrier(lm[r], C.uni_lb[r], C.uni_ub[r]), cf);
+      for (int r = 0; r < NC; ++r) cf = fma(we(FFDDP_CW_UNILATERAL, C.w_uni), ls_barrier(lm[r], C.uni_lb[r], C.uni_ub[r]), cf);
     }
     if (fl & RF_FN) {
 #pragma unroll
       for (int r = 0; r < NC; ++r) {
         const double e = lm[r] - ((FR && r == NC - 1) ? fnr : C.fn_ref[r]);
-        cf = fma(C.w_fn, 0.5 * ((C.fn_w[r] * e) * e), cf);
+        cf = fma(we(FFDDP_CW_FN, C.w_fn), 0.5 * ((C.fn_w[r] * e) * e), cf);
       }
     }
   }

@@ -66,6 +66,8 @@ SYMBOLS = (
     "ffddp_calc_diff_fref",
     "ffddp_fleet_force_refs_dev",
     "ffddp_fleet_metrics_fref_dev",
+    "ffddp_solve_batch_wts_dev",
+    "ffddp_calc_diff_wts",
 )
 PLANT_OBS = 69
 # FFDDP_PLANT_ROW_*: one instance's physics row (ffddp_plant_set_instance_params)
@@ -160,6 +162,17 @@ class FleetTasks(C.Structure):
 
     _fields_ = [("p_site_minus_frame", C.c_double * 3), ("t", C.c_double), ("rec", C.c_void_p)]
 
+
+# FFDDP_COST_W / FFDDP_CW_*: one instance's row of scalar cost weights (ffddp_solve_batch_wts_dev): the entry of
+# ffddp_ocp_config's w_<name> is COST_INDEX["w_<name>"]; entries 0..9 the frame / contact weights, 16..23 the
+# state / control / force-feedback ones, the rest padding (config.cost_weight_row builds a row)
+COST_W = 32
+COST_INDEX = {
+    "w_ee_ori": 0, "w_wdamp": 1, "w_ee_pos": 2, "w_tangent_pos": 3, "w_tangent_vel": 4, "w_plane_z": 5, "w_vz": 6,
+    "w_unilateral": 7, "w_fn": 8, "w_friction_cone": 9,
+    "w_posture": 16, "w_v": 17, "w_q_soft_limits": 18, "w_tau": 19, "w_tau_soft_limits": 20, "w_y": 21, "w_w": 22,
+    "w_w_soft_limits": 23,
+}
 
 FLEET_FORCE_W = 4  # FFDDP_FLEET_FORCE_W: doubles per force record, f0, f1, t_on, t_ramp (trajectory.force_records)
 
@@ -438,6 +451,11 @@ def load() -> C.CDLL:
     lib.ffddp_solve_batch_fref_dev.restype = C.c_int
     lib.ffddp_calc_diff_fref.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, up, dp, dp, dp] + [dp] * 10
     lib.ffddp_calc_diff_fref.restype = C.c_int
+    # ..., stats, active, force_ref, cost_w, stream
+    lib.ffddp_solve_batch_wts_dev.argtypes = dev_args[:-1] + [vp, vp, vp, vp]
+    lib.ffddp_solve_batch_wts_dev.restype = C.c_int
+    lib.ffddp_calc_diff_wts.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, up, dp, dp, dp, dp] + [dp] * 10
+    lib.ffddp_calc_diff_wts.restype = C.c_int
     lib.ffddp_frame_placement.argtypes = [C.POINTER(Robot), dp, dp, dp]
     lib.ffddp_frame_placement.restype = C.c_int
     lib.ffddp_gravity_torque.argtypes = [C.POINTER(Robot), C.c_int, dp, dp]

@@ -98,6 +98,54 @@ class OcpConfig:
         return c
 
 
+# the scalar cost weights a solve can take per instance (ffddp_solve_batch_wts_dev), in ffddp_ocp_config's order
+COST_WEIGHT_NAMES = (
+    "w_ee_pos", "w_ee_ori", "w_wdamp", "w_posture", "w_v", "w_tau", "w_tau_soft_limits", "w_q_soft_limits",
+    "w_tangent_pos", "w_tangent_vel", "w_plane_z", "w_vz", "w_unilateral", "w_fn", "w_friction_cone",
+    "w_w", "w_w_soft_limits", "w_y",
+)
+_FF_ONLY = ("w_w", "w_w_soft_limits", "w_y")
+
+
+def cost_weight_row(cfg, variant: str = None, **overrides) -> np.ndarray:
+    """(_abi.COST_W,) float64: the cost-weight row that repeats `cfg` (an
+    OcpConfig, or any configuration with the w_* fields) for a solve's
+    ``cost_weights``, with named overrides (``w_fn=40.0``).  variant
+    ("classical" | "ff", default cfg.variant): the classical solve has no
+    force-feedback terms, so w_w, w_w_soft_limits and w_y are 0 there as the
+    library takes them.  Which terms exist is the handle's configuration:
+    an unknown name, a value that is not finite and >= 0, and a positive
+    override of a term the configuration does not build (weight 0 there, the
+    force-feedback weights of a classical solve, w_friction_cone without
+    point3d) raise ValueError."""
+    variant = str(getattr(cfg, "variant", "classical") if variant is None else variant).strip().lower()
+    if variant not in ("classical", "ff"):
+        raise ValueError(f"cost_weight_row: unknown variant {variant!r}")
+    nc3 = str(getattr(cfg, "contact_model", "normal_1d")).strip().lower() in ("point3d", "3d", "rigid3d", "route_a_3d")
+
+    def base(name):
+        if name in _FF_ONLY and variant != "ff":
+            return 0.0
+        if name == "w_friction_cone" and not nc3:
+            return 0.0
+        return max(float(getattr(cfg, name, 0.0)), 0.0)
+
+    row = np.zeros(_abi.COST_W)
+    for name in COST_WEIGHT_NAMES:
+        row[_abi.COST_INDEX[name]] = base(name)
+    for name, val in overrides.items():
+        if name not in _abi.COST_INDEX:
+            raise ValueError(f"cost_weight_row: unknown cost weight {name!r} (one of {', '.join(COST_WEIGHT_NAMES)})")
+        val = float(val)
+        if not (np.isfinite(val) and val >= 0.0):
+            raise ValueError(f"cost_weight_row: {name} must be finite and >= 0, not {val!r}")
+        if val > 0.0 and not base(name) > 0.0:
+            raise ValueError(f"cost_weight_row: {name} = {val!r}, but the configuration does not build that term "
+                             "(its weight there is 0)")
+        row[_abi.COST_INDEX[name]] = val
+    return row
+
+
 def classical_preset(horizon: int = 30, contact_model: str = "normal_1d") -> OcpConfig:
     """run_classical.py:269-315 (benchmark mode).  The reference preset uses N=36; BASELINE uses 30 (R9)."""
     return OcpConfig(variant="classical", horizon=horizon, contact_model=contact_model)

@@ -50,7 +50,7 @@ import numpy as np
 
 from . import _abi
 from . import robot as R
-from .config import OcpConfig
+from .config import COST_WEIGHT_NAMES, OcpConfig
 from .controller import (_OCP_FIELDS, _quat_wxyz_to_R, classical_benchmark_config, ff_benchmark_config,
                          ff_filter_alpha)
 from .plant import JOINT_DAMPING, BatchedPlant, PandaTablePlant, PlantPhysics, plant_rows
@@ -596,6 +596,40 @@ def _inject_profile(ucfgs, dt: float):
     return delay, sigma
 
 
+def check_weight_spread(weight_spread) -> dict:
+    """run_sweep's weight_spread, checked: {name: (lo, hi)} with names from
+    config.COST_WEIGHT_NAMES and finite 0 < lo <= hi (ValueError otherwise), as
+    floats in the names' sorted order."""
+    if not isinstance(weight_spread, dict) or not weight_spread:
+        raise ValueError(f"run_sweep: weight_spread is a dict {{name: (lo, hi)}}, not {weight_spread!r}")
+    out = {}
+    for name in sorted(weight_spread):
+        if name not in COST_WEIGHT_NAMES:
+            raise ValueError(f"run_sweep: weight_spread: unknown cost weight {name!r} "
+                             f"(one of {', '.join(COST_WEIGHT_NAMES)})")
+        rng_ = tuple(float(x) for x in np.atleast_1d(weight_spread[name]))
+        if len(rng_) != 2 or not all(np.isfinite(rng_)) or not 0.0 < rng_[0] <= rng_[1]:
+            raise ValueError(f"run_sweep: weight_spread[{name!r}] is (lo, hi), 0 < lo <= hi, not {weight_spread[name]!r}")
+        out[name] = rng_
+    return out
+
+
+def sweep_cost_weights(seed, weight_spread: dict) -> dict:
+    """The sweep's per-instance cost weights: {name: (B,) values}, instance b's
+    value of `name` lo (hi / lo)^((1 + u) / 2) with u = one uniform in [-1, 1]
+    per name, in the names' sorted order, from default_rng([seed_b, 5]) -- a
+    generator of its own, so no other draw of the sweep moves."""
+    spread = check_weight_spread(weight_spread)
+    names = list(spread)
+    out = {name: np.zeros(len(seed)) for name in names}
+    for b, s_ in enumerate(seed):
+        u = np.random.default_rng([int(s_), 5]).uniform(-1.0, 1.0, len(names))
+        for i, name in enumerate(names):
+            lo_, hi_ = spread[name]
+            out[name][b] = lo_ * (hi_ / lo_) ** (0.5 * (1.0 + u[i]))
+    return out
+
+
 def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilted_15", "actuation_uncertainty"),
               seeds: int = 256, total_time: float = 4.0, rank: int = 0, world: int = 1, device: int = 0,
               q_sigma: float = 0.02, verbose: bool = True, record: Sequence[int] = (),
@@ -606,7 +640,8 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
               device_summary: bool = False, keep_logs: bool = True,
               plant_spread: Optional[Tuple[float, float]] = None,
               uncertainty_spread: Optional[Tuple[float, int]] = None,
-              force_spread: Optional[Tuple[float, float]] = None, force_ramp: Optional[float] = None) -> dict:
+              force_spread: Optional[Tuple[float, float]] = None, force_ramp: Optional[float] = None,
+              weight_spread: Optional[dict] = None) -> dict:
     """Closed-loop sweep of len(scenarios) * seeds instances; this rank runs
     its contiguous shard.  Returns per-instance summary arrays (this shard).
     record: shard-local instance indices whose controller inputs (the plant
@@ -682,7 +717,16 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     T = 0 or None: f1 from the start.  The summary's ``avg_abs_force_err`` is
     then against each instance's own reference at every sample, from the logs
     and from the device accumulators alike, and ``force_rec`` (B, 4) carries
-    the profiles (f0, f1, t_on, t_ramp)."""
+    the profiles (f0, f1, t_on, t_ramp).
+    weight_spread (with device_loop only, NotImplementedError otherwise: the
+    host fleets solve with the configuration's weights): the controller's own
+    tuning per instance (DeviceFleetLoop(cost_weights=...)).  weight_spread =
+    {name: (lo, hi), ...}, names from config.COST_WEIGHT_NAMES, 0 < lo <= hi:
+    instance b's value of `name` is lo (hi / lo)^((1 + u) / 2), log-uniform,
+    with one u uniform in [-1, 1] per name, in the names' sorted order, from
+    default_rng([seed_b, 5]) (sweep_cost_weights; the other draws do not
+    move).  The summary carries ``weights`` ({name: (B,) drawn values}) and
+    ``cost_rows`` (B, COST_W), the rows the solves took."""
     variant = str(variant).strip().lower()
     if variant not in ("classical", "ff"):
         raise ValueError(f"run_sweep: unknown variant {variant!r}")
@@ -725,6 +769,11 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
         if not device_loop:
             raise NotImplementedError("run_sweep: force_spread and force_ramp need device_loop=True "
                                       "(the host fleets track the configuration's fn_des)")
+    if weight_spread is not None:
+        weight_spread = check_weight_spread(weight_spread)
+        if not device_loop:
+            raise NotImplementedError("run_sweep: weight_spread needs device_loop=True "
+                                      "(the host fleets solve with the configuration's weights)")
     device_refs = bool(device_refs) or task_spread is not None or stagger > 0
     if device_refs and not device_loop:
         raise NotImplementedError("run_sweep: device_refs, task_spread and stagger need device_loop=True "
@@ -798,7 +847,8 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
                                 neg_step_rule, device, t_cp, verbose, ucfgs, device_noise, solve_period,
                                 command_filter, tasks, device_summary, keep_logs, physics,
                                 allow_plant_fail=plant_spread is not None or uncertainty_spread is not None,
-                                force_profiles=profiles)
+                                force_profiles=profiles,
+                                weights=sweep_cost_weights(seed, weight_spread) if weight_spread else None)
         out.update(names=names, seed=seed, shard=(lo, hi), n_all=n_all)
         return out
     plant = BatchedPlant(B, timestep=0.001, n_substeps=5, device=device, physics=physics)
@@ -940,7 +990,7 @@ DEVICE_MEMORY: dict = {}  # the last device-loop sweep's memory figures (tools/s
 def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, total_time, neg_step_rule, device, t_cp,
                       verbose, ucfgs=None, noise=None, solve_period=1, command_filter=False, tasks=None,
                       device_summary=False, keep_logs=True, plant_physics=None, allow_plant_fail=False,
-                      force_profiles=None) -> dict:
+                      force_profiles=None, weights=None) -> dict:
     """run_sweep's loop on the device (fleet_loop.DeviceFleetLoop) and the
     host path's summary from the downloaded logs.  tasks: per-instance
     FleetTasks in place of traj; the summary's reference position and its
@@ -949,7 +999,9 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     keep_logs=False: the loop keeps no per-tick logs.  plant_physics: one
     PlantPhysics per instance (None: the scene's constants).  force_profiles:
     one ForceProfile (or None) per instance; the force error is then against
-    each instance's own reference at the sample's series time."""
+    each instance's own reference at the sample's series time.  weights:
+    {name: (B,) values} (sweep_cost_weights), each instance's own cost weights
+    over the configuration's."""
     import torch
 
     from .fleet_loop import DeviceFleetLoop
@@ -967,7 +1019,9 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
                            noise=noise or "numpy", solve_period=int(solve_period), tasks=tasks,
                            metrics=bool(device_summary), logs=bool(keep_logs),
                            t_contact_phase=float(t_cp) if device_summary and tasks is None else None,
-                           plant_physics=plant_physics, force_profiles=force_profiles)
+                           plant_physics=plant_physics, force_profiles=force_profiles,
+                           cost_weights=None if weights is None else
+                           [{name: float(v[b]) for name, v in weights.items()} for b in range(B)])
     wall0 = time.perf_counter()
     loop.run(steps)
     torch.cuda.synchronize(loop.dev)
@@ -995,6 +1049,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
         out.update(_mismatch_outputs(loop, r, ucfgs, B, allow_plant_fail))
         if "force_rec" in r:
             out["force_rec"] = r["force_rec"]
+        if weights is not None:
+            out.update(weights=weights, cost_rows=r["cost_rows"])
         if tasks is not None and keep_logs:
             out.update(solved=r["solved"], surface=r["surface"] != 0)
         return out
@@ -1033,6 +1089,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     out.update(_mismatch_outputs(loop, r, ucfgs, B, allow_plant_fail))
     if "force_rec" in r:
         out["force_rec"] = r["force_rec"]
+    if weights is not None:
+        out.update(weights=weights, cost_rows=r["cost_rows"])
     if tasks is not None:
         out.update(solved=r["solved"], surface=r["surface"] != 0)  # (ticks, B): the per-tick solve share
     return out

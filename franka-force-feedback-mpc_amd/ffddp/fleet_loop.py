@@ -78,6 +78,14 @@ A None entry is the constant ``fn_des``.  The sampler is a function of the
 tick's time, so ``state`` / ``load_state`` carry nothing for it.  Without the
 argument (or with every entry None) the loop enqueues exactly the calls it did.
 
+With ``cost_weights`` every instance solves with its own scalar cost weights
+(ffddp_solve_batch_wts_dev): a (B, COST_W) array of rows, or one dict of named
+overrides (or None) per instance over the row that repeats the configuration
+(config.cost_weight_row).  The rows are uploaded once and every tick's solve
+takes them, whatever else the loop runs; there is no launch more per tick and
+``state`` / ``load_state`` carry nothing for them.  Without the argument the
+loop enqueues exactly the calls it did.
+
 Not on the device, and so not supported here: ``run_sweep``'s ``record`` and
 any per-tick host callback; ``tick()`` lets a caller look between ticks at the price of its own
 synchronisation.
@@ -90,6 +98,7 @@ import numpy as np
 
 from . import _abi
 from . import robot as R
+from .config import cost_weight_row
 from .controller import ff_filter_alpha
 from .fleet import Traj, fleet_ocp_config, node_ref, site_calibration
 from .trajectory import FleetTask, ForceProfile, force_records, task_records
@@ -170,6 +179,25 @@ def resolve_solve_period(cfg, solve_period: Optional[int]) -> int:
     return P
 
 
+def cost_weight_rows(ocp, variant: str, cost_weights, B: int) -> np.ndarray:
+    """DeviceFleetLoop's ``cost_weights`` as (B, _abi.COST_W) float64 rows: an
+    array is checked (shape, finite, >= 0) and copied; a sequence holds one
+    dict of named overrides, or None, per instance over the row that repeats
+    the OCP configuration `ocp` (config.cost_weight_row, whose errors apply)."""
+    if isinstance(cost_weights, np.ndarray) or (hasattr(cost_weights, "shape") and not isinstance(cost_weights, (list, tuple))):
+        rows = np.array(cost_weights, dtype=np.float64)
+        if rows.shape != (int(B), _abi.COST_W):
+            raise ValueError(f"DeviceFleetLoop: cost_weights must have shape (B, {_abi.COST_W}), not {rows.shape}")
+        if not (np.all(np.isfinite(rows)) and np.all(rows >= 0.0)):
+            raise ValueError("DeviceFleetLoop: cost_weights must be finite and >= 0")
+        return np.ascontiguousarray(rows)
+    entries = list(cost_weights)
+    if len(entries) != int(B) or not all(e is None or isinstance(e, dict) for e in entries):
+        raise ValueError("DeviceFleetLoop: cost_weights takes a (B, COST_W) array, or one entry (a dict of overrides "
+                         "or None) per instance")
+    return np.stack([cost_weight_row(ocp, variant, **(e or {})) for e in entries])
+
+
 class DeviceFleetLoop:
     """B closed loops (plant + controller) resident on one device.
 
@@ -206,6 +234,10 @@ class DeviceFleetLoop:
     normal force over each instance's task time (the tick's time minus the
     task's delay), sampled per tick and knot on the device (``force_ref``
     (B, N+1), the solve's argument; ``force_rec`` the records).
+    cost_weights: None, a (B, _abi.COST_W) array of cost-weight rows, or one
+    entry per instance, a dict of overrides for config.cost_weight_row
+    (``{"w_fn": 40.0}``) or None (the configuration's weights); ``cost_rows``
+    (B, COST_W) keeps the rows as uploaded.
 
     ``S``: the controller state, ``T``: the solve's arrays, ``P``: the plant's
     (q, v, obs, tau_app, tau_filt, plane), ``J``: the injector's (row, a, b,
@@ -221,7 +253,7 @@ class DeviceFleetLoop:
                  max_table_bytes: int = 1 << 30, solve_period: Optional[int] = None,
                  tasks: Optional[Sequence[FleetTask]] = None, metrics: bool = False, logs: bool = True,
                  t_contact_phase=None, plant_physics=None,
-                 force_profiles: Optional[Sequence[Optional[ForceProfile]]] = None):
+                 force_profiles: Optional[Sequence[Optional[ForceProfile]]] = None, cost_weights=None):
         variant = str(variant).strip().lower()
         if variant not in ("classical", "ff"):
             raise ValueError(f"DeviceFleetLoop: unknown variant {variant!r}")
@@ -361,6 +393,11 @@ class DeviceFleetLoop:
             self.frec = up(self.force_rec)
             self.force_ref = z(B, N + 1)
             self.ftasks = self.ktasks if self.ktasks is not None else _abi.FleetTasks()
+        # per-instance cost weights (ffddp_solve_batch_wts_dev): the rows, uploaded once
+        self.cost_rows = self.cw = None
+        if cost_weights is not None:
+            self.cost_rows = cost_weight_rows(self.solver.cfg, variant, cost_weights, B)
+            self.cw = up(self.cost_rows)
         self.log_info = torch.full((rows, B, _abi.FLEET_INFO_W), float("nan"), **f64)
         self.log_obs = torch.full((rows + 1 if logs else 1, B, _abi.FLEET_LOG_W), float("nan"), **f64)
         self.log_fail = z(rows + 1, B, dtype=torch.int32)  # without logs: the start's row and the ticks'
@@ -496,16 +533,18 @@ class DeviceFleetLoop:
         if self.frec is not None:
             self.ftasks.t = self._tick_time(k)
             fkw = dict(force_ref=self.force_ref)
+        if self.cw is not None:
+            fkw = dict(fkw, cost_weights=self.cw)
         if self.sched is None:
             self.solver.fleet_pre_dev(T, self.params, hint, stream=self._stream, tasks=self.ktasks)
-            if fkw:
+            if self.frec is not None:
                 self._force_refs()
             self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream, **fkw)
             self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream)
         else:
             T["need"] = self.log_need[r]
             self.solver.fleet_pre_dev(T, self.params, hint, stream=self._stream, sched=self.sched, tasks=self.ktasks)
-            if fkw:
+            if self.frec is not None:
                 self._force_refs()
             self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream,
                                   active=T["need"], **fkw)
@@ -625,6 +664,8 @@ class DeviceFleetLoop:
                 out.update(inject_delay=self.inject_delay.copy(), inject_sigma=self.inject_sigma.copy())
             if self.force_rec is not None:
                 out["force_rec"] = self.force_rec.copy()
+            if self.cost_rows is not None:
+                out["cost_rows"] = self.cost_rows.copy()
             return out
         info = self.log_info[:k].cpu().numpy()
         out = dict(info=info, obs=self.log_obs[: k + 1].cpu().numpy(), t=self.times[:k].copy(),
@@ -640,6 +681,8 @@ class DeviceFleetLoop:
             out["t_task"] = self.times[:k, None] - self.task_delay[None, :]
         if self.force_rec is not None:
             out["force_rec"] = self.force_rec.copy()
+        if self.cost_rows is not None:
+            out["cost_rows"] = self.cost_rows.copy()
         if self.metrics:
             out.update(m)
         return out

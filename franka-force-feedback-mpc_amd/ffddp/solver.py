@@ -284,7 +284,8 @@ class BatchedBoxFDDP:
         return plan
 
     # -- solve (device-resident torch tensors; bench path) ---------------------------
-    def solve_dev(self, t, maxiter: int = 10, is_feasible: bool = False, stream=None, active=None, force_ref=None):
+    def solve_dev(self, t, maxiter: int = 10, is_feasible: bool = False, stream=None, active=None, force_ref=None,
+                  cost_weights=None):
         """t: dict of contiguous torch.cuda tensors with keys x0, node_ref, inst_ref,
         surface (uint8), xs_init, us_init and outputs xs, us, K, cost, iters (int32),
         ok (uint8), fn_pred, stats (int32).  Asynchronous on `stream` (hipStream_t int).
@@ -294,7 +295,11 @@ class BatchedBoxFDDP:
         force_ref: optional (B, N+1) float64 device tensor, the desired normal
         contact force of every instance and node in place of the
         configuration's fn_des (ffddp_solve_batch_fref_dev); goes with or
-        without `active`."""
+        without `active`.
+        cost_weights: optional (B, _abi.COST_W) float64 device tensor, one row of
+        scalar cost weights per instance in place of the configuration's
+        (ffddp_solve_batch_wts_dev; config.cost_weight_row builds a row); goes
+        with or without `active` and `force_ref`."""
         B = int(t["x0"].shape[0])
         p = lambda k: C.c_void_p(int(t[k].data_ptr()))
         if active is not None:
@@ -309,6 +314,23 @@ class BatchedBoxFDDP:
             if (not isinstance(force_ref, torch.Tensor) or force_ref.dtype != torch.float64 or not force_ref.is_cuda
                     or not force_ref.is_contiguous() or tuple(force_ref.shape) != (B, self.N + 1)):
                 raise ValueError("force_ref must be a contiguous (B, N+1) float64 device tensor")
+        if cost_weights is not None:
+            import torch
+
+            w = cost_weights
+            if (not isinstance(w, torch.Tensor) or w.dtype != torch.float64 or not w.is_cuda or not w.is_contiguous()
+                    or tuple(w.shape) != (B, _abi.COST_W)):
+                raise ValueError("cost_weights must be a contiguous (B, COST_W) float64 device tensor")
+            rc = self._lib.ffddp_solve_batch_wts_dev(
+                self._h, B, p("x0"), p("node_ref"), p("inst_ref"), p("surface"), p("xs_init"), p("us_init"),
+                int(maxiter), int(bool(is_feasible)), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
+                p("fn_pred"), p("stats"), C.c_void_p(int(active.data_ptr()) if active is not None else 0),
+                C.c_void_p(int(force_ref.data_ptr()) if force_ref is not None else 0), C.c_void_p(int(w.data_ptr())),
+                C.c_void_p(stream if stream else 0),
+            )
+            self._check(rc, "ffddp_solve_batch_wts_dev")
+            return
+        if force_ref is not None:
             rc = self._lib.ffddp_solve_batch_fref_dev(
                 self._h, B, p("x0"), p("node_ref"), p("inst_ref"), p("surface"), p("xs_init"), p("us_init"),
                 int(maxiter), int(bool(is_feasible)), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
@@ -678,9 +700,11 @@ class BatchedBoxFDDP:
         return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(_abi.KERNEL_CLASSES)}
 
     # -- problem.calcDiff(xs, us) -------------------------------------------------------
-    def calc_diff(self, batch, xs, us, force_ref=None):
+    def calc_diff(self, batch, xs, us, force_ref=None, cost_weights=None):
         """force_ref: optional (B, N+1) host array, the desired normal contact
-        force per instance and node (ffddp_calc_diff_fref)."""
+        force per instance and node (ffddp_calc_diff_fref).  cost_weights:
+        optional (B, _abi.COST_W) host array, the scalar cost weights per
+        instance (ffddp_calc_diff_wts)."""
         B = int(batch.x0.shape[0])
         N, nx = self.N, self.nx
         f = lambda a, shape: np.ascontiguousarray(np.asarray(a, np.float64).reshape(shape))
@@ -691,11 +715,27 @@ class BatchedBoxFDDP:
             lam=np.zeros((B, N + 1, 3)),
         )
         d = _abi.dptr
+        fr = None
         if force_ref is not None:
             fr = np.asarray(force_ref, np.float64)
             if fr.shape != (B, N + 1):
                 raise ValueError("force_ref must have shape (B, N+1)")
             fr = np.ascontiguousarray(fr)
+        if cost_weights is not None:
+            cw = np.asarray(cost_weights, np.float64)
+            if cw.shape != (B, _abi.COST_W):
+                raise ValueError("cost_weights must have shape (B, COST_W)")
+            cw = np.ascontiguousarray(cw)
+            rc = self._lib.ffddp_calc_diff_wts(
+                self._h, B, d(f(batch.x0, (B, nx))), d(f(batch.node_ref, (B, N + 1, 6))),
+                d(f(batch.inst_ref, (B, 21))), _abi.uptr(np.ascontiguousarray(np.asarray(batch.surface, np.uint8))),
+                d(f(xs, (B, N + 1, nx))), d(f(us, (B, N, 7))), d(fr) if fr is not None else None, d(cw), d(out["Fx"]),
+                d(out["Fu"]), d(out["Lx"]), d(out["Lu"]), d(out["Lxx"]), d(out["Lxu"]), d(out["Luu"]), d(out["cost"]),
+                d(out["xnext"]), d(out["lam"]),
+            )
+            self._check(rc, "ffddp_calc_diff_wts")
+            return out
+        if fr is not None:
             rc = self._lib.ffddp_calc_diff_fref(
                 self._h, B, d(f(batch.x0, (B, nx))), d(f(batch.node_ref, (B, N + 1, 6))),
                 d(f(batch.inst_ref, (B, 21))), _abi.uptr(np.ascontiguousarray(np.asarray(batch.surface, np.uint8))),

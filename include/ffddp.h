@@ -220,6 +220,63 @@ int ffddp_solve_batch_fref_dev(ffddp_handle* h, int B, const double* x0, const d
                                double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
                                const uint8_t* active, const double* force_ref, void* stream);
 
+/* ffddp_solve_batch_fref_dev with the scalar cost weights per instance:
+ * cost_w is [B][FFDDP_COST_W] device doubles, row b the weights of instance b,
+ * one named entry per scalar cost weight of ffddp_ocp_config (FFDDP_CW_<NAME>
+ * is the entry of w_<name>).  A row is 32 doubles (256 bytes), so with cost_w
+ * on a 128-byte boundary every row starts on one and each of its two blocks
+ * lies in one 128-byte line: entries 0..9 are the frame and contact weights
+ * (read by a node's end-effector lane), entries FFDDP_CW_JOINT0.. the state,
+ * control and force-feedback weights (read by its joint lanes); the remaining
+ * entries are padding, which the library may load and never uses.
+ *
+ * Which terms exist stays the handle's: a row entry replaces the weight of a
+ * term the configuration builds (weight > 0 there, and the free-space /
+ * contact split, use_inner_state_reg / use_inner_tau_reg, nc as before); the
+ * entry of a term it does not build never enters the arithmetic (the node
+ * stage does not load it; the line search loads each block whole and ignores
+ * it), so any value there, NaN included, changes nothing.  An entry of
+ * 0 for an existing term is legal: the term contributes zeros.  Entries must
+ * be finite and >= 0; the rows are device memory, which the library cannot
+ * check.  The weight vectors (ori_weights, v_damp_weights, y_weights, ...),
+ * the activation bounds and margins, fn_des (per node through force_ref), the
+ * contact gains, tau_limits and the solver constants stay the handle's.
+ *
+ * Only the source of each weight changes, not the order or grouping of the
+ * arithmetic, and the terminal node uses the same row: rows that repeat the
+ * handle's configuration give the bits of the call without cost_w.  Rows of
+ * unselected instances are not read (NaN there is harmless).  `active` and
+ * force_ref stay optional and combine freely with cost_w (without a
+ * force_ref the solve reads an array of fn_des the handle keeps, allocated
+ * by the first such call).  cost_w == NULL is ffddp_solve_batch_fref_dev:
+ * same kernels, same bits.  Errors are ffddp_solve_batch_fref_dev's.  The
+ * host-pointer entry point and solve plans take no cost weights. */
+#define FFDDP_COST_W 32
+#define FFDDP_CW_EE_ORI 0
+#define FFDDP_CW_WDAMP 1
+#define FFDDP_CW_EE_POS 2
+#define FFDDP_CW_TANGENT_POS 3
+#define FFDDP_CW_TANGENT_VEL 4
+#define FFDDP_CW_PLANE_Z 5
+#define FFDDP_CW_VZ 6
+#define FFDDP_CW_UNILATERAL 7
+#define FFDDP_CW_FN 8
+#define FFDDP_CW_FRICTION_CONE 9
+#define FFDDP_CW_JOINT0 16 /* first entry of the joint lanes' block */
+#define FFDDP_CW_POSTURE 16
+#define FFDDP_CW_V 17
+#define FFDDP_CW_Q_SOFT_LIMITS 18
+#define FFDDP_CW_TAU 19
+#define FFDDP_CW_TAU_SOFT_LIMITS 20
+#define FFDDP_CW_Y 21
+#define FFDDP_CW_W 22
+#define FFDDP_CW_W_SOFT_LIMITS 23
+int ffddp_solve_batch_wts_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                              const double* inst_ref, const uint8_t* surface, const double* xs_init,
+                              const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
+                              double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
+                              const uint8_t* active, const double* force_ref, const double* cost_w, void* stream);
+
 /* Solve plan for a receding-horizon loop: one solve of a fixed batch per
  * control tick (crocoddyl_classical.py:367 called every tick at
  * run_classical.py:412).  ffddp_plan_create captures the whole host-array
@@ -279,6 +336,14 @@ int ffddp_calc_diff_fref(ffddp_handle* h, int B, const double* x0, const double*
                          const double* us, const double* force_ref, double* Fx, double* Fu, double* Lx,
                          double* Lu, double* Lxx, double* Lxu, double* Luu, double* cost, double* xnext,
                          double* lam);
+
+/* ffddp_calc_diff_fref with host cost-weight rows [B][FFDDP_COST_W]
+ * (ffddp_solve_batch_wts_dev's array; NULL: ffddp_calc_diff_fref). */
+int ffddp_calc_diff_wts(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                        const double* inst_ref, const uint8_t* surface, const double* xs,
+                        const double* us, const double* force_ref, const double* cost_w, double* Fx,
+                        double* Fu, double* Lx, double* Lu, double* Lxx, double* Lxu, double* Luu,
+                        double* cost, double* xnext, double* lam);
 
 /* Host-side setup helpers (CPU, same model code): frame placement of the EE
  * (pin.forwardKinematics + updateFramePlacements, crocoddyl_classical.py:199-225)

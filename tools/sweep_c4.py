@@ -24,6 +24,8 @@ wall time, closed-loop ticks/s).
                                                                # delays vary per instance (host path too)
   python tools/sweep_c4.py --device-loop 1 --device-refs 1 --force-spread 8 36 --force-ramp 0.5
                                                                # a force setpoint per instance, ramped in after touchdown
+  python tools/sweep_c4.py --device-loop 1 --device-refs 1 --weight-spread w_fn 7 112 --weight-spread w_tau 2e-4 3.2e-3
+                                                               # the controller's cost weights per instance, log-uniform
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/sweep_c4.py
 """
 import argparse
@@ -42,7 +44,19 @@ import ffddp_path  # noqa: E402,F401
 ALL_SCENARIOS = ("flat", "tilted_5", "tilted_10", "tilted_15", "actuation_uncertainty")
 
 
-def main():
+def weight_spread_arg(items):
+    """--weight-spread NAME LO HI, repeatable -> run_sweep's {name: (lo, hi)} (None without the option)."""
+    if not items:
+        return None
+    out = {}
+    for name, lo, hi in items:
+        if name in out:
+            raise ValueError(f"--weight-spread: {name} given twice")
+        out[name] = (float(lo), float(hi))
+    return out
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seeds", type=int, default=256)
     ap.add_argument("--time", type=float, default=4.0)
@@ -85,8 +99,20 @@ def main():
     ap.add_argument("--force-ramp", type=float, default=None, metavar="T",
                     help="with --force-spread: the reference ramps from F_LO to the setpoint over T seconds from the end "
                          "of the contact hold (0: the setpoint from the start)")
+    ap.add_argument("--weight-spread", nargs=3, action="append", default=None, metavar=("NAME", "LO", "HI"),
+                    help="with --device-loop 1, repeatable: cost weight NAME (w_fn, w_tangent_pos, w_tau, ...) per "
+                         "instance, log-uniform in [LO, HI]")
     ap.add_argument("--scenarios", nargs="+", default=list(ALL_SCENARIOS), help="scenarios to sweep (default: all 5)")
+    return ap
+
+
+def main():
+    ap = build_parser()
     a = ap.parse_args()
+    try:
+        wspread = weight_spread_arg(a.weight_spread)
+    except ValueError as e:
+        ap.error(str(e))
     import torch
     import torch.distributed as dist
     from ffddp import fleet, shard
@@ -109,7 +135,7 @@ def main():
                            device_refs=bool(a.device_refs), task_spread=a.task_spread, stagger=a.stagger,
                            device_summary=bool(a.device_summary), keep_logs=bool(a.keep_logs),
                            plant_spread=a.plant_spread, uncertainty_spread=uspread,
-                           force_spread=a.force_spread, force_ramp=a.force_ramp)
+                           force_spread=a.force_spread, force_ramp=a.force_ramp, weight_spread=wspread)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -152,6 +178,22 @@ def main():
                  "avg_abs_force_err": float(np.nanmean(pi["avg_abs_force_err"][which == i])),
                  "contact_loss_contact_phase_pct": float(np.nanmean(pi["contact_loss_contact_phase_pct"][which == i]))}
                 for i in range(4) if np.any(which == i)])
+        if "weights" in res:  # this rank's shard by each swept weight, four log-spaced bins
+            pi = res["per_instance"]
+            line["weight_spread"] = wspread
+            line["rank0_weight_bins"] = {}
+            for name, w in res["weights"].items():
+                edges = np.geomspace(wspread[name][0], wspread[name][1], 5)
+                which = np.clip(np.digitize(w, edges) - 1, 0, 3)
+                line["rank0_weight_bins"][name] = [
+                    {"weight_lo": float(edges[i]), "weight_hi": float(edges[i + 1]), "instances": int(np.sum(which == i)),
+                     "weight_mean": float(np.mean(w[which == i])),
+                     "fn_mean_contact_phase": float(np.nanmean(pi["fn_mean_contact_phase"][which == i])),
+                     "avg_abs_force_err": float(np.nanmean(pi["avg_abs_force_err"][which == i])),
+                     "rms_tangential_error_contact_phase":
+                         float(np.nanmean(pi["rms_tangential_error_contact_phase"][which == i])),
+                     "contact_loss_contact_phase_pct": float(np.nanmean(pi["contact_loss_contact_phase_pct"][which == i]))}
+                    for i in range(4) if np.any(which == i)]
         # instances that left the nominal regime, per scenario: any tick on the unstable fallback; a non-finite summary
         ui, ri = fleet.SUMMARY_KEYS.index("unstable_ticks"), fleet.SUMMARY_KEYS.index("rms_3d_error")
         line["diverged"] = {str(s): {"unstable_instances": int(np.sum(m[names == s, ui] > 0)),
