@@ -3248,12 +3248,26 @@ Dev dev_slice(const Dev& d0, int b0, int Bk, int k) {
   return d;
 }
 
-template <int NC, bool FF, bool FR = false, bool CW = false>
-int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref, const double* iref,
-                 const uint8_t* surf, const double* xs_init, const double* us_init, int maxiter, int is_feasible,
-                 double* xs, double* us, double* K, double* cost, int32_t* iters, uint8_t* ok, double* fn_pred,
-                 int32_t* stats, hipStream_t s, HostIO* io, const uint8_t* active, const double* fref = nullptr,
-                 const double* cw = nullptr) {
+// What a solve takes, in the C ABI's order (include/ffddp.h: ffddp_solve_batch_wts_dev): the host entry
+// point, the device entry points and the plan capture fill one and hand it down to launch_solve_t.
+struct SolveArgs {
+  int B;
+  const double *x0, *nref, *iref;
+  const uint8_t* surf;
+  const double *xs_init, *us_init;
+  int maxiter, is_feasible;
+  double *xs, *us, *K, *cost;
+  int32_t* iters;
+  uint8_t* ok;
+  double* fn_pred;
+  int32_t* stats;
+  const uint8_t* active;
+  const double *fref, *cw;
+};
+
+template <int NC, bool FF, bool FR, bool CW>
+int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* io) {
+  const int B = a.B, maxiter = a.maxiter;
   const int N = h->hc.N, nx = h->hc.nx;
   int S = h->nstreams;
   if (B < 64 * S) S = 1;
@@ -3286,12 +3300,12 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
   // buffers), so no copy of the solution follows the last kernel; the host
   // entry point keeps the handle's buffers (its outputs are host memory)
   Dev dbase = h->d;
-  dbase.fref = FR ? fref : nullptr;
-  dbase.cw = CW ? cw : nullptr;
+  dbase.fref = FR ? a.fref : nullptr;
+  dbase.cw = CW ? a.cw : nullptr;
   if (!io) {
-    dbase.xs = xs;
-    dbase.us = us;
-    dbase.K = K;
+    dbase.xs = a.xs;
+    dbase.us = a.us;
+    dbase.K = a.K;
   }
   for (int k = 0; k < S; ++k) {
     sl[k].b0 = k * Bs;
@@ -3327,12 +3341,12 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
   auto enqueue_init = [&](int k) {
     ProfScope p(h, sl[k].s, KC_INIT);
     const long b0 = sl[k].b0;
-    if (active)
+    if (a.active)
       hipLaunchKernelGGL(k_init<true>, dim3(1024), dim3(INIT_BLOCK), 0, sl[k].s, h->dc, sl[k].d,
-                         xs_init + b0 * N1 * nxl, us_init + b0 * (long)N * NU, is_feasible, active + b0);
+                         a.xs_init + b0 * N1 * nxl, a.us_init + b0 * (long)N * NU, a.is_feasible, a.active + b0);
     else
       hipLaunchKernelGGL(k_init<false>, dim3(1024), dim3(INIT_BLOCK), 0, sl[k].s, h->dc, sl[k].d,
-                         xs_init + b0 * N1 * nxl, us_init + b0 * (long)N * NU, is_feasible, nullptr);
+                         a.xs_init + b0 * N1 * nxl, a.us_init + b0 * (long)N * NU, a.is_feasible, nullptr);
   };
   // one FDDP iteration of slice k: node stage, backward pass, line search, step decision
   auto enqueue_iter = [&](int k, int it) -> int {
@@ -3340,10 +3354,10 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
     const hipStream_t ss = sl[k].s;
     const int Bk = sl[k].B;
     const long b0 = sl[k].b0;
-    const double* x0k = x0 + b0 * nxl;
-    const double* nrefk = nref + b0 * N1 * 6;
-    const double* irefk = iref + b0 * 21;
-    const uint8_t* surfk = surf + b0;
+    const double* x0k = a.x0 + b0 * nxl;
+    const double* nrefk = a.nref + b0 * N1 * 6;
+    const double* irefk = a.iref + b0 * 21;
+    const uint8_t* surfk = a.surf + b0;
     const long nodes = (long)Bk * (N + 1);
     // optional start stagger: slice k's first node stage waits for slice
     // k-1's, so the throughput-bound node stages do not all collide
@@ -3465,9 +3479,9 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
     {
       ProfScope p(h, ss, KC_FINALIZE);
       hipLaunchKernelGGL((k_finalize<NC, FF>), dim3((2 * Bk + 63) / 64), dim3(64), 0, ss, h->dc, d, maxiter,
-                         x0 + b0 * nxl, nref + b0 * N1 * 6, iref + b0 * 21, surf + b0, cost + b0, iters + b0, ok + b0,
-                         fn_pred ? fn_pred + 2 * b0 : nullptr, stats ? stats + b0 * FFDDP_NSTATS : nullptr,
-                         active ? active + b0 : nullptr);
+                         a.x0 + b0 * nxl, a.nref + b0 * N1 * 6, a.iref + b0 * 21, a.surf + b0, a.cost + b0, a.iters + b0,
+                         a.ok + b0, a.fn_pred ? a.fn_pred + 2 * b0 : nullptr,
+                         a.stats ? a.stats + b0 * FFDDP_NSTATS : nullptr, a.active ? a.active + b0 : nullptr);
     }
     // host entry point: page-locked host memory, the slice's results go
     // down as soon as it finishes (the device entry point solved in place)
@@ -3477,9 +3491,9 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
       io->dus[k] = d.us;
       io->dK[k] = d.K;
       if (!io->defer_out) {
-        HIPCHK(h, hipMemcpyAsync(xs + b0 * N1 * nxl, d.xs, bxs * Bk, hipMemcpyDefault, ss));
-        HIPCHK(h, hipMemcpyAsync(us + b0 * (long)N * NU, d.us, bus * Bk, hipMemcpyDefault, ss));
-        HIPCHK(h, hipMemcpyAsync(K + b0 * (long)N * NU * nx, d.K, bks * Bk, hipMemcpyDefault, ss));
+        HIPCHK(h, hipMemcpyAsync(a.xs + b0 * N1 * nxl, d.xs, bxs * Bk, hipMemcpyDefault, ss));
+        HIPCHK(h, hipMemcpyAsync(a.us + b0 * (long)N * NU, d.us, bus * Bk, hipMemcpyDefault, ss));
+        HIPCHK(h, hipMemcpyAsync(a.K + b0 * (long)N * NU * nx, d.K, bks * Bk, hipMemcpyDefault, ss));
       }
       for (int i = 0; i < io->n_out; ++i) {
         const size_t o = (size_t)b0 * io->out[i].per_inst;
@@ -3527,37 +3541,44 @@ int launch_solve_t(ffddp_handle* h, int B, const double* x0, const double* nref,
   return 0;
 }
 
-int launch_solve(ffddp_handle* h, int B, const double* x0, const double* nref, const double* iref,
-                 const uint8_t* surf, const double* xs_init, const double* us_init, int maxiter, int is_feasible,
-                 double* xs, double* us, double* K, double* cost, int32_t* iters, uint8_t* ok, double* fn_pred,
-                 int32_t* stats, hipStream_t s, HostIO* io = nullptr, const uint8_t* active = nullptr,
-                 const double* fref = nullptr, const double* cw = nullptr) {
+// The one (nc, variant, force reference, cost weights) -> template constants decision, for the solve and for
+// ffddp_calc_diff_wts: f(NC, FF, FR, CW) is called with std::integral_constant arguments.  fr: there is a force
+// reference; without one the kernels are the FR = false instantiations.  cw: there are cost-weight rows.  The CW
+// kernels exist with FR only (the caller supplies a force reference of fn_des where the user gave none: the same
+// bits), so the build does not double.
+template <class F> int dispatch_variant(ffddp_handle* h, bool fr, bool cw, F&& f) {
+  if (cw && !fr) return fail(h, FFDDP_E_INVALID, "cost weights without a force reference");
+  using NC1 = std::integral_constant<int, 1>;
+  using NC3 = std::integral_constant<int, 3>;
   const bool ff = h->hc.variant == FFDDP_FORCE_FEEDBACK;
-  const int nc = h->hc.nc;
-  // fref: the solve's force reference; without one the kernels are the FR = false instantiations, as before.
-  // cw: the solve's cost-weight rows.  The CW kernels exist with FR only (the caller supplies a
-  // force reference of fn_des where the user gave none: the same bits), so the build does not double.
-#define FFDDP_LS(NC_, FF_, FR_, CW_) \
-  launch_solve_t<NC_, FF_, FR_, CW_>(h, B, x0, nref, iref, surf, xs_init, us_init, maxiter, is_feasible, xs, us, K, cost, iters, ok, fn_pred, stats, s, io, active, fref, cw)
-  if (cw) {
-    if (!fref) return fail(h, FFDDP_E_INVALID, "cost weights without a force reference");
-    if (nc == 1) return ff ? FFDDP_LS(1, true, true, true) : FFDDP_LS(1, false, true, true);
-    return ff ? FFDDP_LS(3, true, true, true) : FFDDP_LS(3, false, true, true);
-  }
-  if (fref) {
-    if (nc == 1) return ff ? FFDDP_LS(1, true, true, false) : FFDDP_LS(1, false, true, false);
-    return ff ? FFDDP_LS(3, true, true, false) : FFDDP_LS(3, false, true, false);
-  }
-  if (nc == 1) return ff ? FFDDP_LS(1, true, false, false) : FFDDP_LS(1, false, false, false);
-  return ff ? FFDDP_LS(3, true, false, false) : FFDDP_LS(3, false, false, false);
-#undef FFDDP_LS
+  auto nc_ff = [&](auto FR, auto CW) -> int {
+    if (h->hc.nc == 1) return ff ? f(NC1{}, std::true_type{}, FR, CW) : f(NC1{}, std::false_type{}, FR, CW);
+    return ff ? f(NC3{}, std::true_type{}, FR, CW) : f(NC3{}, std::false_type{}, FR, CW);
+  };
+  if (cw) return nc_ff(std::true_type{}, std::true_type{});
+  if (fr) return nc_ff(std::true_type{}, std::false_type{});
+  return nc_ff(std::false_type{}, std::false_type{});
 }
 
-template <int NC, bool FF, bool FR = false, bool CW = false>
-void launch_node(ffddp_handle* h, Dev d, int B, hipStream_t s, int force_all) {
-  const long nodes = (long)B * (h->hc.N + 1);
-  hipLaunchKernelGGL((k_node<NC, FF, FR, CW>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, s, h->dc,
-                     d, h->in_x0, h->in_nref, h->in_iref, h->in_surf, force_all, 0);
+// io: the host entry point's copies (nullptr: the device entry points and the plan capture)
+int launch_solve(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* io) {
+  return dispatch_variant(h, a.fref != nullptr, a.cw != nullptr, [&](auto NC, auto FF, auto FR, auto CW) {
+    return launch_solve_t<decltype(NC)::value, decltype(FF)::value, decltype(FR)::value, decltype(CW)::value>(h, a, s, io);
+  });
+}
+
+// The one argument check of ffddp_solve_batch and ffddp_solve_batch_wts_dev.  B == 0 passes without a look at
+// the pointers: the caller returns 0 for it.
+int solve_args_check(ffddp_handle* h, const SolveArgs& a) {
+  if (!h) return FFDDP_E_INVALID;
+  if (a.fref && !(h->hc.w_fn > 0.0))
+    return fail(h, FFDDP_E_INVALID, "force_ref given but the handle has no fn_track cost (w_fn <= 0)");
+  if (a.B < 0 || a.maxiter < 0) return fail(h, FFDDP_E_INVALID, "negative B or maxiter");
+  if (a.B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  if (a.B > 0 && (!a.x0 || !a.nref || !a.iref || !a.surf || !a.xs_init || !a.us_init || !a.xs || !a.us || !a.K ||
+                  !a.cost || !a.iters || !a.ok))
+    return fail(h, FFDDP_E_INVALID, "null pointer");
+  return 0;
 }
 
 // Slice streams shared by every handle of the process on a device: a
@@ -3829,26 +3850,19 @@ int ffddp_solve_batch_wts_dev(ffddp_handle* h, int B, const double* x0, const do
                               const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
                               double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
                               const uint8_t* active, const double* force_ref, const double* cost_w, void* stream) {
-  if (!h) return FFDDP_E_INVALID;
-  if (force_ref && !(h->hc.w_fn > 0.0))
-    return fail(h, FFDDP_E_INVALID, "force_ref given but the handle has no fn_track cost (w_fn <= 0)");
-  if (B < 0 || maxiter < 0) return fail(h, FFDDP_E_INVALID, "negative B or maxiter");
-  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  SolveArgs a{B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs, us, K, cost, iters, ok,
+              fn_pred, stats, active, force_ref, cost_w};
+  if (int rc = solve_args_check(h, a)) return rc;
   if (B == 0) return 0;
-  if (!x0 || !node_ref || !inst_ref || !surface || !xs_init || !us_init || !xs || !us || !K || !cost || !iters || !ok)
-    return fail(h, FFDDP_E_INVALID, "null pointer");
   HIPCHK(h, hipSetDevice(h->device));
   // the handle's workspace is shared by every solve: a solve enqueued on
   // another (possibly non-blocking) stream must finish before this one starts
   if (h->last_done_set) HIPCHK(h, hipStreamWaitEvent((hipStream_t)stream, h->last_done, 0));
   if (cost_w && !force_ref) {
     if (int rc = const_force_ref(h)) return rc;
-    force_ref = h->fref_const;
+    a.fref = h->fref_const;
   }
-  const int rc = launch_solve(h, B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs, us,
-                              K, cost, iters, ok, fn_pred, stats, (hipStream_t)stream, nullptr, active, force_ref,
-                              cost_w);
-  if (rc) return rc;
+  if (int rc = launch_solve(h, a, (hipStream_t)stream, nullptr)) return rc;
   return mark_solve_done(h, (hipStream_t)stream);
 }
 
@@ -3892,12 +3906,11 @@ int ffddp_solve_batch(ffddp_handle* h, int B, const double* x0, const double* no
                       const uint8_t* surface, const double* xs_init, const double* us_init, int maxiter,
                       int is_feasible, double* xs, double* us, double* K, double* cost, int32_t* iters, uint8_t* ok,
                       double* fn_pred, int32_t* stats) {
-  if (!h) return FFDDP_E_INVALID;
-  if (B < 0 || maxiter < 0) return fail(h, FFDDP_E_INVALID, "negative B or maxiter");
-  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  // the caller's host arrays; no active mask, force reference or cost weights on this path
+  const SolveArgs user{B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs, us, K, cost,
+                       iters, ok, fn_pred, stats, nullptr, nullptr, nullptr};
+  if (int rc = solve_args_check(h, user)) return rc;
   if (B == 0) return 0;
-  if (!x0 || !node_ref || !inst_ref || !surface || !xs_init || !us_init || !xs || !us || !K || !cost || !iters || !ok)
-    return fail(h, FFDDP_E_INVALID, "null pointer");
   HIPCHK(h, hipSetDevice(h->device));
   const size_t N = (size_t)h->hc.N, nx = (size_t)h->hc.nx;
   // per-instance bytes: inputs x0, node_ref, inst_ref, surface, xs_init, us_init;
@@ -3989,10 +4002,11 @@ int ffddp_solve_batch(ffddp_handle* h, int B, const double* x0, const double* no
     const hipError_t e = hipStreamWaitEvent(cs, h->last_done, 0);
     if (e != hipSuccess) return fail(h, FFDDP_E_DEVICE, std::string("hipStreamWaitEvent: ") + hipGetErrorString(e));
   }
-  int rc = launch_solve(h, B, h->in_x0, h->in_nref, h->in_iref, h->in_surf, h->in_xs, h->in_us, maxiter, is_feasible,
-                        (double*)hout[0], (double*)hout[1], (double*)hout[2], h->out_cost, h->out_iters, h->out_ok,
-                        h->out_fn, h->out_stats, cs, &io);
-  if (rc) return drain_host_solve(h, rc);
+  // the solve itself works on the handle's device buffers; xs / us / K: where launch_solve_t copies them down to
+  const SolveArgs a{B, h->in_x0, h->in_nref, h->in_iref, h->in_surf, h->in_xs, h->in_us, maxiter, is_feasible,
+                    (double*)hout[0], (double*)hout[1], (double*)hout[2], h->out_cost, h->out_iters, h->out_ok,
+                    h->out_fn, h->out_stats, nullptr, nullptr, nullptr};
+  if (int rc = launch_solve(h, a, cs, &io)) return drain_host_solve(h, rc);
   const double t2 = tm ? now() : 0.0;
   // while the device solves: the first touch of the caller's pageable output
   // arrays (fresh numpy arrays are unmapped pages; faulting them in during
@@ -4183,16 +4197,17 @@ int ffddp_plan_create(ffddp_handle* h, int B, int maxiter, int is_feasible, ffdd
   h->prof = false;
   char* di = p->din;
   char* dq = p->dout;
+  const SolveArgs a{B, (const double*)(di + L.x0), (const double*)(di + L.nref), (const double*)(di + L.iref),
+                    (const uint8_t*)(di + L.surf), (const double*)(di + L.xs_init), (const double*)(di + L.us_init),
+                    maxiter, is_feasible, (double*)(dq + L.xs), (double*)(dq + L.us), (double*)(dq + L.K),
+                    (double*)(dq + L.cost), (int32_t*)(dq + L.iters), (uint8_t*)(dq + L.ok), (double*)(dq + L.fn),
+                    (int32_t*)(dq + L.stats), nullptr, nullptr, nullptr};
   int rc = 0;
   hipError_t e = hipStreamBeginCapture(p->s, hipStreamCaptureModeThreadLocal);
   if (e == hipSuccess) {
     e = hipMemcpyAsync(p->din, p->hin, L.in_bytes, hipMemcpyHostToDevice, p->s);
     if (e == hipSuccess)
-      rc = launch_solve(h, B, (const double*)(di + L.x0), (const double*)(di + L.nref), (const double*)(di + L.iref),
-                        (const uint8_t*)(di + L.surf), (const double*)(di + L.xs_init),
-                        (const double*)(di + L.us_init), maxiter, is_feasible, (double*)(dq + L.xs),
-                        (double*)(dq + L.us), (double*)(dq + L.K), (double*)(dq + L.cost), (int32_t*)(dq + L.iters),
-                        (uint8_t*)(dq + L.ok), (double*)(dq + L.fn), (int32_t*)(dq + L.stats), p->s);
+      rc = launch_solve(h, a, p->s, nullptr);
     if (e == hipSuccess && rc == 0) e = hipMemcpyAsync(p->hout, p->dout, L.out_bytes, hipMemcpyDeviceToHost, p->s);
     hipGraph_t g = nullptr;
     const hipError_t e2 = hipStreamEndCapture(p->s, &g);
@@ -4414,20 +4429,14 @@ int ffddp_calc_diff_wts(ffddp_handle* h, int B, const double* x0, const double* 
   HIPCHK(h, hipMemcpy(h->in_us, us, (size_t)B * N * NU * 8, hipMemcpyHostToDevice));
   // node kernel reads (xs, us) from the solver state: initialise it from the inputs
   hipLaunchKernelGGL(k_init<false>, dim3(1024), dim3(INIT_BLOCK), 0, nullptr, h->dc, d, h->in_xs, h->in_us, 0, nullptr);
-  if (cost_w) {
-    if (h->hc.nc == 1)
-      ff ? launch_node<1, true, true, true>(h, d, B, nullptr, 1) : launch_node<1, false, true, true>(h, d, B, nullptr, 1);
-    else
-      ff ? launch_node<3, true, true, true>(h, d, B, nullptr, 1) : launch_node<3, false, true, true>(h, d, B, nullptr, 1);
-  } else if (force_ref) {
-    if (h->hc.nc == 1)
-      ff ? launch_node<1, true, true>(h, d, B, nullptr, 1) : launch_node<1, false, true>(h, d, B, nullptr, 1);
-    else
-      ff ? launch_node<3, true, true>(h, d, B, nullptr, 1) : launch_node<3, false, true>(h, d, B, nullptr, 1);
-  } else if (h->hc.nc == 1)
-    ff ? launch_node<1, true>(h, d, B, nullptr, 1) : launch_node<1, false>(h, d, B, nullptr, 1);
-  else
-    ff ? launch_node<3, true>(h, d, B, nullptr, 1) : launch_node<3, false>(h, d, B, nullptr, 1);
+  const int rc = dispatch_variant(h, d.fref != nullptr, d.cw != nullptr, [&](auto NC, auto FF, auto FR, auto CW) {
+    const long nodes = (long)B * (N + 1);
+    hipLaunchKernelGGL((k_node<decltype(NC)::value, decltype(FF)::value, decltype(FR)::value, decltype(CW)::value>),
+                       dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, nullptr, h->dc, d, h->in_x0,
+                       h->in_nref, h->in_iref, h->in_surf, 1, 0);
+    return 0;
+  });
+  if (rc) return rc;
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipDeviceSynchronize());
   std::vector<double> rec((size_t)B * (N + 1) * R), fsv((size_t)B * (N + 1) * nx);
@@ -4572,26 +4581,92 @@ static bool fleet_state_complete(const ffddp_fleet_state* s) {
   return s->valid && s->latched && s->loss_count && s->prev_mode && s->tau_prev && s->keep_xs && s->keep_us && s->keep_K;
 }
 
+static int fleet_sched_check(ffddp_handle* h, const ffddp_fleet_sched& c, const std::string& who) {
+  if (!c.since || !c.age || !c.need) return fail(h, FFDDP_E_INVALID, who + ": null pointer");
+  if (c.period < 1) return fail(h, FFDDP_E_INVALID, who + ": period must be at least 1");
+  if (c.apply_filter && !(c.tau_smoothing_alpha >= 0.0 && c.tau_smoothing_alpha <= 1.0))
+    return fail(h, FFDDP_E_INVALID, who + ": tau_smoothing_alpha outside [0, 1]");
+  return 0;
+}
+
+// The body of ffddp_fleet_pre_dev, _pre_sched_dev and _pre_task_dev; `name`: the entry point called, for the
+// messages.  sched: the scheduled tick (the SCHED instantiations).  tasks: per-instance tasks (the TASK
+// instantiations) in place of node_ref1 / contact_hint.
+static int fleet_pre(ffddp_handle* h, const char* name, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                     const double* q, const double* v, const double* fn_meas, const double* contact,
+                     const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
+                     const double* q_nom, const double* node_ref1, int contact_hint, double* x0, uint8_t* surface,
+                     double* inst_ref, double* node_ref, double* xs_init, double* us_init,
+                     const ffddp_fleet_sched* sched, const ffddp_fleet_tasks* tasks, void* stream) {
+  if (!h) return FFDDP_E_INVALID;
+  const std::string who(name);
+  if (B <= 0) return fail(h, FFDDP_E_INVALID, who + ": B must be positive");
+  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  const bool ff = h->hc.nx == 21;
+  if (!p || !s || !fleet_state_complete(s) || !q || !v || !fn_meas || !ee_z || (ff && !tau_hat) || !q_nom ||
+      (tasks ? !tasks->rec : !node_ref1) || !x0 || !surface || !inst_ref || !node_ref || !xs_init || !us_init)
+    return fail(h, FFDDP_E_INVALID, who + ": null pointer");
+  if (ld_qv < NQ || ld_scalar < 1 || (ff && ld_tau_hat < NU) || p->phase_source < 0 || p->phase_source > 1 || p->torque_mode < 0 ||
+      p->torque_mode > 2 || p->posture_mode < 0 || p->posture_mode > 1)
+    return fail(h, FFDDP_E_INVALID, who + ": bad stride or mode");
+  if (sched)
+    if (const int rc = fleet_sched_check(h, *sched, who)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  const auto kern = sched ? (tasks ? k_fleet_pre<true, true> : k_fleet_pre<true, false>)
+                          : (tasks ? k_fleet_pre<false, true> : k_fleet_pre<false, false>);
+  hipLaunchKernelGGL(kern, dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx, *p, *s,
+                     sched ? *sched : ffddp_fleet_sched{}, q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar,
+                     tau_hat, (long)ld_tau_hat, q_nom, node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init,
+                     us_init, tasks ? *tasks : ffddp_fleet_tasks{}, tasks ? h->hc.dt : 0.0);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 int ffddp_fleet_pre_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
                         const double* q, const double* v, const double* fn_meas, const double* contact,
                         const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
                         const double* q_nom,
                         const double* node_ref1, int contact_hint, double* x0, uint8_t* surface, double* inst_ref,
                         double* node_ref, double* xs_init, double* us_init, void* stream) {
+  return fleet_pre(h, "ffddp_fleet_pre_dev", B, p, s, q, v, fn_meas, contact, ee_z, ld_qv, ld_scalar, tau_hat, ld_tau_hat,
+                   q_nom, node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init, nullptr, nullptr,
+                   stream);
+}
+
+int ffddp_fleet_pre_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                              const double* q, const double* v, const double* fn_meas, const double* contact,
+                              const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
+                              const double* q_nom, const double* node_ref1, int contact_hint, double* x0,
+                              uint8_t* surface, double* inst_ref, double* node_ref, double* xs_init, double* us_init,
+                              ffddp_fleet_sched sched, void* stream) {
+  return fleet_pre(h, "ffddp_fleet_pre_sched_dev", B, p, s, q, v, fn_meas, contact, ee_z, ld_qv, ld_scalar, tau_hat,
+                   ld_tau_hat, q_nom, node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init, &sched,
+                   nullptr, stream);
+}
+
+// The body of ffddp_fleet_post_dev and _post_sched_dev (sched: the scheduled tick, the SCHED instantiation)
+static int fleet_post(ffddp_handle* h, const char* name, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                      const double* xs, const double* us, const double* K, const double* cost, const int32_t* iters,
+                      const uint8_t* ok, const double* fn_pred, const int32_t* stats, const double* x0,
+                      const uint8_t* surface, const double* tau_bias, int ld_tau_bias, double* tau_cmd, double* info,
+                      const double* scale, double* tau_app, double* tau_filt, double lpf, const double* obs,
+                      int ld_obs, double* log_obs, const ffddp_fleet_sched* sched, void* stream) {
   if (!h) return FFDDP_E_INVALID;
-  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_dev: B must be positive");
+  const std::string who(name);
+  if (B <= 0) return fail(h, FFDDP_E_INVALID, who + ": B must be positive");
   if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
-  const bool ff = h->hc.nx == 21;
-  if (!p || !s || !fleet_state_complete(s) || !q || !v || !fn_meas || !ee_z || (ff && !tau_hat) || !q_nom ||
-      !node_ref1 || !x0 || !surface || !inst_ref || !node_ref || !xs_init || !us_init)
-    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_dev: null pointer");
-  if (ld_qv < NQ || ld_scalar < 1 || (ff && ld_tau_hat < NU) || p->phase_source < 0 || p->phase_source > 1 || p->torque_mode < 0 ||
-      p->torque_mode > 2 || p->posture_mode < 0 || p->posture_mode > 1)
-    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_dev: bad stride or mode");
+  if (!p || !s || !fleet_state_complete(s) || !xs || !us || !K || !cost || !iters || !ok || !fn_pred || !stats ||
+      !x0 || !surface || !tau_bias || !tau_cmd || !info)
+    return fail(h, FFDDP_E_INVALID, who + ": null pointer");
+  if (ld_tau_bias < NU || (log_obs && (!obs || ld_obs < FFDDP_PLANT_OBS)) || (tau_filt && !tau_app))
+    return fail(h, FFDDP_E_INVALID, who + ": bad stride or optional arguments");
+  if (sched)
+    if (const int rc = fleet_sched_check(h, *sched, who)) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL((k_fleet_pre<false, false>), dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx, *p, *s,
-                     ffddp_fleet_sched{}, q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar, tau_hat, (long)ld_tau_hat, q_nom, node_ref1,
-                     contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init, ffddp_fleet_tasks{}, 0.0);
+  hipLaunchKernelGGL(sched ? k_fleet_post<true> : k_fleet_post<false>, dim3(B, FLEET_CHUNKS), dim3(FLEET_BLOCK), 0,
+                     (hipStream_t)stream, h->hc.N, h->hc.nx, *p, *s, sched ? *sched : ffddp_fleet_sched{}, xs, us, K, cost,
+                     iters, ok, fn_pred, stats, x0, surface, tau_bias, (long)ld_tau_bias, tau_cmd, info, scale, tau_app,
+                     tau_filt, lpf, obs, (long)ld_obs, log_obs);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -4602,54 +4677,8 @@ int ffddp_fleet_post_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, co
                          const double* x0, const uint8_t* surface, const double* tau_bias, int ld_tau_bias,
                          double* tau_cmd, double* info, const double* scale, double* tau_app, double* tau_filt,
                          double lpf, const double* obs, int ld_obs, double* log_obs, void* stream) {
-  if (!h) return FFDDP_E_INVALID;
-  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_post_dev: B must be positive");
-  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
-  if (!p || !s || !fleet_state_complete(s) || !xs || !us || !K || !cost || !iters || !ok || !fn_pred || !stats ||
-      !x0 || !surface || !tau_bias || !tau_cmd || !info)
-    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_post_dev: null pointer");
-  if (ld_tau_bias < NU || (log_obs && (!obs || ld_obs < FFDDP_PLANT_OBS)) || (tau_filt && !tau_app))
-    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_post_dev: bad stride or optional arguments");
-  HIPCHK(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(k_fleet_post<false>, dim3(B, FLEET_CHUNKS), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->hc.N, h->hc.nx,
-                     *p, *s, ffddp_fleet_sched{}, xs, us, K, cost, iters, ok, fn_pred, stats, x0, surface, tau_bias, (long)ld_tau_bias,
-                     tau_cmd, info, scale, tau_app, tau_filt, lpf, obs, (long)ld_obs, log_obs);
-  HIPCHK(h, hipGetLastError());
-  return 0;
-}
-
-// the scheduled tick: the same checks, then the SCHED instantiations
-static int fleet_sched_check(ffddp_handle* h, const ffddp_fleet_sched& c, const char* who) {
-  if (!c.since || !c.age || !c.need) return fail(h, FFDDP_E_INVALID, std::string(who) + ": null pointer");
-  if (c.period < 1) return fail(h, FFDDP_E_INVALID, std::string(who) + ": period must be at least 1");
-  if (c.apply_filter && !(c.tau_smoothing_alpha >= 0.0 && c.tau_smoothing_alpha <= 1.0))
-    return fail(h, FFDDP_E_INVALID, std::string(who) + ": tau_smoothing_alpha outside [0, 1]");
-  return 0;
-}
-
-int ffddp_fleet_pre_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
-                              const double* q, const double* v, const double* fn_meas, const double* contact,
-                              const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
-                              const double* q_nom, const double* node_ref1, int contact_hint, double* x0,
-                              uint8_t* surface, double* inst_ref, double* node_ref, double* xs_init, double* us_init,
-                              ffddp_fleet_sched sched, void* stream) {
-  if (!h) return FFDDP_E_INVALID;
-  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_sched_dev: B must be positive");
-  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
-  const bool ff = h->hc.nx == 21;
-  if (!p || !s || !fleet_state_complete(s) || !q || !v || !fn_meas || !ee_z || (ff && !tau_hat) || !q_nom ||
-      !node_ref1 || !x0 || !surface || !inst_ref || !node_ref || !xs_init || !us_init)
-    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_sched_dev: null pointer");
-  if (ld_qv < NQ || ld_scalar < 1 || (ff && ld_tau_hat < NU) || p->phase_source < 0 || p->phase_source > 1 || p->torque_mode < 0 ||
-      p->torque_mode > 2 || p->posture_mode < 0 || p->posture_mode > 1)
-    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_sched_dev: bad stride or mode");
-  if (const int rc = fleet_sched_check(h, sched, "ffddp_fleet_pre_sched_dev")) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL((k_fleet_pre<true, false>), dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx, *p, *s,
-                     sched, q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar, tau_hat, (long)ld_tau_hat, q_nom,
-                     node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init, ffddp_fleet_tasks{}, 0.0);
-  HIPCHK(h, hipGetLastError());
-  return 0;
+  return fleet_post(h, "ffddp_fleet_post_dev", B, p, s, xs, us, K, cost, iters, ok, fn_pred, stats, x0, surface, tau_bias,
+                    ld_tau_bias, tau_cmd, info, scale, tau_app, tau_filt, lpf, obs, ld_obs, log_obs, nullptr, stream);
 }
 
 int ffddp_fleet_post_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
@@ -4659,21 +4688,9 @@ int ffddp_fleet_post_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params*
                                double* tau_cmd, double* info, const double* scale, double* tau_app, double* tau_filt,
                                double lpf, const double* obs, int ld_obs, double* log_obs, ffddp_fleet_sched sched,
                                void* stream) {
-  if (!h) return FFDDP_E_INVALID;
-  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_post_sched_dev: B must be positive");
-  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
-  if (!p || !s || !fleet_state_complete(s) || !xs || !us || !K || !cost || !iters || !ok || !fn_pred || !stats ||
-      !x0 || !surface || !tau_bias || !tau_cmd || !info)
-    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_post_sched_dev: null pointer");
-  if (ld_tau_bias < NU || (log_obs && (!obs || ld_obs < FFDDP_PLANT_OBS)) || (tau_filt && !tau_app))
-    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_post_sched_dev: bad stride or optional arguments");
-  if (const int rc = fleet_sched_check(h, sched, "ffddp_fleet_post_sched_dev")) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(k_fleet_post<true>, dim3(B, FLEET_CHUNKS), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->hc.N, h->hc.nx,
-                     *p, *s, sched, xs, us, K, cost, iters, ok, fn_pred, stats, x0, surface, tau_bias, (long)ld_tau_bias,
-                     tau_cmd, info, scale, tau_app, tau_filt, lpf, obs, (long)ld_obs, log_obs);
-  HIPCHK(h, hipGetLastError());
-  return 0;
+  return fleet_post(h, "ffddp_fleet_post_sched_dev", B, p, s, xs, us, K, cost, iters, ok, fn_pred, stats, x0, surface,
+                    tau_bias, ld_tau_bias, tau_cmd, info, scale, tau_app, tau_filt, lpf, obs, ld_obs, log_obs, &sched,
+                    stream);
 }
 
 // per-instance tasks (ffddp_task.hpp): the sampler alone, and pre with it in place of node_ref1 / contact_hint
@@ -4713,30 +4730,8 @@ int ffddp_fleet_pre_task_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p
                              const double* q_nom, ffddp_fleet_tasks tasks, double* x0, uint8_t* surface,
                              double* inst_ref, double* node_ref, double* xs_init, double* us_init,
                              const ffddp_fleet_sched* sched, void* stream) {
-  if (!h) return FFDDP_E_INVALID;
-  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_task_dev: B must be positive");
-  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
-  const bool ff = h->hc.nx == 21;
-  if (!p || !s || !fleet_state_complete(s) || !q || !v || !fn_meas || !ee_z || (ff && !tau_hat) || !q_nom ||
-      !tasks.rec || !x0 || !surface || !inst_ref || !node_ref || !xs_init || !us_init)
-    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_task_dev: null pointer");
-  if (ld_qv < NQ || ld_scalar < 1 || (ff && ld_tau_hat < NU) || p->phase_source < 0 || p->phase_source > 1 || p->torque_mode < 0 ||
-      p->torque_mode > 2 || p->posture_mode < 0 || p->posture_mode > 1)
-    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_pre_task_dev: bad stride or mode");
-  if (sched)
-    if (const int rc = fleet_sched_check(h, *sched, "ffddp_fleet_pre_task_dev")) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  if (sched)
-    hipLaunchKernelGGL((k_fleet_pre<true, true>), dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx,
-                       *p, *s, *sched, q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar, tau_hat, (long)ld_tau_hat,
-                       q_nom, (const double*)nullptr, 0, x0, surface, inst_ref, node_ref, xs_init, us_init, tasks, h->hc.dt);
-  else
-    hipLaunchKernelGGL((k_fleet_pre<false, true>), dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx,
-                       *p, *s, ffddp_fleet_sched{}, q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar, tau_hat,
-                       (long)ld_tau_hat, q_nom, (const double*)nullptr, 0, x0, surface, inst_ref, node_ref, xs_init, us_init, tasks,
-                       h->hc.dt);
-  HIPCHK(h, hipGetLastError());
-  return 0;
+  return fleet_pre(h, "ffddp_fleet_pre_task_dev", B, p, s, q, v, fn_meas, contact, ee_z, ld_qv, ld_scalar, tau_hat,
+                   ld_tau_hat, q_nom, nullptr, 0, x0, surface, inst_ref, node_ref, xs_init, us_init, sched, &tasks, stream);
 }
 
 // the sweep's task metrics (ffddp_metrics.hpp): one record per instance folded into acc [W][ld]
@@ -4791,33 +4786,57 @@ static int fleet_inject_check(ffddp_handle* h, int B, const ffddp_fleet_inject* 
   return 0;
 }
 
-int ffddp_fleet_inject_obs_dev(ffddp_handle* h, int B, const ffddp_fleet_inject* inj, int k, const double* z,
-                               const double* q, const double* v, int ld_qv, const double* tau_filt, double* qv_ctrl,
-                               double* tau_hat, double* tau_ctrl, void* stream) {
+// The body of ffddp_fleet_inject_obs_dev and _obs_rows_dev (`who`: the entry point called; rows: per-row delays
+// and sigmas, the ROWS instantiation)
+static int fleet_inject_obs(ffddp_handle* h, const char* who, int B, const ffddp_fleet_inject* inj, int k,
+                            const double* z, const double* q, const double* v, int ld_qv, const double* tau_filt,
+                            double* qv_ctrl, double* tau_hat, double* tau_ctrl, const ffddp_fleet_inject_rows* rows,
+                            void* stream) {
   if (!h) return FFDDP_E_INVALID;
-  if (int rc = fleet_inject_check(h, B, inj, k, "ffddp_fleet_inject_obs_dev")) return rc;
+  if (int rc = fleet_inject_check(h, B, inj, k, who)) return rc;
   if (!q || !v || !qv_ctrl || (inj->noise == FFDDP_INJECT_NOISE_TABLE ? (inj->rows > 0 && !z) : !inj->seed))
-    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_inject_obs_dev: null pointer");
-  if (ld_qv < NQ) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_inject_obs_dev: bad stride");
+    return fail(h, FFDDP_E_INVALID, std::string(who) + ": null pointer");
+  if (ld_qv < NQ) return fail(h, FFDDP_E_INVALID, std::string(who) + ": bad stride");
   HIPCHK(h, hipSetDevice(h->device));
   const int nb = (int)(((long)B * NU + INJECT_BLOCK - 1) / INJECT_BLOCK);
-  hipLaunchKernelGGL(k_fleet_inject_obs<false>, dim3(nb), dim3(INJECT_BLOCK), 0, (hipStream_t)stream, B, *inj, k, z, q, v,
-                     (long)ld_qv, tau_filt, qv_ctrl, tau_hat, tau_ctrl);
+  if (rows)
+    hipLaunchKernelGGL((k_fleet_inject_obs<true, ffddp_fleet_inject_rows>), dim3(nb), dim3(INJECT_BLOCK), 0,
+                       (hipStream_t)stream, B, *inj, k, z, q, v, (long)ld_qv, tau_filt, qv_ctrl, tau_hat, tau_ctrl, *rows);
+  else
+    hipLaunchKernelGGL(k_fleet_inject_obs<false>, dim3(nb), dim3(INJECT_BLOCK), 0, (hipStream_t)stream, B, *inj, k, z, q,
+                       v, (long)ld_qv, tau_filt, qv_ctrl, tau_hat, tau_ctrl);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
 
-int ffddp_fleet_inject_cmd_dev(ffddp_handle* h, int B, const ffddp_fleet_inject* inj, int k, const double* tau_cmd,
-                               double* tau_app, void* stream) {
+// The body of ffddp_fleet_inject_cmd_dev and _cmd_rows_dev
+static int fleet_inject_cmd(ffddp_handle* h, const char* who, int B, const ffddp_fleet_inject* inj, int k,
+                            const double* tau_cmd, double* tau_app, const ffddp_fleet_inject_rows* rows, void* stream) {
   if (!h) return FFDDP_E_INVALID;
-  if (int rc = fleet_inject_check(h, B, inj, k, "ffddp_fleet_inject_cmd_dev")) return rc;
-  if (!tau_cmd || !tau_app) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_inject_cmd_dev: null pointer");
+  if (int rc = fleet_inject_check(h, B, inj, k, who)) return rc;
+  if (!tau_cmd || !tau_app) return fail(h, FFDDP_E_INVALID, std::string(who) + ": null pointer");
   HIPCHK(h, hipSetDevice(h->device));
   const int nb = (int)(((long)B * NU + INJECT_BLOCK - 1) / INJECT_BLOCK);
-  hipLaunchKernelGGL(k_fleet_inject_cmd<false>, dim3(nb), dim3(INJECT_BLOCK), 0, (hipStream_t)stream, B, *inj, k, tau_cmd,
-                     tau_app);
+  if (rows)
+    hipLaunchKernelGGL((k_fleet_inject_cmd<true, ffddp_fleet_inject_rows>), dim3(nb), dim3(INJECT_BLOCK), 0,
+                       (hipStream_t)stream, B, *inj, k, tau_cmd, tau_app, *rows);
+  else
+    hipLaunchKernelGGL(k_fleet_inject_cmd<false>, dim3(nb), dim3(INJECT_BLOCK), 0, (hipStream_t)stream, B, *inj, k,
+                       tau_cmd, tau_app);
   HIPCHK(h, hipGetLastError());
   return 0;
+}
+
+int ffddp_fleet_inject_obs_dev(ffddp_handle* h, int B, const ffddp_fleet_inject* inj, int k, const double* z,
+                               const double* q, const double* v, int ld_qv, const double* tau_filt, double* qv_ctrl,
+                               double* tau_hat, double* tau_ctrl, void* stream) {
+  return fleet_inject_obs(h, "ffddp_fleet_inject_obs_dev", B, inj, k, z, q, v, ld_qv, tau_filt, qv_ctrl, tau_hat,
+                          tau_ctrl, nullptr, stream);
+}
+
+int ffddp_fleet_inject_cmd_dev(ffddp_handle* h, int B, const ffddp_fleet_inject* inj, int k, const double* tau_cmd,
+                               double* tau_app, void* stream) {
+  return fleet_inject_cmd(h, "ffddp_fleet_inject_cmd_dev", B, inj, k, tau_cmd, tau_app, nullptr, stream);
 }
 
 // the same two calls with per-row delays and sigmas; without any row array they are the calls above
@@ -4827,17 +4846,8 @@ int ffddp_fleet_inject_obs_rows_dev(ffddp_handle* h, int B, const ffddp_fleet_in
                                     const ffddp_fleet_inject_rows* rows, void* stream) {
   if (!rows || (!rows->d_obs && !rows->d_cmd && !rows->sigma))
     return ffddp_fleet_inject_obs_dev(h, B, inj, k, z, q, v, ld_qv, tau_filt, qv_ctrl, tau_hat, tau_ctrl, stream);
-  if (!h) return FFDDP_E_INVALID;
-  if (int rc = fleet_inject_check(h, B, inj, k, "ffddp_fleet_inject_obs_rows_dev")) return rc;
-  if (!q || !v || !qv_ctrl || (inj->noise == FFDDP_INJECT_NOISE_TABLE ? (inj->rows > 0 && !z) : !inj->seed))
-    return fail(h, FFDDP_E_INVALID, "ffddp_fleet_inject_obs_rows_dev: null pointer");
-  if (ld_qv < NQ) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_inject_obs_rows_dev: bad stride");
-  HIPCHK(h, hipSetDevice(h->device));
-  const int nb = (int)(((long)B * NU + INJECT_BLOCK - 1) / INJECT_BLOCK);
-  hipLaunchKernelGGL((k_fleet_inject_obs<true, ffddp_fleet_inject_rows>), dim3(nb), dim3(INJECT_BLOCK), 0,
-                     (hipStream_t)stream, B, *inj, k, z, q, v, (long)ld_qv, tau_filt, qv_ctrl, tau_hat, tau_ctrl, *rows);
-  HIPCHK(h, hipGetLastError());
-  return 0;
+  return fleet_inject_obs(h, "ffddp_fleet_inject_obs_rows_dev", B, inj, k, z, q, v, ld_qv, tau_filt, qv_ctrl, tau_hat,
+                          tau_ctrl, rows, stream);
 }
 
 int ffddp_fleet_inject_cmd_rows_dev(ffddp_handle* h, int B, const ffddp_fleet_inject* inj, int k,
@@ -4845,15 +4855,7 @@ int ffddp_fleet_inject_cmd_rows_dev(ffddp_handle* h, int B, const ffddp_fleet_in
                                     void* stream) {
   if (!rows || (!rows->d_obs && !rows->d_cmd && !rows->sigma))
     return ffddp_fleet_inject_cmd_dev(h, B, inj, k, tau_cmd, tau_app, stream);
-  if (!h) return FFDDP_E_INVALID;
-  if (int rc = fleet_inject_check(h, B, inj, k, "ffddp_fleet_inject_cmd_rows_dev")) return rc;
-  if (!tau_cmd || !tau_app) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_inject_cmd_rows_dev: null pointer");
-  HIPCHK(h, hipSetDevice(h->device));
-  const int nb = (int)(((long)B * NU + INJECT_BLOCK - 1) / INJECT_BLOCK);
-  hipLaunchKernelGGL((k_fleet_inject_cmd<true, ffddp_fleet_inject_rows>), dim3(nb), dim3(INJECT_BLOCK), 0,
-                     (hipStream_t)stream, B, *inj, k, tau_cmd, tau_app, *rows);
-  HIPCHK(h, hipGetLastError());
-  return 0;
+  return fleet_inject_cmd(h, "ffddp_fleet_inject_cmd_rows_dev", B, inj, k, tau_cmd, tau_app, rows, stream);
 }
 
 int ffddp_fleet_noise_dev(ffddp_handle* h, int B, const uint64_t* seed, int k, double* z, uint64_t* words,

@@ -34,6 +34,20 @@ _PARAMS = ("th_stop", "th_grad", "th_acceptstep", "th_acceptnegstep", "th_stepde
            "reg_max", "reg_incfactor", "reg_decfactor", "neg_step_rule")
 
 
+def _opt_dev_ptr(a, dtype: str, shape, what: str) -> C.c_void_p:
+    """The device pointer of an optional solve_dev argument, null for None;
+    ValueError(what) unless it is a contiguous device tensor of that torch
+    dtype and shape."""
+    if a is None:
+        return C.c_void_p(0)
+    import torch
+
+    if (not isinstance(a, torch.Tensor) or a.dtype != getattr(torch, dtype) or not a.is_cuda
+            or not a.is_contiguous() or tuple(a.shape) != shape):
+        raise ValueError(what)
+    return C.c_void_p(int(a.data_ptr()))
+
+
 class _RecycledPinned:
     """Page-locked host blocks (ffddp_host_alloc) for solve()'s output arrays,
     recycled instead of freed: every solve() returns fresh arrays (no other
@@ -302,57 +316,18 @@ class BatchedBoxFDDP:
         with or without `active` and `force_ref`."""
         B = int(t["x0"].shape[0])
         p = lambda k: C.c_void_p(int(t[k].data_ptr()))
-        if active is not None:
-            import torch
-
-            if (active.dtype != torch.uint8 or not active.is_cuda or not active.is_contiguous()
-                    or tuple(active.shape) != (B,)):
-                raise ValueError("active must be a contiguous (B,) uint8 device tensor")
-        if force_ref is not None:
-            import torch
-
-            if (not isinstance(force_ref, torch.Tensor) or force_ref.dtype != torch.float64 or not force_ref.is_cuda
-                    or not force_ref.is_contiguous() or tuple(force_ref.shape) != (B, self.N + 1)):
-                raise ValueError("force_ref must be a contiguous (B, N+1) float64 device tensor")
-        if cost_weights is not None:
-            import torch
-
-            w = cost_weights
-            if (not isinstance(w, torch.Tensor) or w.dtype != torch.float64 or not w.is_cuda or not w.is_contiguous()
-                    or tuple(w.shape) != (B, _abi.COST_W)):
-                raise ValueError("cost_weights must be a contiguous (B, COST_W) float64 device tensor")
-            rc = self._lib.ffddp_solve_batch_wts_dev(
-                self._h, B, p("x0"), p("node_ref"), p("inst_ref"), p("surface"), p("xs_init"), p("us_init"),
-                int(maxiter), int(bool(is_feasible)), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
-                p("fn_pred"), p("stats"), C.c_void_p(int(active.data_ptr()) if active is not None else 0),
-                C.c_void_p(int(force_ref.data_ptr()) if force_ref is not None else 0), C.c_void_p(int(w.data_ptr())),
-                C.c_void_p(stream if stream else 0),
-            )
-            self._check(rc, "ffddp_solve_batch_wts_dev")
-            return
-        if force_ref is not None:
-            rc = self._lib.ffddp_solve_batch_fref_dev(
-                self._h, B, p("x0"), p("node_ref"), p("inst_ref"), p("surface"), p("xs_init"), p("us_init"),
-                int(maxiter), int(bool(is_feasible)), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
-                p("fn_pred"), p("stats"), C.c_void_p(int(active.data_ptr()) if active is not None else 0),
-                C.c_void_p(int(force_ref.data_ptr())), C.c_void_p(stream if stream else 0),
-            )
-            self._check(rc, "ffddp_solve_batch_fref_dev")
-            return
-        if active is not None:
-            rc = self._lib.ffddp_solve_batch_sel_dev(
-                self._h, B, p("x0"), p("node_ref"), p("inst_ref"), p("surface"), p("xs_init"), p("us_init"),
-                int(maxiter), int(bool(is_feasible)), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
-                p("fn_pred"), p("stats"), C.c_void_p(int(active.data_ptr())), C.c_void_p(stream if stream else 0),
-            )
-            self._check(rc, "ffddp_solve_batch_sel_dev")
-            return
-        rc = self._lib.ffddp_solve_batch_dev(
+        rc = self._lib.ffddp_solve_batch_wts_dev(
             self._h, B, p("x0"), p("node_ref"), p("inst_ref"), p("surface"), p("xs_init"), p("us_init"),
             int(maxiter), int(bool(is_feasible)), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
-            p("fn_pred"), p("stats"), C.c_void_p(stream if stream else 0),
+            p("fn_pred"), p("stats"),
+            _opt_dev_ptr(active, "uint8", (B,), "active must be a contiguous (B,) uint8 device tensor"),
+            _opt_dev_ptr(force_ref, "float64", (B, self.N + 1),
+                         "force_ref must be a contiguous (B, N+1) float64 device tensor"),
+            _opt_dev_ptr(cost_weights, "float64", (B, _abi.COST_W),
+                         "cost_weights must be a contiguous (B, COST_W) float64 device tensor"),
+            C.c_void_p(stream if stream else 0),
         )
-        self._check(rc, "ffddp_solve_batch_dev")
+        self._check(rc, "ffddp_solve_batch_wts_dev")
 
     # -- fleet tick glue (include/ffddp.h: ffddp_fleet_warm_start_dev / ffddp_fleet_keep_dev) --
     def fleet_warm_start_dev(self, t, stream=None):
@@ -472,25 +447,18 @@ class BatchedBoxFDDP:
         assert plant_fail is None or (tuple(plant_fail.shape) == (B,) and plant_fail.is_contiguous())
         assert p_ref is None or (p_ref.numel() == 3 and p_ref.is_contiguous())
         p = lambda a: C.c_void_p(int(a.data_ptr()) if a is not None else 0)  # noqa: E731
+        rf = 0
         if force is not None:
             assert force.is_cuda and force.is_contiguous() and force.dim() == 2 and force.shape[1] == _abi.FLEET_FORCE_W
             assert str(force.dtype) == "torch.float64"
             rf = int(force.shape[0]) if rows_force is None else int(rows_force)
             assert rf <= int(force.shape[0])
-            rc = self._lib.ffddp_fleet_metrics_fref_dev(
-                self._h, B, int(acc.shape[1]), p(obs), int(obs.stride(0)),
-                tasks if tasks is not None else _abi.FleetTasks(), B if rows is None else int(rows), float(dt), p(p_ref),
-                float(ts), p(t_phase), float(fn_des), p(info), p(need), p(plant_fail), p(acc), p(force), rf,
-                C.c_void_p(stream if stream else 0),
-            )
-            self._check(rc, "ffddp_fleet_metrics_fref_dev")
-            return
-        rc = self._lib.ffddp_fleet_metrics_dev(
+        rc = self._lib.ffddp_fleet_metrics_fref_dev(
             self._h, B, int(acc.shape[1]), p(obs), int(obs.stride(0)), tasks if tasks is not None else _abi.FleetTasks(),
             B if rows is None else int(rows), float(dt), p(p_ref), float(ts), p(t_phase), float(fn_des), p(info),
-            p(need), p(plant_fail), p(acc), C.c_void_p(stream if stream else 0),
+            p(need), p(plant_fail), p(acc), p(force), rf, C.c_void_p(stream if stream else 0),
         )
-        self._check(rc, "ffddp_fleet_metrics_dev")
+        self._check(rc, "ffddp_fleet_metrics_fref_dev")
 
     def fleet_pre_dev(self, t, params: _abi.FleetParams, hint: bool = False, stream=None, sched: _abi.FleetSched = None,
                       tasks: _abi.FleetTasks = None):
@@ -626,12 +594,9 @@ class BatchedBoxFDDP:
         assert z is None or (z.is_contiguous() and tuple(z.shape) == (inj.rows, _abi.INJECT_NZ))
         args = (self._h, B, C.byref(inj), int(k), C.c_void_p(int(z.data_ptr()) if z is not None else 0), p("q"), p("v"),
                 int(t["q"].stride(0)), p("tau_filt"), p("qv_ctrl"), p("tau_hat"), p("tau_ctrl"))
-        if rows is not None:
-            rc = self._lib.ffddp_fleet_inject_obs_rows_dev(*args, C.byref(rows), C.c_void_p(stream if stream else 0))
-            self._check(rc, "ffddp_fleet_inject_obs_rows_dev")
-            return
-        rc = self._lib.ffddp_fleet_inject_obs_dev(*args, C.c_void_p(stream if stream else 0))
-        self._check(rc, "ffddp_fleet_inject_obs_dev")
+        rc = self._lib.ffddp_fleet_inject_obs_rows_dev(*args, C.byref(rows) if rows is not None else None,
+                                                       C.c_void_p(stream if stream else 0))
+        self._check(rc, "ffddp_fleet_inject_obs_rows_dev")
 
     def fleet_inject_cmd_dev(self, t, inj: _abi.FleetInject, k: int, stream=None, rows=None):
         """Tick k's command_for_plant, enqueued after fleet_post_dev and before
@@ -641,12 +606,9 @@ class BatchedBoxFDDP:
         B = int(t["tau_cmd"].shape[0])
         args = (self._h, B, C.byref(inj), int(k), C.c_void_p(int(t["tau_cmd"].data_ptr())),
                 C.c_void_p(int(t["tau_app"].data_ptr())))
-        if rows is not None:
-            rc = self._lib.ffddp_fleet_inject_cmd_rows_dev(*args, C.byref(rows), C.c_void_p(stream if stream else 0))
-            self._check(rc, "ffddp_fleet_inject_cmd_rows_dev")
-            return
-        rc = self._lib.ffddp_fleet_inject_cmd_dev(*args, C.c_void_p(stream if stream else 0))
-        self._check(rc, "ffddp_fleet_inject_cmd_dev")
+        rc = self._lib.ffddp_fleet_inject_cmd_rows_dev(*args, C.byref(rows) if rows is not None else None,
+                                                       C.c_void_p(stream if stream else 0))
+        self._check(rc, "ffddp_fleet_inject_cmd_rows_dev")
 
     def fleet_noise_dev(self, seed, k: int, z, words=None, stream=None):
         """The device Philox source alone: z (B, 28) float64 <- tick k's normals
@@ -715,7 +677,7 @@ class BatchedBoxFDDP:
             lam=np.zeros((B, N + 1, 3)),
         )
         d = _abi.dptr
-        fr = None
+        fr = cw = None
         if force_ref is not None:
             fr = np.asarray(force_ref, np.float64)
             if fr.shape != (B, N + 1):
@@ -726,32 +688,14 @@ class BatchedBoxFDDP:
             if cw.shape != (B, _abi.COST_W):
                 raise ValueError("cost_weights must have shape (B, COST_W)")
             cw = np.ascontiguousarray(cw)
-            rc = self._lib.ffddp_calc_diff_wts(
-                self._h, B, d(f(batch.x0, (B, nx))), d(f(batch.node_ref, (B, N + 1, 6))),
-                d(f(batch.inst_ref, (B, 21))), _abi.uptr(np.ascontiguousarray(np.asarray(batch.surface, np.uint8))),
-                d(f(xs, (B, N + 1, nx))), d(f(us, (B, N, 7))), d(fr) if fr is not None else None, d(cw), d(out["Fx"]),
-                d(out["Fu"]), d(out["Lx"]), d(out["Lu"]), d(out["Lxx"]), d(out["Lxu"]), d(out["Luu"]), d(out["cost"]),
-                d(out["xnext"]), d(out["lam"]),
-            )
-            self._check(rc, "ffddp_calc_diff_wts")
-            return out
-        if fr is not None:
-            rc = self._lib.ffddp_calc_diff_fref(
-                self._h, B, d(f(batch.x0, (B, nx))), d(f(batch.node_ref, (B, N + 1, 6))),
-                d(f(batch.inst_ref, (B, 21))), _abi.uptr(np.ascontiguousarray(np.asarray(batch.surface, np.uint8))),
-                d(f(xs, (B, N + 1, nx))), d(f(us, (B, N, 7))), d(fr), d(out["Fx"]), d(out["Fu"]), d(out["Lx"]),
-                d(out["Lu"]), d(out["Lxx"]), d(out["Lxu"]), d(out["Luu"]), d(out["cost"]), d(out["xnext"]),
-                d(out["lam"]),
-            )
-            self._check(rc, "ffddp_calc_diff_fref")
-            return out
-        rc = self._lib.ffddp_calc_diff(
+        rc = self._lib.ffddp_calc_diff_wts(
             self._h, B, d(f(batch.x0, (B, nx))), d(f(batch.node_ref, (B, N + 1, 6))), d(f(batch.inst_ref, (B, 21))),
             _abi.uptr(np.ascontiguousarray(np.asarray(batch.surface, np.uint8))), d(f(xs, (B, N + 1, nx))),
-            d(f(us, (B, N, 7))), d(out["Fx"]), d(out["Fu"]), d(out["Lx"]), d(out["Lu"]), d(out["Lxx"]),
-            d(out["Lxu"]), d(out["Luu"]), d(out["cost"]), d(out["xnext"]), d(out["lam"]),
+            d(f(us, (B, N, 7))), d(fr) if fr is not None else None, d(cw) if cw is not None else None, d(out["Fx"]),
+            d(out["Fu"]), d(out["Lx"]), d(out["Lu"]), d(out["Lxx"]), d(out["Lxu"]), d(out["Luu"]), d(out["cost"]),
+            d(out["xnext"]), d(out["lam"]),
         )
-        self._check(rc, "ffddp_calc_diff")
+        self._check(rc, "ffddp_calc_diff_wts")
         return out
 
 
