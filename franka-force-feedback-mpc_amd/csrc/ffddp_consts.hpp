@@ -16,6 +16,45 @@ namespace ffddp {
 // "FFDDPINJ"), mirrored by ffddp/uncertainty.py PHILOX_TAG.
 constexpr uint64_t INJECT_PHILOX_TAG = 0x4646444450494e4aull;
 
+// Everything the OCP derives from the torque limits: the BoxQP bounds, the
+// torque soft-limit barrier's bounds (the margin clamped below the smallest
+// limit) and the force-feedback w soft limit.  One body for fill_consts and
+// for ffddp_torque_limit_rows, so a row built from the configuration's limits
+// is the handle's constants by construction.
+struct TorqueLimitConsts {
+  double u_lb[7], u_ub[7], ts_lb[7], ts_ub[7], ws_lim[7];
+};
+inline void torque_limit_consts(const double* tau_limits, double margin, TorqueLimitConsts& o) {
+  double mn = tau_limits[0];
+  for (int i = 1; i < 7; ++i) mn = tau_limits[i] < mn ? tau_limits[i] : mn;
+  double mg = margin > 0.0 ? margin : 0.0;
+  mg = mg < mn - 1.0e-6 ? mg : mn - 1.0e-6;
+  for (int i = 0; i < 7; ++i) {
+    o.ts_lb[i] = -tau_limits[i] + mg;
+    o.ts_ub[i] = tau_limits[i] - mg;
+    o.u_lb[i] = -tau_limits[i];
+    o.u_ub[i] = tau_limits[i];
+  }
+  const double wm = margin > 0.0 ? margin : 0.0;
+  for (int i = 0; i < 7; ++i) {
+    const double l = tau_limits[i] - wm;
+    o.ws_lim[i] = l > 1.0e-9 ? l : 1.0e-9;
+  }
+}
+
+// One instance's torque-limit row (ffddp.h FFDDP_TAU_LIM_W, joint-major):
+// entry 4j u_ub[j], 4j + 1 ts_ub[j], 4j + 2 ws_lim[j], the rest zero padding.
+inline void torque_limit_row(const double* tau_limits, double margin, double* row) {
+  TorqueLimitConsts tl;
+  torque_limit_consts(tau_limits, margin, tl);
+  for (int e = 0; e < FFDDP_TAU_LIM_W; ++e) row[e] = 0.0;
+  for (int j = 0; j < 7; ++j) {
+    row[4 * j + 0] = tl.u_ub[j];
+    row[4 * j + 1] = tl.ts_ub[j];
+    row[4 * j + 2] = tl.ws_lim[j];
+  }
+}
+
 inline void fill_consts(const ffddp_robot& rb, const ffddp_ocp_config& c, DevConsts& k) {
   std::memset(&k, 0, sizeof(k));
   k.rb = rb;
@@ -116,15 +155,13 @@ inline void fill_consts(const ffddp_robot& rb, const ffddp_ocp_config& c, DevCon
   k.w_tau = c.w_tau;
   k.has_tsoft = c.w_tau_soft_limits > 0.0;
   k.w_ts = c.w_tau_soft_limits;
-  double mn = c.tau_limits[0];
-  for (int i = 1; i < 7; ++i) mn = c.tau_limits[i] < mn ? c.tau_limits[i] : mn;
-  double mg = c.tau_soft_limit_margin > 0.0 ? c.tau_soft_limit_margin : 0.0;
-  mg = mg < mn - 1.0e-6 ? mg : mn - 1.0e-6;
+  TorqueLimitConsts tl;
+  torque_limit_consts(c.tau_limits, c.tau_soft_limit_margin, tl);
   for (int i = 0; i < 7; ++i) {
-    k.ts_lb[i] = -c.tau_limits[i] + mg;
-    k.ts_ub[i] = c.tau_limits[i] - mg;
-    k.u_lb[i] = -c.tau_limits[i];
-    k.u_ub[i] = c.tau_limits[i];
+    k.ts_lb[i] = tl.ts_lb[i];
+    k.ts_ub[i] = tl.ts_ub[i];
+    k.u_lb[i] = tl.u_lb[i];
+    k.u_ub[i] = tl.u_ub[i];
   }
   k.Kp = c.contact_gains[0];
   k.Kd = c.contact_gains[1];
@@ -137,11 +174,7 @@ inline void fill_consts(const ffddp_robot& rb, const ffddp_ocp_config& c, DevCon
   k.beta = 1.0 - al;
   k.w_w = c.w_w > 0.0 ? c.w_w : 0.0;
   k.w_ws = c.w_w_soft_limits > 0.0 ? c.w_w_soft_limits : 0.0;
-  const double wm = c.tau_soft_limit_margin > 0.0 ? c.tau_soft_limit_margin : 0.0;
-  for (int i = 0; i < 7; ++i) {
-    const double l = c.tau_limits[i] - wm;
-    k.ws_lim[i] = l > 1.0e-9 ? l : 1.0e-9;
-  }
+  for (int i = 0; i < 7; ++i) k.ws_lim[i] = tl.ws_lim[i];
   k.w_y = c.w_y > 0.0 ? c.w_y : 0.0;
   for (int i = 0; i < 21; ++i) k.Wy2[i] = c.y_weights[i] * c.y_weights[i];
   // solver constants (SolverBoxFDDP / SolverFDDP / BoxQP defaults)

@@ -120,6 +120,9 @@ struct Dev {
                        //          read by the FR instantiations of k_node / k_forward_g8 only; null: C.fn_ref
   const double* cw;    // [B][FFDDP_COST_W] cost-weight rows (ffddp_solve_batch_wts_dev), read by the CW
                        //          instantiations of k_node / k_forward_g8 only; null: C's weights
+  const double* ul;    // [B][FFDDP_TAU_LIM_W] torque-limit rows (ffddp_solve_batch_lim_dev), read by the UL
+                       //          instantiations of k_node / k_forward_g8 and by the backward pass's fill of its
+                       //          BoxQP bounds; null: C's limits
 };
 
 // Active-instance compaction.  Iteration it reads list (it & 1): the
@@ -276,7 +279,9 @@ struct NodeShared {
 // lk (the node group's LDS in k_node).
 // CW: the scalar cost weights come from the instance's row d.cw[b] (index
 // constants FFDDP_CW_* of ffddp.h) instead of C; which terms exist stays C's.
-template <int NC, bool FF, bool FR, bool CW>
+// UL: the torque soft-limit bounds and the w soft limit come from the
+// instance's row d.ul[b] (ffddp.h FFDDP_TAU_LIM_W), read where C's were.
+template <int NC, bool FF, bool FR, bool CW, bool UL>
 __device__ __forceinline__ void primal_group(const DevConsts& C, const Dev& d, const double* __restrict__ x0,
                                              const double* __restrict__ node_ref, const double* __restrict__ inst_ref,
                                              const uint8_t* __restrict__ surface, int b, int t, Primal* P,
@@ -315,8 +320,9 @@ __device__ __forceinline__ void primal_group(const DevConsts& C, const Dev& d, c
   }
   double lam[3];
   const double* cw = CW ? d.cw + (long)b * FFDDP_COST_W : nullptr;
-  const double pc = node_primal_g8<NC, FR, CW>(C, mode, surf, q, v, u, xreg[ji], xreg[7 + ji], xreg[14 + ji], ref,
-                                               P, lk, lam, FR ? d.fref + ((long)b * (N + 1) + t) : nullptr, cw);
+  const double* ul = UL ? d.ul + (long)b * FFDDP_TAU_LIM_W : nullptr;
+  const double pc = node_primal_g8<NC, FR, CW, UL>(C, mode, surf, q, v, u, xreg[ji], xreg[7 + ji], xreg[14 + ji], ref,
+                                                   P, lk, lam, FR ? d.fref + ((long)b * (N + 1) + t) : nullptr, cw, ul);
   double* rec = d.rec_buf + ((long)b * (N + 1) + t) * d.rec;
   // node cost (IAM scaling, FF augmentation terms): per-lane shares summed over the group
   double c = FF ? C.dt * pc : (terminal ? pc : C.dt * pc);
@@ -336,7 +342,7 @@ __device__ __forceinline__ void primal_group(const DevConsts& C, const Dev& d, c
         const double ww = usrc[(long)t * NU + li];
         if (C.w_w > 0.0) part += 0.5 * cw_get<CW>(cw, FFDDP_CW_W, C.w_w) * (ww * ww);
         if (C.w_ws > 0.0) {
-          const double ov = fabs(ww) - C.ws_lim[li];
+          const double ov = fabs(ww) - (UL ? ul[4 * li + 2] : C.ws_lim[li]);
           const double o = ov > 0.0 ? ov : 0.0;
           part += cw_get<CW>(cw, FFDDP_CW_W_SOFT_LIMITS, C.w_ws) * (0.5 * (o * o));
         }
@@ -400,7 +406,10 @@ __device__ __forceinline__ double fquad(const double* a, const double* Dd, const
 // CW: the scalar cost weights are those of the instance's row d.cw[b] (a solve
 // with cost_w), each loaded where its term is evaluated; CW = false is the
 // kernel as it was.
-template <int NC, bool FF, bool FR = false, bool CW = false>
+// UL: the torque soft-limit bounds and the w soft limit are those of the
+// instance's row d.ul[b] (a solve with tau_lim), each read where C's was;
+// UL = false is the kernel as it was.
+template <int NC, bool FF, bool FR = false, bool CW = false, bool UL = false>
 __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE_WAVES))) void k_node(const DevConsts* __restrict__ Cg, Dev d,
                                                       const double* __restrict__ x0,
                                                       const double* __restrict__ node_ref,
@@ -439,7 +448,7 @@ __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE
   const double* ref = node_ref + ((long)b * (N + 1) + t) * 6;
   NodeGroupShared& G = S.g[grp];
   Primal& P = G.P;
-  if (active && lane < G8) primal_group<NC, FF, FR, CW>(C, d, x0, node_ref, inst_ref, surface, b, t, &P, G.lk, xsrc, usrc);
+  if (active && lane < G8) primal_group<NC, FF, FR, CW, UL>(C, d, x0, node_ref, inst_ref, surface, b, t, &P, G.lk, xsrc, usrc);
   __syncthreads();
   const bool need_u = mode != MODE_TERMINAL_X;
   // control directions first, their results stored at once (neither touches
@@ -554,7 +563,14 @@ __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE
         // augmented control terms: Lu = w_w w + w_s g_soft ; Luu = diag ; Lxu = 0
         double wk = 0.0;
         if (!terminal) wk = usrc[(long)t * NU + kk];
-        const double ov = fabs(wk) - C.ws_lim[kk];
+        double wsl;
+        if constexpr (UL) {
+          // a term the handle does not build never reads its entry
+          wsl = C.w_ws > 0.0 ? d.ul[(long)b * FFDDP_TAU_LIM_W + 4 * kk + 2] : C.ws_lim[kk];
+        } else {
+          wsl = C.ws_lim[kk];
+        }
+        const double ov = fabs(wk) - wsl;
         const bool act = ov > 0.0;
         const double gs = act ? ov * (wk > 0.0 ? 1.0 : (wk < 0.0 ? -1.0 : 0.0)) : 0.0;
         if constexpr (CW) {
@@ -1026,8 +1042,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LATE ? 1 : (
   int retries = 0;
   bool fail_inst = false;
   double dg = 0.0, dq = 0.0, stop = 0.0, ffl = 0.0;
-  S.ulb[BW_DIET_SLOTS ? l % NU : l] = C.u_lb[l % NU];
-  S.uub[BW_DIET_SLOTS ? l % NU : l] = C.u_ub[l % NU];
+  {
+    // per-instance torque limits (d.ul, wave-uniform): the row's u_ub and its negation; once per pass
+    double ulb_l = C.u_lb[l % NU], uub_l = C.u_ub[l % NU];
+    if (d.ul && C.use_box) {
+      uub_l = d.ul[(long)b * FFDDP_TAU_LIM_W + 4 * (l % NU)];
+      ulb_l = -uub_l;
+    }
+    S.ulb[BW_DIET_SLOTS ? l % NU : l] = ulb_l;
+    S.uub[BW_DIET_SLOTS ? l % NU : l] = uub_l;
+  }
   // this lane's lower-triangle entries of Q (phase C) and V (phase F), fixed for the whole pass
   constexpr int NQE = ND * (ND + 1) / 2, NQL = (NQE + 63) / 64;
   // phase C unroll: full in the latency variants (FF's 7 passes move into
@@ -1461,8 +1485,14 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(WPE))) void
   bool fail_inst = false;
   double dg = 0.0, dq = 0.0, stop = 0.0, ffl = 0.0;
   if (wv == 0) {
-    S.ulb[BW_DIET_SLOTS ? l % NU : l] = C.u_lb[l % NU];
-    S.uub[BW_DIET_SLOTS ? l % NU : l] = C.u_ub[l % NU];
+    // per-instance torque limits (d.ul, wave-uniform): the row's u_ub and its negation; once per pass
+    double ulb_l = C.u_lb[l % NU], uub_l = C.u_ub[l % NU];
+    if (d.ul && C.use_box) {
+      uub_l = d.ul[(long)b * FFDDP_TAU_LIM_W + 4 * (l % NU)];
+      ulb_l = -uub_l;
+    }
+    S.ulb[BW_DIET_SLOTS ? l % NU : l] = ulb_l;
+    S.uub[BW_DIET_SLOTS ? l % NU : l] = uub_l;
   }
   // this lane's lower-triangle entries of Q (phase C) and V (phase F) over 128 lanes
   constexpr int NQE = ND * (ND + 1) / 2, NQL = (NQE + 127) / 128;
@@ -2015,7 +2045,11 @@ __device__ __forceinline__ int ls_row_bcast0(int v) {  // lane 0 of the row into
 // only its role's block of the row (joint lanes the state / control weights,
 // the EE lane the frame / contact ones: LS_CW registers shared by both roles),
 // loaded once before the node loop: the row does not depend on the node.
-template <int NC, bool FF, bool ROW, bool FR = false, bool CW = false>
+// UL: the BoxQP clamp, the torque soft-limit bounds and the w soft limit are
+// the lane's three entries of the instance's row d.ul[b], held in registers
+// next to W in place of LaneK's (per block, while a block's groups belong to
+// different instances).  The EE lane takes joint 6's, as LaneK gives it.
+template <int NC, bool FF, bool ROW, bool FR = false, bool CW = false, bool UL = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW_WPE))) void k_forward_g8(const DevConsts* __restrict__ Cg, Dev d,
                                                    const double* __restrict__ x0,
                                                    const double* __restrict__ node_ref,
@@ -2103,6 +2137,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
 #pragma unroll
     for (int k = 0; k < LS_CW; ++k) W.w[k] = cwr[k];
   }
+  LsL L;
+  if constexpr (UL) {
+    // a term the handle does not build never reads its entry
+    const double* ulr = d.ul + (long)b * FFDDP_TAU_LIM_W + 4 * (J ? li : NQ - 1);
+    L.uub = (fl & RF_BOX) ? ulr[0] : 0.0;
+    L.tsub = (fl & RF_TSOFT) ? ulr[1] : 0.0;
+    L.wslim = (FF && C.w_ws > 0.0) ? ulr[2] : K.wslim;
+  }
   // FF augmentation weights (joint lanes) at their use: a term the handle does not build keeps C's zero
   auto w_y = [&]() { return (CW && C.w_y > 0.0) ? W.w[FFDDP_CW_Y - FFDDP_CW_JOINT0] : C.w_y; };
   auto w_w = [&]() { return (CW && C.w_w > 0.0) ? W.w[FFDDP_CW_W - FFDDP_CW_JOINT0] : C.w_w; };
@@ -2163,7 +2205,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
           acc = fma(-pK[7 + m], dvm, acc);
           if (FF) acc = fma(-pK[14 + m], ls_get<ROW>(dtt, m), acc);
         }
-        if (fl & RF_BOX) acc = fmin(fmax(acc, K.ulb), K.uub);
+        if (fl & RF_BOX) acc = UL ? fmin(fmax(acc, -L.uub), L.uub) : fmin(fmax(acc, K.ulb), K.uub);
         u = acc;
         if (Js) utr[(long)t * NU + ji] = u;
       }
@@ -2171,7 +2213,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
       double qn, vn, cp, lam[3];
       const double uin = FF ? xt_t : u;
       PP(8);
-      ls_node_calc<NC, ROW, FR, CW>(C, fl, K, W, MODE_RUNNING, surf, xq_t, xv_t, uin, xq, xv, tref, ref, fnr, qn, vn, cp, lam
+      ls_node_calc<NC, ROW, FR, CW, UL>(C, fl, K, W, L, MODE_RUNNING, surf, xq_t, xv_t, uin, xq, xv, tref, ref, fnr, qn, vn, cp, lam
 #ifdef FFDDP_PHASE_PROF
                             , pp_acc, pp_last
 #endif
@@ -2184,7 +2226,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
           const double e1 = xq_t - yq, e2 = xv_t - yv, e3 = xt_t - yt;
           c = fma(0.5 * w_y(), fma(K.wy2t * e3, e3, fma(K.wy2v * e2, e2, (K.wy2q * e1) * e1)), c);
           c = fma(0.5 * w_w(), u * u, c);
-          const double ov = fabs(u) - K.wslim;
+          const double ov = fabs(u) - (UL ? L.wslim : K.wslim);
           const double oo = ov > 0.0 ? ov : 0.0;
           c = fma(w_ws(), 0.5 * (oo * oo), c);
         }
@@ -2204,7 +2246,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
       double qn, vn, cp, lam[3];
       const int mode = FF ? MODE_TERMINAL_U : MODE_TERMINAL_X;
       PP(8);
-      ls_node_calc<NC, ROW, FR, CW>(C, fl, K, W, mode, surf, xq_t, xv_t, FF ? xt_t : 0.0, xq, xv, tref, ref, fnr, qn, vn, cp, lam
+      ls_node_calc<NC, ROW, FR, CW, UL>(C, fl, K, W, L, mode, surf, xq_t, xv_t, FF ? xt_t : 0.0, xq, xv, tref, ref, fnr, qn, vn, cp, lam
 #ifdef FFDDP_PHASE_PROF
                             , pp_acc, pp_last
 #endif
@@ -2828,6 +2870,9 @@ __device__ __forceinline__ double fleet_clip(double x, double lo, double hi) {
 // instance's first block, lanes 0-6 = the seven joints) the policy, _command,
 // the info record, and the sweep's actuation and log columns when asked for.
 //
+// tau_lim (ffddp_fleet_post_lim_dev): the clips use the instance's own limit,
+// entry 4i of its torque-limit row; null: P.tau_limits.
+//
 // SCHED (ffddp_fleet_post_sched_dev): only the instances that solved this tick
 // (Q.need) can be kept; the policy reads the kept solution through Q.age (see
 // k_fleet_pre), _safe_tau's trust / rate / smoothing filter follows the clip
@@ -2842,7 +2887,7 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_post(
     const int32_t* __restrict__ stats, const double* __restrict__ x0, const uint8_t* __restrict__ surface,
     const double* __restrict__ tau_bias, long ld_bias, double* __restrict__ tau_cmd, double* __restrict__ info,
     const double* __restrict__ scale, double* __restrict__ tau_app, double* __restrict__ tau_filt, double lpf,
-    const double* __restrict__ obs, long ld_obs, double* __restrict__ log_obs) {
+    const double* __restrict__ obs, long ld_obs, double* __restrict__ log_obs, const double* __restrict__ tau_lim) {
   const long b = blockIdx.x;
   const int t0 = blockIdx.y * FLEET_BLOCK + threadIdx.x, step = FLEET_CHUNKS * FLEET_BLOCK;
   const long nxs = (long)(N + 1) * nx, nus = (long)N * NU, nK = (long)N * NU * nx;
@@ -2890,7 +2935,8 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_post(
 #pragma clang fp contract(off)
     if (unstable) traw = tau_bias[b * ld_bias + i] - P.fallback_dq_damping * x0b[7 + i];
     const bool bad = __ballot(on && !isfinite(traw)) != 0;
-    const double lim = P.tau_limits[i], x = bad ? tprev[i] : traw;
+    // tau_lim (ffddp_fleet_post_lim_dev): the instance's own limit, entry 4i of its row
+    const double lim = tau_lim ? tau_lim[b * FFDDP_TAU_LIM_W + 4 * i] : P.tau_limits[i], x = bad ? tprev[i] : traw;
     tc = x != x ? x : fmin(fmax(x, -lim), lim);
     if (SCHED && Q.apply_filter) {  // _safe_tau's filter (crocoddyl_classical.py:272-284), its order and grouping
       const double prev = tprev[i], al = Q.tau_smoothing_alpha, ms = Q.tau_rate_limit[i] * Q.dt;
@@ -3111,6 +3157,9 @@ struct ffddp_handle {
   // [max_batch][N+1] filled with fn_des: the force reference of a solve with cost weights
   // and no force_ref of its own (first such solve)
   double* fref_const = nullptr;
+  // [max_batch][FFDDP_COST_W] rows of the configuration's weights: the cost weights of a solve with torque
+  // limits and no cost_w of its own (first such solve)
+  double* cw_const = nullptr;
   // sub-batch streams: the batch is split into nstreams slices solved on their
   // own HIP streams, so latency-bound phases of one slice overlap with the
   // throughput-bound phases of another (FFDDP_STREAMS, default 4: three
@@ -3193,6 +3242,7 @@ void free_all(ffddp_handle* h) {
     if (p) (void)hipFree(p);
   if (h->trace) (void)hipFree(h->trace);
   if (h->fref_const) (void)hipFree(h->fref_const);
+  if (h->cw_const) (void)hipFree(h->cw_const);
   if (h->stage) (void)hipHostFree(h->stage);
 }
 
@@ -3245,6 +3295,7 @@ Dev dev_slice(const Dev& d0, int b0, int Bk, int k) {
   if (d.trace) d.trace += (long)b0 * d0.trace_it * FFDDP_TRACE_W;
   if (d.fref) d.fref += (long)b0 * (N + 1);
   if (d.cw) d.cw += (long)b0 * FFDDP_COST_W;
+  if (d.ul) d.ul += (long)b0 * FFDDP_TAU_LIM_W;
   return d;
 }
 
@@ -3262,10 +3313,10 @@ struct SolveArgs {
   double* fn_pred;
   int32_t* stats;
   const uint8_t* active;
-  const double *fref, *cw;
+  const double *fref, *cw, *ul;
 };
 
-template <int NC, bool FF, bool FR, bool CW>
+template <int NC, bool FF, bool FR, bool CW, bool UL>
 int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* io) {
   const int B = a.B, maxiter = a.maxiter;
   const int N = h->hc.N, nx = h->hc.nx;
@@ -3302,6 +3353,7 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
   Dev dbase = h->d;
   dbase.fref = FR ? a.fref : nullptr;
   dbase.cw = CW ? a.cw : nullptr;
+  dbase.ul = UL ? a.ul : nullptr;
   if (!io) {
     dbase.xs = a.xs;
     dbase.us = a.us;
@@ -3365,7 +3417,7 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
     if (it == 0 && stagger == 2 && k + 1 < S) HIPCHK(h, hipEventRecord(h->stg[k], ss));
     {
       ProfScope p(h, ss, KC_NODE);
-      hipLaunchKernelGGL((k_node<NC, FF, FR, CW>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, ss,
+      hipLaunchKernelGGL((k_node<NC, FF, FR, CW, UL>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, ss,
                          h->dc, d, x0k, nrefk, irefk, surfk, 0, it & 1);
     }
     if (it == 0 && stagger == 1 && k + 1 < S) HIPCHK(h, hipEventRecord(h->stg[k], ss));
@@ -3436,13 +3488,13 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
         const long groups = more ? (long)Bk * ntr : g1;
         if (!row_only) {
           const dim3 grid((unsigned)((groups * G8 + 63) / 64));
-          hipLaunchKernelGGL((k_forward_g8<NC, FF, false, FR, CW>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
+          hipLaunchKernelGGL((k_forward_g8<NC, FF, false, FR, CW, UL>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
                              surfk, tr0, ntr, more, it & 1, wide, row_max);
         }
         if (row_max > 0) {
           const long rg = std::min(groups, (long)row_max);  // the row layout runs only when they fit
           const dim3 grid((unsigned)((rg * 16 + 63) / 64));
-          hipLaunchKernelGGL((k_forward_g8<NC, FF, true, FR, CW>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
+          hipLaunchKernelGGL((k_forward_g8<NC, FF, true, FR, CW, UL>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
                              surfk, tr0, ntr, more, it & 1, wide, row_max);
         }
       };
@@ -3541,30 +3593,35 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
   return 0;
 }
 
-// The one (nc, variant, force reference, cost weights) -> template constants decision, for the solve and for
-// ffddp_calc_diff_wts: f(NC, FF, FR, CW) is called with std::integral_constant arguments.  fr: there is a force
-// reference; without one the kernels are the FR = false instantiations.  cw: there are cost-weight rows.  The CW
-// kernels exist with FR only (the caller supplies a force reference of fn_des where the user gave none: the same
-// bits), so the build does not double.
-template <class F> int dispatch_variant(ffddp_handle* h, bool fr, bool cw, F&& f) {
+// The one (nc, variant, force reference, cost weights, torque limits) -> template constants decision, for the solve
+// and for ffddp_calc_diff_lim: f(NC, FF, FR, CW, UL) is called with std::integral_constant arguments.  fr: there is
+// a force reference; without one the kernels are the FR = false instantiations.  cw: there are cost-weight rows.
+// The CW kernels exist with FR only (the caller supplies a force reference of fn_des where the user gave none: the
+// same bits), so the build does not double.  ul: there are torque-limit rows; the UL kernels exist with FR and CW
+// only (the caller supplies rows of the configuration's weights likewise).
+template <class F> int dispatch_variant(ffddp_handle* h, bool fr, bool cw, bool ul, F&& f) {
   if (cw && !fr) return fail(h, FFDDP_E_INVALID, "cost weights without a force reference");
+  if (ul && !cw) return fail(h, FFDDP_E_INVALID, "torque limits without cost weights");
   using NC1 = std::integral_constant<int, 1>;
   using NC3 = std::integral_constant<int, 3>;
   const bool ff = h->hc.variant == FFDDP_FORCE_FEEDBACK;
-  auto nc_ff = [&](auto FR, auto CW) -> int {
-    if (h->hc.nc == 1) return ff ? f(NC1{}, std::true_type{}, FR, CW) : f(NC1{}, std::false_type{}, FR, CW);
-    return ff ? f(NC3{}, std::true_type{}, FR, CW) : f(NC3{}, std::false_type{}, FR, CW);
+  auto nc_ff = [&](auto FR, auto CW, auto UL) -> int {
+    if (h->hc.nc == 1) return ff ? f(NC1{}, std::true_type{}, FR, CW, UL) : f(NC1{}, std::false_type{}, FR, CW, UL);
+    return ff ? f(NC3{}, std::true_type{}, FR, CW, UL) : f(NC3{}, std::false_type{}, FR, CW, UL);
   };
-  if (cw) return nc_ff(std::true_type{}, std::true_type{});
-  if (fr) return nc_ff(std::true_type{}, std::false_type{});
-  return nc_ff(std::false_type{}, std::false_type{});
+  if (ul) return nc_ff(std::true_type{}, std::true_type{}, std::true_type{});
+  if (cw) return nc_ff(std::true_type{}, std::true_type{}, std::false_type{});
+  if (fr) return nc_ff(std::true_type{}, std::false_type{}, std::false_type{});
+  return nc_ff(std::false_type{}, std::false_type{}, std::false_type{});
 }
 
 // io: the host entry point's copies (nullptr: the device entry points and the plan capture)
 int launch_solve(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* io) {
-  return dispatch_variant(h, a.fref != nullptr, a.cw != nullptr, [&](auto NC, auto FF, auto FR, auto CW) {
-    return launch_solve_t<decltype(NC)::value, decltype(FF)::value, decltype(FR)::value, decltype(CW)::value>(h, a, s, io);
-  });
+  return dispatch_variant(h, a.fref != nullptr, a.cw != nullptr, a.ul != nullptr,
+                          [&](auto NC, auto FF, auto FR, auto CW, auto UL) {
+                            return launch_solve_t<decltype(NC)::value, decltype(FF)::value, decltype(FR)::value,
+                                                  decltype(CW)::value, decltype(UL)::value>(h, a, s, io);
+                          });
 }
 
 // The one argument check of ffddp_solve_batch and ffddp_solve_batch_wts_dev.  B == 0 passes without a look at
@@ -3845,20 +3902,77 @@ static int const_force_ref(ffddp_handle* h) {
   return 0;
 }
 
+// the handle's constant cost-weight rows (the configuration's weights in every row; config.cost_weight_row's
+// entries), made on first use: the UL kernels are instantiated with CW only, and rows of the handle's weights
+// reproduce the scalar path's bits
+static int const_cost_rows(ffddp_handle* h) {
+  if (h->cw_const) return 0;
+  const DevConsts& c = h->hc;
+  const bool ff = c.variant == FFDDP_FORCE_FEEDBACK;
+  double row[FFDDP_COST_W] = {};
+  row[FFDDP_CW_EE_ORI] = c.w_ori;
+  row[FFDDP_CW_WDAMP] = c.w_wd;
+  row[FFDDP_CW_EE_POS] = c.w_ee_pos;
+  row[FFDDP_CW_TANGENT_POS] = c.w_tp;
+  row[FFDDP_CW_TANGENT_VEL] = c.w_tv;
+  row[FFDDP_CW_PLANE_Z] = c.w_pz;
+  row[FFDDP_CW_VZ] = c.w_vz;
+  row[FFDDP_CW_UNILATERAL] = c.w_uni;
+  row[FFDDP_CW_FN] = c.w_fn;
+  row[FFDDP_CW_FRICTION_CONE] = c.nc == 3 ? c.w_fc : 0.0;
+  row[FFDDP_CW_POSTURE] = c.w_post;
+  row[FFDDP_CW_V] = c.w_v;
+  row[FFDDP_CW_Q_SOFT_LIMITS] = c.w_qs;
+  row[FFDDP_CW_TAU] = c.w_tau;
+  row[FFDDP_CW_TAU_SOFT_LIMITS] = c.w_ts;
+  row[FFDDP_CW_Y] = ff ? c.w_y : 0.0;
+  row[FFDDP_CW_W] = ff ? c.w_w : 0.0;
+  row[FFDDP_CW_W_SOFT_LIMITS] = ff ? c.w_ws : 0.0;
+  const size_t n = (size_t)h->max_batch * FFDDP_COST_W;
+  std::vector<double> v(n);
+  for (size_t i = 0; i < n; ++i) v[i] = row[i % FFDDP_COST_W];
+  if (int rc = dalloc(h, &h->cw_const, n)) return rc;
+  HIPCHK(h, hipMemcpy(h->cw_const, v.data(), n * 8, hipMemcpyHostToDevice));
+  return 0;
+}
+
+int ffddp_torque_limit_rows(const ffddp_ocp_config* cfg, int B, const double* tau_limits, double* rows) {
+  if (!cfg || B < 0 || (B > 0 && (!tau_limits || !rows))) return FFDDP_E_INVALID;
+  for (long i = 0; i < (long)B * 7; ++i)
+    if (!(std::isfinite(tau_limits[i]) && tau_limits[i] > 0.0)) return FFDDP_E_INVALID;
+  for (long b = 0; b < B; ++b)
+    torque_limit_row(tau_limits + b * 7, cfg->tau_soft_limit_margin, rows + b * FFDDP_TAU_LIM_W);
+  return 0;
+}
+
 int ffddp_solve_batch_wts_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
                               const double* inst_ref, const uint8_t* surface, const double* xs_init,
                               const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
                               double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
                               const uint8_t* active, const double* force_ref, const double* cost_w, void* stream) {
+  return ffddp_solve_batch_lim_dev(h, B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs,
+                                   us, K, cost, iters, ok, fn_pred, stats, active, force_ref, cost_w, nullptr, stream);
+}
+
+int ffddp_solve_batch_lim_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                              const double* inst_ref, const uint8_t* surface, const double* xs_init,
+                              const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
+                              double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
+                              const uint8_t* active, const double* force_ref, const double* cost_w,
+                              const double* tau_lim, void* stream) {
   SolveArgs a{B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs, us, K, cost, iters, ok,
-              fn_pred, stats, active, force_ref, cost_w};
+              fn_pred, stats, active, force_ref, cost_w, tau_lim};
   if (int rc = solve_args_check(h, a)) return rc;
   if (B == 0) return 0;
   HIPCHK(h, hipSetDevice(h->device));
   // the handle's workspace is shared by every solve: a solve enqueued on
   // another (possibly non-blocking) stream must finish before this one starts
   if (h->last_done_set) HIPCHK(h, hipStreamWaitEvent((hipStream_t)stream, h->last_done, 0));
-  if (cost_w && !force_ref) {
+  if (tau_lim && !cost_w) {
+    if (int rc = const_cost_rows(h)) return rc;
+    a.cw = h->cw_const;
+  }
+  if (a.cw && !force_ref) {
     if (int rc = const_force_ref(h)) return rc;
     a.fref = h->fref_const;
   }
@@ -3906,9 +4020,9 @@ int ffddp_solve_batch(ffddp_handle* h, int B, const double* x0, const double* no
                       const uint8_t* surface, const double* xs_init, const double* us_init, int maxiter,
                       int is_feasible, double* xs, double* us, double* K, double* cost, int32_t* iters, uint8_t* ok,
                       double* fn_pred, int32_t* stats) {
-  // the caller's host arrays; no active mask, force reference or cost weights on this path
+  // the caller's host arrays; no active mask, force reference, cost weights or torque limits on this path
   const SolveArgs user{B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs, us, K, cost,
-                       iters, ok, fn_pred, stats, nullptr, nullptr, nullptr};
+                       iters, ok, fn_pred, stats, nullptr, nullptr, nullptr, nullptr};
   if (int rc = solve_args_check(h, user)) return rc;
   if (B == 0) return 0;
   HIPCHK(h, hipSetDevice(h->device));
@@ -4005,7 +4119,7 @@ int ffddp_solve_batch(ffddp_handle* h, int B, const double* x0, const double* no
   // the solve itself works on the handle's device buffers; xs / us / K: where launch_solve_t copies them down to
   const SolveArgs a{B, h->in_x0, h->in_nref, h->in_iref, h->in_surf, h->in_xs, h->in_us, maxiter, is_feasible,
                     (double*)hout[0], (double*)hout[1], (double*)hout[2], h->out_cost, h->out_iters, h->out_ok,
-                    h->out_fn, h->out_stats, nullptr, nullptr, nullptr};
+                    h->out_fn, h->out_stats, nullptr, nullptr, nullptr, nullptr};
   if (int rc = launch_solve(h, a, cs, &io)) return drain_host_solve(h, rc);
   const double t2 = tm ? now() : 0.0;
   // while the device solves: the first touch of the caller's pageable output
@@ -4201,7 +4315,7 @@ int ffddp_plan_create(ffddp_handle* h, int B, int maxiter, int is_feasible, ffdd
                     (const uint8_t*)(di + L.surf), (const double*)(di + L.xs_init), (const double*)(di + L.us_init),
                     maxiter, is_feasible, (double*)(dq + L.xs), (double*)(dq + L.us), (double*)(dq + L.K),
                     (double*)(dq + L.cost), (int32_t*)(dq + L.iters), (uint8_t*)(dq + L.ok), (double*)(dq + L.fn),
-                    (int32_t*)(dq + L.stats), nullptr, nullptr, nullptr};
+                    (int32_t*)(dq + L.stats), nullptr, nullptr, nullptr, nullptr};
   int rc = 0;
   hipError_t e = hipStreamBeginCapture(p->s, hipStreamCaptureModeThreadLocal);
   if (e == hipSuccess) {
@@ -4393,6 +4507,14 @@ int ffddp_calc_diff_wts(ffddp_handle* h, int B, const double* x0, const double* 
                         const uint8_t* surface, const double* xs, const double* us, const double* force_ref,
                         const double* cost_w, double* Fx, double* Fu, double* Lx, double* Lu, double* Lxx, double* Lxu,
                         double* Luu, double* cost, double* xnext, double* lam) {
+  return ffddp_calc_diff_lim(h, B, x0, node_ref, inst_ref, surface, xs, us, force_ref, cost_w, nullptr, Fx, Fu, Lx, Lu,
+                             Lxx, Lxu, Luu, cost, xnext, lam);
+}
+
+int ffddp_calc_diff_lim(ffddp_handle* h, int B, const double* x0, const double* node_ref, const double* inst_ref,
+                        const uint8_t* surface, const double* xs, const double* us, const double* force_ref,
+                        const double* cost_w, const double* tau_lim, double* Fx, double* Fu, double* Lx, double* Lu,
+                        double* Lxx, double* Lxu, double* Luu, double* cost, double* xnext, double* lam) {
   if (!h) return FFDDP_E_INVALID;
   if (B < 1 || B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "bad B");
   if (force_ref && !(h->hc.w_fn > 0.0))
@@ -4404,12 +4526,19 @@ int ffddp_calc_diff_wts(ffddp_handle* h, int B, const double* x0, const double* 
     ~Tmp() {
       if (p) (void)hipFree(p);
     }
-  } fref, cw;
+  } fref, cw, ul;
+  const bool with_cw = cost_w || tau_lim;
   if (force_ref) {
     HIPCHK(h, hipMalloc((void**)&fref.p, (size_t)B * (h->hc.N + 1) * 8));
     HIPCHK(h, hipMemcpy(fref.p, force_ref, (size_t)B * (h->hc.N + 1) * 8, hipMemcpyHostToDevice));
-  } else if (cost_w) {
+  } else if (with_cw) {
     if (int rc = const_force_ref(h)) return rc;
+  }
+  if (tau_lim) {
+    if (!cost_w)
+      if (int rc = const_cost_rows(h)) return rc;
+    HIPCHK(h, hipMalloc((void**)&ul.p, (size_t)B * FFDDP_TAU_LIM_W * 8));
+    HIPCHK(h, hipMemcpy(ul.p, tau_lim, (size_t)B * FFDDP_TAU_LIM_W * 8, hipMemcpyHostToDevice));
   }
   if (cost_w) {
     HIPCHK(h, hipMalloc((void**)&cw.p, (size_t)B * FFDDP_COST_W * 8));
@@ -4419,8 +4548,9 @@ int ffddp_calc_diff_wts(ffddp_handle* h, int B, const double* x0, const double* 
   const bool ff = h->hc.variant == FFDDP_FORCE_FEEDBACK;
   Dev d = h->d;
   d.B = B;
-  d.fref = fref.p ? fref.p : (cost_w ? h->fref_const : nullptr);
-  d.cw = cw.p;
+  d.fref = fref.p ? fref.p : (with_cw ? h->fref_const : nullptr);
+  d.cw = cw.p ? cw.p : (tau_lim ? h->cw_const : nullptr);
+  d.ul = ul.p;
   HIPCHK(h, hipMemcpy(h->in_x0, x0, (size_t)B * nx * 8, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->in_nref, node_ref, (size_t)B * (N + 1) * 6 * 8, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->in_iref, inst_ref, (size_t)B * 21 * 8, hipMemcpyHostToDevice));
@@ -4429,9 +4559,11 @@ int ffddp_calc_diff_wts(ffddp_handle* h, int B, const double* x0, const double* 
   HIPCHK(h, hipMemcpy(h->in_us, us, (size_t)B * N * NU * 8, hipMemcpyHostToDevice));
   // node kernel reads (xs, us) from the solver state: initialise it from the inputs
   hipLaunchKernelGGL(k_init<false>, dim3(1024), dim3(INIT_BLOCK), 0, nullptr, h->dc, d, h->in_xs, h->in_us, 0, nullptr);
-  const int rc = dispatch_variant(h, d.fref != nullptr, d.cw != nullptr, [&](auto NC, auto FF, auto FR, auto CW) {
+  const int rc = dispatch_variant(h, d.fref != nullptr, d.cw != nullptr, d.ul != nullptr,
+                                  [&](auto NC, auto FF, auto FR, auto CW, auto UL) {
     const long nodes = (long)B * (N + 1);
-    hipLaunchKernelGGL((k_node<decltype(NC)::value, decltype(FF)::value, decltype(FR)::value, decltype(CW)::value>),
+    hipLaunchKernelGGL((k_node<decltype(NC)::value, decltype(FF)::value, decltype(FR)::value, decltype(CW)::value,
+                               decltype(UL)::value>),
                        dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, nullptr, h->dc, d, h->in_x0,
                        h->in_nref, h->in_iref, h->in_surf, 1, 0);
     return 0;
@@ -4644,13 +4776,15 @@ int ffddp_fleet_pre_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params* 
                    nullptr, stream);
 }
 
-// The body of ffddp_fleet_post_dev and _post_sched_dev (sched: the scheduled tick, the SCHED instantiation)
+// The body of ffddp_fleet_post_dev, _post_sched_dev and _post_lim_dev (sched: the scheduled tick, the SCHED
+// instantiation; tau_lim: per-instance torque-limit rows or null)
 static int fleet_post(ffddp_handle* h, const char* name, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
                       const double* xs, const double* us, const double* K, const double* cost, const int32_t* iters,
                       const uint8_t* ok, const double* fn_pred, const int32_t* stats, const double* x0,
                       const uint8_t* surface, const double* tau_bias, int ld_tau_bias, double* tau_cmd, double* info,
                       const double* scale, double* tau_app, double* tau_filt, double lpf, const double* obs,
-                      int ld_obs, double* log_obs, const ffddp_fleet_sched* sched, void* stream) {
+                      int ld_obs, double* log_obs, const ffddp_fleet_sched* sched, const double* tau_lim,
+                      void* stream) {
   if (!h) return FFDDP_E_INVALID;
   const std::string who(name);
   if (B <= 0) return fail(h, FFDDP_E_INVALID, who + ": B must be positive");
@@ -4666,9 +4800,21 @@ static int fleet_post(ffddp_handle* h, const char* name, int B, const ffddp_flee
   hipLaunchKernelGGL(sched ? k_fleet_post<true> : k_fleet_post<false>, dim3(B, FLEET_CHUNKS), dim3(FLEET_BLOCK), 0,
                      (hipStream_t)stream, h->hc.N, h->hc.nx, *p, *s, sched ? *sched : ffddp_fleet_sched{}, xs, us, K, cost,
                      iters, ok, fn_pred, stats, x0, surface, tau_bias, (long)ld_tau_bias, tau_cmd, info, scale, tau_app,
-                     tau_filt, lpf, obs, (long)ld_obs, log_obs);
+                     tau_filt, lpf, obs, (long)ld_obs, log_obs, tau_lim);
   HIPCHK(h, hipGetLastError());
   return 0;
+}
+
+int ffddp_fleet_post_lim_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                             const double* xs, const double* us, const double* K, const double* cost,
+                             const int32_t* iters, const uint8_t* ok, const double* fn_pred, const int32_t* stats,
+                             const double* x0, const uint8_t* surface, const double* tau_bias, int ld_tau_bias,
+                             double* tau_cmd, double* info, const double* scale, double* tau_app, double* tau_filt,
+                             double lpf, const double* obs, int ld_obs, double* log_obs,
+                             const ffddp_fleet_sched* sched, const double* tau_lim, void* stream) {
+  return fleet_post(h, "ffddp_fleet_post_lim_dev", B, p, s, xs, us, K, cost, iters, ok, fn_pred, stats, x0, surface,
+                    tau_bias, ld_tau_bias, tau_cmd, info, scale, tau_app, tau_filt, lpf, obs, ld_obs, log_obs, sched,
+                    tau_lim, stream);
 }
 
 int ffddp_fleet_post_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
@@ -4678,7 +4824,8 @@ int ffddp_fleet_post_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, co
                          double* tau_cmd, double* info, const double* scale, double* tau_app, double* tau_filt,
                          double lpf, const double* obs, int ld_obs, double* log_obs, void* stream) {
   return fleet_post(h, "ffddp_fleet_post_dev", B, p, s, xs, us, K, cost, iters, ok, fn_pred, stats, x0, surface, tau_bias,
-                    ld_tau_bias, tau_cmd, info, scale, tau_app, tau_filt, lpf, obs, ld_obs, log_obs, nullptr, stream);
+                    ld_tau_bias, tau_cmd, info, scale, tau_app, tau_filt, lpf, obs, ld_obs, log_obs, nullptr, nullptr,
+                    stream);
 }
 
 int ffddp_fleet_post_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
@@ -4690,7 +4837,7 @@ int ffddp_fleet_post_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params*
                                void* stream) {
   return fleet_post(h, "ffddp_fleet_post_sched_dev", B, p, s, xs, us, K, cost, iters, ok, fn_pred, stats, x0, surface,
                     tau_bias, ld_tau_bias, tau_cmd, info, scale, tau_app, tau_filt, lpf, obs, ld_obs, log_obs, &sched,
-                    stream);
+                    nullptr, stream);
 }
 
 // per-instance tasks (ffddp_task.hpp): the sampler alone, and pre with it in place of node_ref1 / contact_hint

@@ -77,12 +77,16 @@ __device__ __forceinline__ double friction_cone_w(const DevConsts& C, const doub
 // FFDDP_CW_* of ffddp.h) instead of C's, each loaded inside the block of the
 // term that uses it, for the same reason; a term C does not build never
 // reads its entry.
-template <int NC, bool FR = false, bool CW = false>
+// UL: the torque soft-limit barrier's bounds are +-ulr[4 j + 1] (the instance's
+// torque-limit row, ffddp.h FFDDP_TAU_LIM_W) instead of C.ts_lb / ts_ub, read
+// by the joint lane at the barrier, for the same reason.
+template <int NC, bool FR = false, bool CW = false, bool UL = false>
 __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, bool surface, double q, double v, double u,
                                                  double xq, double xv, double tr, const double* ref,
                                                  Primal* __restrict__ gp, double* __restrict__ lk, double (&lam)[3],
                                                  const double* __restrict__ fnp = nullptr,
-                                                 const double* __restrict__ cwr = nullptr) {
+                                                 const double* __restrict__ cwr = nullptr,
+                                                 const double* __restrict__ ulr = nullptr) {
   const ffddp_robot& rb = C.rb;
   const int li = g8_lane();
   const bool J = li < NQ;
@@ -558,7 +562,12 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
         cj += wt(FFDDP_CW_TAU, C.w_tau) * (0.5 * r * r);
         if (C.has_tsoft) {
           double ai, Ar, Arr;
-          barrier(u, C.ts_lb[ji], C.ts_ub[ji], ai, Ar, Arr);
+          if constexpr (UL) {
+            const double tsub = ulr[4 * ji + 1];
+            barrier(u, -tsub, tsub, ai, Ar, Arr);
+          } else {
+            barrier(u, C.ts_lb[ji], C.ts_ub[ji], ai, Ar, Arr);
+          }
           du += wt(FFDDP_CW_TAU_SOFT_LIMITS, C.w_ts) * Arr;
           gu += wt(FFDDP_CW_TAU_SOFT_LIMITS, C.w_ts) * Ar;
           cj += wt(FFDDP_CW_TAU_SOFT_LIMITS, C.w_ts) * ai;

@@ -162,6 +162,12 @@ static_assert(FFDDP_CW_FRICTION_CONE < LS_CW && FFDDP_CW_JOINT0 + LS_CW <= FFDDP
 struct LsW {
   double w[LS_CW];
 };
+// A joint lane's entries of its instance's torque-limit row (ffddp.h
+// FFDDP_TAU_LIM_W), loaded once before the node loop: LaneK is per block, and
+// a block's groups belong to different instances.
+struct LsL {
+  double uub, tsub, wslim;
+};
 
 // friction-cone cost (ffddp_node.hpp friction_cone, value only); CW: the weight is W's entry
 template <bool CW>
@@ -257,8 +263,10 @@ template <bool ROW> __device__ __forceinline__ double ls_bwd(const double (&Lt)[
 // row) instead of C's; W is unused otherwise.  On a joint lane the EE terms
 // (and on the EE lane the joint terms) are then formed with the other role's
 // entries and discarded, as they are discarded without CW.
-template <int NC, bool ROW, bool FR = false, bool CW = false>
-__device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, const LaneK& K, const LsW& W, int mode, bool surface, double q,
+// UL: the torque soft-limit barrier's bounds are +-L.tsub (the instance's
+// torque-limit row) instead of K's; L is unused otherwise.
+template <int NC, bool ROW, bool FR = false, bool CW = false, bool UL = false>
+__device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, const LaneK& K, const LsW& W, const LsL& L, int mode, bool surface, double q,
                                              double v, double u, double xq, double xv, double tr, const double* ref,
                                              double fnr, double& qn, double& vn, double& cpart, double (&lam)[3]
 #ifdef FFDDP_PHASE_PROF
@@ -418,7 +426,7 @@ __device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, co
     if (!terminal && (fl & RF_TAU)) {
       const double r = u - tr;
       cj = fma(wj(FFDDP_CW_TAU, C.w_tau), 0.5 * (r * r), cj);
-      if (fl & RF_TSOFT) cj = fma(wj(FFDDP_CW_TAU_SOFT_LIMITS, C.w_ts), ls_barrier(u, K.tslb, K.tsub), cj);
+      if (fl & RF_TSOFT) cj = fma(wj(FFDDP_CW_TAU_SOFT_LIMITS, C.w_ts), ls_barrier(u, UL ? -L.tsub : K.tslb, UL ? L.tsub : K.tsub), cj);
     }
   }
   lam[0] = lam[1] = lam[2] = 0.0;

@@ -68,6 +68,10 @@ SYMBOLS = (
     "ffddp_fleet_metrics_fref_dev",
     "ffddp_solve_batch_wts_dev",
     "ffddp_calc_diff_wts",
+    "ffddp_solve_batch_lim_dev",
+    "ffddp_calc_diff_lim",
+    "ffddp_torque_limit_rows",
+    "ffddp_fleet_post_lim_dev",
 )
 PLANT_OBS = 69
 # FFDDP_PLANT_ROW_*: one instance's physics row (ffddp_plant_set_instance_params)
@@ -173,6 +177,10 @@ COST_INDEX = {
     "w_posture": 16, "w_v": 17, "w_q_soft_limits": 18, "w_tau": 19, "w_tau_soft_limits": 20, "w_y": 21, "w_w": 22,
     "w_w_soft_limits": 23,
 }
+
+# FFDDP_TAU_LIM_W: one instance's torque-limit row (ffddp_solve_batch_lim_dev), joint-major: entry 4j u_ub[j],
+# 4j + 1 ts_ub[j], 4j + 2 ws_lim[j], the rest padding (config.torque_limit_rows builds rows)
+TAU_LIM_W = 32
 
 FLEET_FORCE_W = 4  # FFDDP_FLEET_FORCE_W: doubles per force record, f0, f1, t_on, t_ramp (trajectory.force_records)
 
@@ -456,6 +464,13 @@ def load() -> C.CDLL:
     lib.ffddp_solve_batch_wts_dev.restype = C.c_int
     lib.ffddp_calc_diff_wts.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, up, dp, dp, dp, dp] + [dp] * 10
     lib.ffddp_calc_diff_wts.restype = C.c_int
+    # ..., stats, active, force_ref, cost_w, tau_lim, stream
+    lib.ffddp_solve_batch_lim_dev.argtypes = dev_args[:-1] + [vp, vp, vp, vp, vp]
+    lib.ffddp_solve_batch_lim_dev.restype = C.c_int
+    lib.ffddp_calc_diff_lim.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, up, dp, dp, dp, dp, dp] + [dp] * 10
+    lib.ffddp_calc_diff_lim.restype = C.c_int
+    lib.ffddp_torque_limit_rows.argtypes = [C.POINTER(OcpConfig), C.c_int, dp, dp]
+    lib.ffddp_torque_limit_rows.restype = C.c_int
     lib.ffddp_frame_placement.argtypes = [C.POINTER(Robot), dp, dp, dp]
     lib.ffddp_frame_placement.restype = C.c_int
     lib.ffddp_gravity_torque.argtypes = [C.POINTER(Robot), C.c_int, dp, dp]
@@ -511,6 +526,9 @@ def load() -> C.CDLL:
     lib.ffddp_fleet_pre_sched_dev.restype = C.c_int
     lib.ffddp_fleet_post_sched_dev.argtypes = lib.ffddp_fleet_post_dev.argtypes[:-1] + [FleetSched, vp]
     lib.ffddp_fleet_post_sched_dev.restype = C.c_int
+    # per-instance torque limits: const ffddp_fleet_sched* (NULL = unscheduled), tau_lim, stream
+    lib.ffddp_fleet_post_lim_dev.argtypes = lib.ffddp_fleet_post_dev.argtypes[:-1] + [C.POINTER(FleetSched), vp, vp]
+    lib.ffddp_fleet_post_lim_dev.restype = C.c_int
     fi = [C.c_void_p, C.c_int, C.POINTER(FleetInject), C.c_int]
     lib.ffddp_fleet_inject_obs_dev.argtypes = fi + [vp, vp, vp, C.c_int, vp, vp, vp, vp] + [vp]
     lib.ffddp_fleet_inject_obs_dev.restype = C.c_int

@@ -146,6 +146,28 @@ def cost_weight_row(cfg, variant: str = None, **overrides) -> np.ndarray:
     return row
 
 
+def torque_limit_rows(cfg, limits) -> np.ndarray:
+    """(B, _abi.TAU_LIM_W) float64: the torque-limit rows of a solve's
+    ``torque_limits`` (ffddp_solve_batch_lim_dev) for `limits` of shape (B, 7),
+    instance b's tau_limits, built by the library's own code
+    (ffddp_torque_limit_rows) from `cfg`'s tau_soft_limit_margin.  A row of
+    cfg.tau_limits repeats the handle's constants.  A limit that is not finite
+    and > 0, or another shape, raises ValueError."""
+    import ctypes as C
+
+    lim = np.ascontiguousarray(limits, dtype=np.float64)
+    if lim.ndim != 2 or lim.shape[1] != 7:
+        raise ValueError(f"torque_limit_rows: limits must have shape (B, 7), not {lim.shape}")
+    if not (np.all(np.isfinite(lim)) and np.all(lim > 0.0)):
+        raise ValueError("torque_limit_rows: limits must be finite and > 0")
+    st = cfg.to_struct() if hasattr(cfg, "to_struct") else cfg
+    rows = np.zeros((lim.shape[0], _abi.TAU_LIM_W))
+    rc = _abi.load().ffddp_torque_limit_rows(C.byref(st), int(lim.shape[0]), _abi.dptr(lim), _abi.dptr(rows))
+    if rc:
+        raise ValueError(f"ffddp_torque_limit_rows failed ({rc})")
+    return rows
+
+
 def classical_preset(horizon: int = 30, contact_model: str = "normal_1d") -> OcpConfig:
     """run_classical.py:269-315 (benchmark mode).  The reference preset uses N=36; BASELINE uses 30 (R9)."""
     return OcpConfig(variant="classical", horizon=horizon, contact_model=contact_model)

@@ -630,6 +630,30 @@ def sweep_cost_weights(seed, weight_spread: dict) -> dict:
     return out
 
 
+def check_limit_spread(limit_spread) -> Tuple[float, float]:
+    """run_sweep's limit_spread, checked: (lo, hi), finite, 0 < lo <= hi (ValueError otherwise)."""
+    try:
+        rng_ = tuple(float(x) for x in limit_spread)
+    except TypeError:
+        rng_ = ()
+    if len(rng_) != 2 or not all(np.isfinite(rng_)) or not 0.0 < rng_[0] <= rng_[1]:
+        raise ValueError(f"run_sweep: limit_spread is (lo, hi), 0 < lo <= hi, not {limit_spread!r}")
+    return rng_
+
+
+def sweep_limit_scales(seed, limit_spread) -> np.ndarray:
+    """The sweep's per-instance torque-limit scales (B,): instance b's scale is
+    lo (hi / lo)^((1 + u) / 2), log-uniform in [lo, hi], with u one uniform in
+    [-1, 1] from default_rng([seed_b, 6]) -- a generator of its own, so no
+    other draw of the sweep moves."""
+    lo_, hi_ = check_limit_spread(limit_spread)
+    out = np.zeros(len(seed))
+    for b, s_ in enumerate(seed):
+        u = np.random.default_rng([int(s_), 6]).uniform(-1.0, 1.0)
+        out[b] = lo_ * (hi_ / lo_) ** (0.5 * (1.0 + u))
+    return out
+
+
 def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilted_15", "actuation_uncertainty"),
               seeds: int = 256, total_time: float = 4.0, rank: int = 0, world: int = 1, device: int = 0,
               q_sigma: float = 0.02, verbose: bool = True, record: Sequence[int] = (),
@@ -641,7 +665,8 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
               plant_spread: Optional[Tuple[float, float]] = None,
               uncertainty_spread: Optional[Tuple[float, int]] = None,
               force_spread: Optional[Tuple[float, float]] = None, force_ramp: Optional[float] = None,
-              weight_spread: Optional[dict] = None) -> dict:
+              weight_spread: Optional[dict] = None,
+              limit_spread: Optional[Tuple[float, float]] = None) -> dict:
     """Closed-loop sweep of len(scenarios) * seeds instances; this rank runs
     its contiguous shard.  Returns per-instance summary arrays (this shard).
     record: shard-local instance indices whose controller inputs (the plant
@@ -726,7 +751,15 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     with one u uniform in [-1, 1] per name, in the names' sorted order, from
     default_rng([seed_b, 5]) (sweep_cost_weights; the other draws do not
     move).  The summary carries ``weights`` ({name: (B,) drawn values}) and
-    ``cost_rows`` (B, COST_W), the rows the solves took."""
+    ``cost_rows`` (B, COST_W), the rows the solves took.
+    limit_spread (with device_loop only, NotImplementedError otherwise: the
+    host fleets solve within the configuration's limits): each instance's own
+    torque authority (DeviceFleetLoop(torque_limits=...)).  limit_spread =
+    (lo, hi), 0 < lo <= hi: instance b's tau_limits are the configuration's
+    times lo (hi / lo)^((1 + u) / 2), log-uniform, u uniform in [-1, 1] from
+    default_rng([seed_b, 6]) (sweep_limit_scales; the other draws do not
+    move).  The summary carries ``limit_scale`` (B,), the drawn scales, and
+    ``tau_limits`` (B, 7), the limits the solves and the command clip took."""
     variant = str(variant).strip().lower()
     if variant not in ("classical", "ff"):
         raise ValueError(f"run_sweep: unknown variant {variant!r}")
@@ -774,6 +807,11 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
         if not device_loop:
             raise NotImplementedError("run_sweep: weight_spread needs device_loop=True "
                                       "(the host fleets solve with the configuration's weights)")
+    if limit_spread is not None:
+        limit_spread = check_limit_spread(limit_spread)
+        if not device_loop:
+            raise NotImplementedError("run_sweep: limit_spread needs device_loop=True "
+                                      "(the host fleets solve within the configuration's limits)")
     device_refs = bool(device_refs) or task_spread is not None or stagger > 0
     if device_refs and not device_loop:
         raise NotImplementedError("run_sweep: device_refs, task_spread and stagger need device_loop=True "
@@ -848,7 +886,8 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
                                 command_filter, tasks, device_summary, keep_logs, physics,
                                 allow_plant_fail=plant_spread is not None or uncertainty_spread is not None,
                                 force_profiles=profiles,
-                                weights=sweep_cost_weights(seed, weight_spread) if weight_spread else None)
+                                weights=sweep_cost_weights(seed, weight_spread) if weight_spread else None,
+                                limit_scale=sweep_limit_scales(seed, limit_spread) if limit_spread else None)
         out.update(names=names, seed=seed, shard=(lo, hi), n_all=n_all)
         return out
     plant = BatchedPlant(B, timestep=0.001, n_substeps=5, device=device, physics=physics)
@@ -990,7 +1029,7 @@ DEVICE_MEMORY: dict = {}  # the last device-loop sweep's memory figures (tools/s
 def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, total_time, neg_step_rule, device, t_cp,
                       verbose, ucfgs=None, noise=None, solve_period=1, command_filter=False, tasks=None,
                       device_summary=False, keep_logs=True, plant_physics=None, allow_plant_fail=False,
-                      force_profiles=None, weights=None) -> dict:
+                      force_profiles=None, weights=None, limit_scale=None) -> dict:
     """run_sweep's loop on the device (fleet_loop.DeviceFleetLoop) and the
     host path's summary from the downloaded logs.  tasks: per-instance
     FleetTasks in place of traj; the summary's reference position and its
@@ -1001,7 +1040,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     one ForceProfile (or None) per instance; the force error is then against
     each instance's own reference at the sample's series time.  weights:
     {name: (B,) values} (sweep_cost_weights), each instance's own cost weights
-    over the configuration's."""
+    over the configuration's.  limit_scale: (B,) scales (sweep_limit_scales) of
+    the configuration's tau_limits, each instance's own torque limits."""
     import torch
 
     from .fleet_loop import DeviceFleetLoop
@@ -1021,7 +1061,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
                            t_contact_phase=float(t_cp) if device_summary and tasks is None else None,
                            plant_physics=plant_physics, force_profiles=force_profiles,
                            cost_weights=None if weights is None else
-                           [{name: float(v[b]) for name, v in weights.items()} for b in range(B)])
+                           [{name: float(v[b]) for name, v in weights.items()} for b in range(B)],
+                           torque_limits=None if limit_scale is None else np.asarray(limit_scale, float))
     wall0 = time.perf_counter()
     loop.run(steps)
     torch.cuda.synchronize(loop.dev)
@@ -1051,6 +1092,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
             out["force_rec"] = r["force_rec"]
         if weights is not None:
             out.update(weights=weights, cost_rows=r["cost_rows"])
+        if limit_scale is not None:
+            out.update(limit_scale=np.asarray(limit_scale, float), tau_limits=loop.tau_limits)
         if tasks is not None and keep_logs:
             out.update(solved=r["solved"], surface=r["surface"] != 0)
         return out
@@ -1091,6 +1134,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
         out["force_rec"] = r["force_rec"]
     if weights is not None:
         out.update(weights=weights, cost_rows=r["cost_rows"])
+    if limit_scale is not None:
+        out.update(limit_scale=np.asarray(limit_scale, float), tau_limits=loop.tau_limits)
     if tasks is not None:
         out.update(solved=r["solved"], surface=r["surface"] != 0)  # (ticks, B): the per-tick solve share
     return out

@@ -86,6 +86,15 @@ takes them, whatever else the loop runs; there is no launch more per tick and
 ``state`` / ``load_state`` carry nothing for them.  Without the argument the
 loop enqueues exactly the calls it did.
 
+With ``torque_limits`` every instance solves, and is commanded, within its own
+torque limits (ffddp_solve_batch_lim_dev, ffddp_fleet_post_lim_dev): a (B, 7)
+array of limits, or one scalar per instance that scales the configuration's
+``tau_limits``.  The rows (config.torque_limit_rows) are uploaded once and
+every tick's solve and post take them, scheduled or not, together with every
+other per-instance option; there is no launch more per tick and ``state`` /
+``load_state`` carry nothing for them.  Without the argument the loop enqueues
+exactly the calls it did.
+
 Not on the device, and so not supported here: ``run_sweep``'s ``record`` and
 any per-tick host callback; ``tick()`` lets a caller look between ticks at the price of its own
 synchronisation.
@@ -98,7 +107,7 @@ import numpy as np
 
 from . import _abi
 from . import robot as R
-from .config import cost_weight_row
+from .config import cost_weight_row, torque_limit_rows
 from .controller import ff_filter_alpha
 from .fleet import Traj, fleet_ocp_config, node_ref, site_calibration
 from .trajectory import FleetTask, ForceProfile, force_records, task_records
@@ -198,6 +207,26 @@ def cost_weight_rows(ocp, variant: str, cost_weights, B: int) -> np.ndarray:
     return np.stack([cost_weight_row(ocp, variant, **(e or {})) for e in entries])
 
 
+def instance_torque_limits(tau_limits, torque_limits, B: int) -> np.ndarray:
+    """DeviceFleetLoop's ``torque_limits`` as (B, 7) float64 limits: a (B, 7)
+    array is taken as it is, a length-B sequence of scalars scales the
+    configuration's `tau_limits`.  Another shape, or a value that is not finite
+    and > 0, raises ValueError.  Host only: needs no device."""
+    a = np.array(torque_limits, dtype=np.float64)
+    if a.shape == (int(B), 7):
+        lim = a
+    elif a.shape == (int(B),):
+        if not (np.all(np.isfinite(a)) and np.all(a > 0.0)):
+            raise ValueError("DeviceFleetLoop: torque_limits scales must be finite and > 0")
+        lim = a[:, None] * np.asarray(tau_limits, dtype=np.float64).reshape(1, 7)
+    else:
+        raise ValueError(f"DeviceFleetLoop: torque_limits takes a (B, 7) array of limits or B scalars that scale the "
+                         f"configuration's, not shape {a.shape}")
+    if not (np.all(np.isfinite(lim)) and np.all(lim > 0.0)):
+        raise ValueError("DeviceFleetLoop: torque_limits must be finite and > 0")
+    return np.ascontiguousarray(lim)
+
+
 class DeviceFleetLoop:
     """B closed loops (plant + controller) resident on one device.
 
@@ -238,6 +267,9 @@ class DeviceFleetLoop:
     entry per instance, a dict of overrides for config.cost_weight_row
     (``{"w_fn": 40.0}``) or None (the configuration's weights); ``cost_rows``
     (B, COST_W) keeps the rows as uploaded.
+    torque_limits: None, a (B, 7) array of torque limits, or B scalars that
+    scale the configuration's tau_limits; ``tau_limits`` (B, 7) keeps the
+    limits and ``limit_rows`` (B, TAU_LIM_W) the rows as uploaded.
 
     ``S``: the controller state, ``T``: the solve's arrays, ``P``: the plant's
     (q, v, obs, tau_app, tau_filt, plane), ``J``: the injector's (row, a, b,
@@ -253,10 +285,14 @@ class DeviceFleetLoop:
                  max_table_bytes: int = 1 << 30, solve_period: Optional[int] = None,
                  tasks: Optional[Sequence[FleetTask]] = None, metrics: bool = False, logs: bool = True,
                  t_contact_phase=None, plant_physics=None,
-                 force_profiles: Optional[Sequence[Optional[ForceProfile]]] = None, cost_weights=None):
+                 force_profiles: Optional[Sequence[Optional[ForceProfile]]] = None, cost_weights=None,
+                 torque_limits=None):
         variant = str(variant).strip().lower()
         if variant not in ("classical", "ff"):
             raise ValueError(f"DeviceFleetLoop: unknown variant {variant!r}")
+        inst_limits = None
+        if torque_limits is not None:
+            inst_limits = instance_torque_limits(config.tau_limits, torque_limits, B)
         metrics, logs = bool(metrics), bool(logs)
         if not logs and not metrics:
             raise ValueError("DeviceFleetLoop: logs=False needs metrics=True (a run without either reports nothing)")
@@ -398,6 +434,12 @@ class DeviceFleetLoop:
         if cost_weights is not None:
             self.cost_rows = cost_weight_rows(self.solver.cfg, variant, cost_weights, B)
             self.cw = up(self.cost_rows)
+        # per-instance torque limits (ffddp_solve_batch_lim_dev, ffddp_fleet_post_lim_dev): the rows, uploaded once
+        self.tau_limits = self.limit_rows = self.ul = None
+        if inst_limits is not None:
+            self.tau_limits = inst_limits
+            self.limit_rows = torque_limit_rows(self.solver.cfg, inst_limits)
+            self.ul = up(self.limit_rows)
         self.log_info = torch.full((rows, B, _abi.FLEET_INFO_W), float("nan"), **f64)
         self.log_obs = torch.full((rows + 1 if logs else 1, B, _abi.FLEET_LOG_W), float("nan"), **f64)
         self.log_fail = z(rows + 1, B, dtype=torch.int32)  # without logs: the start's row and the ticks'
@@ -535,12 +577,16 @@ class DeviceFleetLoop:
             fkw = dict(force_ref=self.force_ref)
         if self.cw is not None:
             fkw = dict(fkw, cost_weights=self.cw)
+        pkw = {}
+        if self.ul is not None:
+            fkw = dict(fkw, torque_limits=self.ul)
+            pkw = dict(torque_limits=self.ul)
         if self.sched is None:
             self.solver.fleet_pre_dev(T, self.params, hint, stream=self._stream, tasks=self.ktasks)
             if self.frec is not None:
                 self._force_refs()
             self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream, **fkw)
-            self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream)
+            self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream, **pkw)
         else:
             T["need"] = self.log_need[r]
             self.solver.fleet_pre_dev(T, self.params, hint, stream=self._stream, sched=self.sched, tasks=self.ktasks)
@@ -548,7 +594,7 @@ class DeviceFleetLoop:
                 self._force_refs()
             self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream,
                                   active=T["need"], **fkw)
-            self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream, sched=self.sched)
+            self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream, sched=self.sched, **pkw)
         if self.inject is not None:
             self.solver.fleet_inject_cmd_dev(self.J, self.inject, k, stream=self._stream, rows=self.inject_rows)
         self._stepped = False

@@ -299,7 +299,7 @@ class BatchedBoxFDDP:
 
     # -- solve (device-resident torch tensors; bench path) ---------------------------
     def solve_dev(self, t, maxiter: int = 10, is_feasible: bool = False, stream=None, active=None, force_ref=None,
-                  cost_weights=None):
+                  cost_weights=None, torque_limits=None):
         """t: dict of contiguous torch.cuda tensors with keys x0, node_ref, inst_ref,
         surface (uint8), xs_init, us_init and outputs xs, us, K, cost, iters (int32),
         ok (uint8), fn_pred, stats (int32).  Asynchronous on `stream` (hipStream_t int).
@@ -313,10 +313,14 @@ class BatchedBoxFDDP:
         cost_weights: optional (B, _abi.COST_W) float64 device tensor, one row of
         scalar cost weights per instance in place of the configuration's
         (ffddp_solve_batch_wts_dev; config.cost_weight_row builds a row); goes
-        with or without `active` and `force_ref`."""
+        with or without `active` and `force_ref`.
+        torque_limits: optional (B, _abi.TAU_LIM_W) float64 device tensor, one
+        torque-limit row per instance in place of the configuration's
+        tau_limits (ffddp_solve_batch_lim_dev; config.torque_limit_rows builds
+        the rows); goes with or without the other three."""
         B = int(t["x0"].shape[0])
         p = lambda k: C.c_void_p(int(t[k].data_ptr()))
-        rc = self._lib.ffddp_solve_batch_wts_dev(
+        rc = self._lib.ffddp_solve_batch_lim_dev(
             self._h, B, p("x0"), p("node_ref"), p("inst_ref"), p("surface"), p("xs_init"), p("us_init"),
             int(maxiter), int(bool(is_feasible)), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
             p("fn_pred"), p("stats"),
@@ -325,9 +329,11 @@ class BatchedBoxFDDP:
                          "force_ref must be a contiguous (B, N+1) float64 device tensor"),
             _opt_dev_ptr(cost_weights, "float64", (B, _abi.COST_W),
                          "cost_weights must be a contiguous (B, COST_W) float64 device tensor"),
+            _opt_dev_ptr(torque_limits, "float64", (B, _abi.TAU_LIM_W),
+                         "torque_limits must be a contiguous (B, TAU_LIM_W) float64 device tensor"),
             C.c_void_p(stream if stream else 0),
         )
-        self._check(rc, "ffddp_solve_batch_wts_dev")
+        self._check(rc, "ffddp_solve_batch_lim_dev")
 
     # -- fleet tick glue (include/ffddp.h: ffddp_fleet_warm_start_dev / ffddp_fleet_keep_dev) --
     def fleet_warm_start_dev(self, t, stream=None):
@@ -502,7 +508,7 @@ class BatchedBoxFDDP:
         self._check(rc, "ffddp_fleet_pre_dev")
 
     def fleet_post_dev(self, t, params: _abi.FleetParams, lpf: float = 0.0, stream=None,
-                       sched: _abi.FleetSched = None):
+                       sched: _abi.FleetSched = None, torque_limits=None):
         """Everything a fleet tick does after solve_dev(t): keep, torque policy,
         unstable fallback and _safe_tau -> t["tau_cmd"] (B, 7), t["info"]
         (B, _abi.FLEET_INFO_W; fields _abi.FLEET_INFO_FIELDS) and the state.
@@ -511,7 +517,10 @@ class BatchedBoxFDDP:
         `lpf`, t["log_obs"] (B, _abi.FLEET_LOG_W) from the plant records
         t["obs"].  sched: the scheduled tick (ffddp_fleet_post_sched_dev), after
         solve_dev(t, active=t["need"]); reads t["need"], updates t["since"] and
-        t["age"].  Asynchronous on `stream`."""
+        t["age"].  torque_limits: optional (B, _abi.TAU_LIM_W) float64 device
+        tensor, the solve's torque-limit rows: the clips use each instance's own
+        limit (ffddp_fleet_post_lim_dev), scheduled or not.  Asynchronous on
+        `stream`."""
         B = int(t["x0"].shape[0])
         p = lambda k: C.c_void_p(int(t[k].data_ptr()) if t.get(k) is not None else 0)
         st = self._fleet_state(t)
@@ -520,6 +529,14 @@ class BatchedBoxFDDP:
                 p("fn_pred"), p("stats"), p("x0"), p("surface"), p("tau_bias"), int(t["tau_bias"].stride(0)),
                 p("tau_cmd"), p("info"), p("scale"), p("tau_app"), p("tau_filt"), float(lpf), p("obs"),
                 int(obs.stride(0)) if obs is not None else 0, p("log_obs"))
+        if torque_limits is not None:
+            sp = C.byref(self._fleet_sched(t, sched)) if sched is not None else None
+            rc = self._lib.ffddp_fleet_post_lim_dev(
+                *args, sp, _opt_dev_ptr(torque_limits, "float64", (B, _abi.TAU_LIM_W),
+                                        "torque_limits must be a contiguous (B, TAU_LIM_W) float64 device tensor"),
+                C.c_void_p(stream if stream else 0))
+            self._check(rc, "ffddp_fleet_post_lim_dev")
+            return
         if sched is not None:
             rc = self._lib.ffddp_fleet_post_sched_dev(*args, self._fleet_sched(t, sched), C.c_void_p(stream if stream else 0))
             self._check(rc, "ffddp_fleet_post_sched_dev")
@@ -662,11 +679,13 @@ class BatchedBoxFDDP:
         return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(_abi.KERNEL_CLASSES)}
 
     # -- problem.calcDiff(xs, us) -------------------------------------------------------
-    def calc_diff(self, batch, xs, us, force_ref=None, cost_weights=None):
+    def calc_diff(self, batch, xs, us, force_ref=None, cost_weights=None, torque_limits=None):
         """force_ref: optional (B, N+1) host array, the desired normal contact
         force per instance and node (ffddp_calc_diff_fref).  cost_weights:
         optional (B, _abi.COST_W) host array, the scalar cost weights per
-        instance (ffddp_calc_diff_wts)."""
+        instance (ffddp_calc_diff_wts).  torque_limits: optional
+        (B, _abi.TAU_LIM_W) host array, the torque-limit rows per instance
+        (ffddp_calc_diff_lim)."""
         B = int(batch.x0.shape[0])
         N, nx = self.N, self.nx
         f = lambda a, shape: np.ascontiguousarray(np.asarray(a, np.float64).reshape(shape))
@@ -677,7 +696,7 @@ class BatchedBoxFDDP:
             lam=np.zeros((B, N + 1, 3)),
         )
         d = _abi.dptr
-        fr = cw = None
+        fr = cw = ul = None
         if force_ref is not None:
             fr = np.asarray(force_ref, np.float64)
             if fr.shape != (B, N + 1):
@@ -688,14 +707,20 @@ class BatchedBoxFDDP:
             if cw.shape != (B, _abi.COST_W):
                 raise ValueError("cost_weights must have shape (B, COST_W)")
             cw = np.ascontiguousarray(cw)
-        rc = self._lib.ffddp_calc_diff_wts(
+        if torque_limits is not None:
+            ul = np.asarray(torque_limits, np.float64)
+            if ul.shape != (B, _abi.TAU_LIM_W):
+                raise ValueError("torque_limits must have shape (B, TAU_LIM_W)")
+            ul = np.ascontiguousarray(ul)
+        rc = self._lib.ffddp_calc_diff_lim(
             self._h, B, d(f(batch.x0, (B, nx))), d(f(batch.node_ref, (B, N + 1, 6))), d(f(batch.inst_ref, (B, 21))),
             _abi.uptr(np.ascontiguousarray(np.asarray(batch.surface, np.uint8))), d(f(xs, (B, N + 1, nx))),
-            d(f(us, (B, N, 7))), d(fr) if fr is not None else None, d(cw) if cw is not None else None, d(out["Fx"]),
+            d(f(us, (B, N, 7))), d(fr) if fr is not None else None, d(cw) if cw is not None else None,
+            d(ul) if ul is not None else None, d(out["Fx"]),
             d(out["Fu"]), d(out["Lx"]), d(out["Lu"]), d(out["Lxx"]), d(out["Lxu"]), d(out["Luu"]), d(out["cost"]),
             d(out["xnext"]), d(out["lam"]),
         )
-        self._check(rc, "ffddp_calc_diff_wts")
+        self._check(rc, "ffddp_calc_diff_lim")
         return out
 
 

@@ -240,7 +240,8 @@ int ffddp_solve_batch_fref_dev(ffddp_handle* h, int B, const double* x0, const d
  * be finite and >= 0; the rows are device memory, which the library cannot
  * check.  The weight vectors (ori_weights, v_damp_weights, y_weights, ...),
  * the activation bounds and margins, fn_des (per node through force_ref), the
- * contact gains, tau_limits and the solver constants stay the handle's.
+ * contact gains, tau_limits (per instance through ffddp_solve_batch_lim_dev)
+ * and the solver constants stay the handle's.
  *
  * Only the source of each weight changes, not the order or grouping of the
  * arithmetic, and the terminal node uses the same row: rows that repeat the
@@ -276,6 +277,45 @@ int ffddp_solve_batch_wts_dev(ffddp_handle* h, int B, const double* x0, const do
                               const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
                               double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
                               const uint8_t* active, const double* force_ref, const double* cost_w, void* stream);
+
+/* ffddp_solve_batch_wts_dev with the torque limits per instance: tau_lim is
+ * [B][FFDDP_TAU_LIM_W] device doubles, row b what the OCP of instance b derives
+ * from its own tau_limits.  A row is 32 doubles (256 bytes), joint-major, so
+ * that joint j's values are one aligned 32-byte read of its lane:
+ *     4j + 0   u_ub[j]   = tau_limits[j]         the BoxQP bound, the rollout's clamp
+ *     4j + 1   ts_ub[j]  = tau_limits[j] - mg    the torque soft-limit barrier's bound
+ *     4j + 2   ws_lim[j]                         the force-feedback w soft limit
+ *     4j + 3, 28..31     padding, which the library may load and never uses
+ * mg is the configuration's tau_soft_limit_margin clamped below the instance's
+ * smallest limit.  The lower bounds are the exact negations and the kernels
+ * form them so.  ffddp_torque_limit_rows builds rows on the host with the code
+ * that fills the handle's constants, so rows of the configuration's limits
+ * give the bits of the call without tau_lim.
+ *
+ * Which terms exist stays the handle's (use_box, w_tau_soft_limits > 0,
+ * w_w_soft_limits > 0, the variant): the entry of a term the handle does not
+ * build never enters the arithmetic, so any value there, NaN included, changes
+ * nothing.  Rows of unselected instances are not read.  `active`, force_ref
+ * and cost_w stay optional and combine freely with tau_lim (without cost_w the
+ * solve reads rows of the configuration's weights that the handle keeps,
+ * allocated by the first such call; likewise fn_des without a force_ref).
+ * tau_lim == NULL is ffddp_solve_batch_wts_dev: same kernels, same bits.
+ * Errors are ffddp_solve_batch_wts_dev's.  The bounds' margins, the weights
+ * and the solver constants stay the handle's; the host-pointer entry point and
+ * solve plans take no limits. */
+#define FFDDP_TAU_LIM_W 32
+int ffddp_solve_batch_lim_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                              const double* inst_ref, const uint8_t* surface, const double* xs_init,
+                              const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
+                              double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
+                              const uint8_t* active, const double* force_ref, const double* cost_w,
+                              const double* tau_lim, void* stream);
+
+/* Host function: rows [B][FFDDP_TAU_LIM_W] for ffddp_solve_batch_lim_dev /
+ * ffddp_fleet_post_lim_dev from tau_limits [B][7] and cfg's
+ * tau_soft_limit_margin (the only field read).  FFDDP_E_INVALID for a null
+ * pointer, B < 0, or a limit that is not finite and > 0. */
+int ffddp_torque_limit_rows(const ffddp_ocp_config* cfg, int B, const double* tau_limits, double* rows);
 
 /* Solve plan for a receding-horizon loop: one solve of a fixed batch per
  * control tick (crocoddyl_classical.py:367 called every tick at
@@ -343,6 +383,14 @@ int ffddp_calc_diff_wts(ffddp_handle* h, int B, const double* x0, const double* 
                         const double* inst_ref, const uint8_t* surface, const double* xs,
                         const double* us, const double* force_ref, const double* cost_w, double* Fx,
                         double* Fu, double* Lx, double* Lu, double* Lxx, double* Lxu, double* Luu,
+                        double* cost, double* xnext, double* lam);
+
+/* ffddp_calc_diff_wts with host torque-limit rows [B][FFDDP_TAU_LIM_W]
+ * (ffddp_solve_batch_lim_dev's array; NULL: ffddp_calc_diff_wts). */
+int ffddp_calc_diff_lim(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                        const double* inst_ref, const uint8_t* surface, const double* xs,
+                        const double* us, const double* force_ref, const double* cost_w, const double* tau_lim,
+                        double* Fx, double* Fu, double* Lx, double* Lu, double* Lxx, double* Lxu, double* Luu,
                         double* cost, double* xnext, double* lam);
 
 /* Host-side setup helpers (CPU, same model code): frame placement of the EE
@@ -627,6 +675,20 @@ int ffddp_fleet_post_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params*
                                double* tau_cmd, double* info, const double* scale, double* tau_app, double* tau_filt,
                                double lpf, const double* obs, int ld_obs, double* log_obs, ffddp_fleet_sched sched,
                                void* stream);
+/* The post stage with each instance's own torque limit: tau_lim is the solve's
+ * [B][FFDDP_TAU_LIM_W] rows (ffddp_solve_batch_lim_dev), of which entry 4i of
+ * row b replaces p->tau_limits[i] in _command's clip and in the filter's final
+ * clip, so a derated instance is never commanded beyond what its solver
+ * planned for.  sched as in ffddp_fleet_pre_task_dev: NULL is the unscheduled
+ * tick.  tau_lim == NULL gives ffddp_fleet_post_dev's / _post_sched_dev's bits.
+ * Errors are theirs, under this function's name. */
+int ffddp_fleet_post_lim_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                             const double* xs, const double* us, const double* K, const double* cost,
+                             const int32_t* iters, const uint8_t* ok, const double* fn_pred, const int32_t* stats,
+                             const double* x0, const uint8_t* surface, const double* tau_bias, int ld_tau_bias,
+                             double* tau_cmd, double* info, const double* scale, double* tau_app, double* tau_filt,
+                             double lpf, const double* obs, int ld_obs, double* log_obs,
+                             const ffddp_fleet_sched* sched, const double* tau_lim, void* stream);
 
 /* The closed-loop sweep's actuation-uncertainty injector on the device
  * (ffddp/uncertainty.py BatchedUncertaintyInjector, bit for bit): two more

@@ -26,6 +26,8 @@ wall time, closed-loop ticks/s).
                                                                # a force setpoint per instance, ramped in after touchdown
   python tools/sweep_c4.py --device-loop 1 --device-refs 1 --weight-spread w_fn 7 112 --weight-spread w_tau 2e-4 3.2e-3
                                                                # the controller's cost weights per instance, log-uniform
+  python tools/sweep_c4.py --device-loop 1 --device-refs 1 --limit-spread 0.25 1
+                                                               # the torque limits per instance, scaled log-uniformly
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/sweep_c4.py
 """
 import argparse
@@ -102,6 +104,9 @@ def build_parser():
     ap.add_argument("--weight-spread", nargs=3, action="append", default=None, metavar=("NAME", "LO", "HI"),
                     help="with --device-loop 1, repeatable: cost weight NAME (w_fn, w_tangent_pos, w_tau, ...) per "
                          "instance, log-uniform in [LO, HI]")
+    ap.add_argument("--limit-spread", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="with --device-loop 1: per-instance torque limits, the configuration's scaled log-uniformly "
+                         "in [LO, HI]")
     ap.add_argument("--scenarios", nargs="+", default=list(ALL_SCENARIOS), help="scenarios to sweep (default: all 5)")
     return ap
 
@@ -135,7 +140,8 @@ def main():
                            device_refs=bool(a.device_refs), task_spread=a.task_spread, stagger=a.stagger,
                            device_summary=bool(a.device_summary), keep_logs=bool(a.keep_logs),
                            plant_spread=a.plant_spread, uncertainty_spread=uspread,
-                           force_spread=a.force_spread, force_ramp=a.force_ramp, weight_spread=wspread)
+                           force_spread=a.force_spread, force_ramp=a.force_ramp, weight_spread=wspread,
+                           limit_spread=a.limit_spread)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -194,6 +200,19 @@ def main():
                          float(np.nanmean(pi["rms_tangential_error_contact_phase"][which == i])),
                      "contact_loss_contact_phase_pct": float(np.nanmean(pi["contact_loss_contact_phase_pct"][which == i]))}
                     for i in range(4) if np.any(which == i)]
+        if "limit_scale" in res:  # this rank's shard by torque-limit scale, four log-spaced bins
+            pi, sc = res["per_instance"], res["limit_scale"]
+            edges = np.geomspace(a.limit_spread[0], a.limit_spread[1], 5)
+            which = np.clip(np.digitize(sc, edges) - 1, 0, 3)
+            line.update(limit_spread=a.limit_spread, rank0_limit_bins=[
+                {"scale_lo": float(edges[i]), "scale_hi": float(edges[i + 1]), "instances": int(np.sum(which == i)),
+                 "scale_mean": float(np.mean(sc[which == i])),
+                 "fn_mean_contact_phase": float(np.nanmean(pi["fn_mean_contact_phase"][which == i])),
+                 "avg_abs_force_err": float(np.nanmean(pi["avg_abs_force_err"][which == i])),
+                 "rms_tangential_error_contact_phase":
+                     float(np.nanmean(pi["rms_tangential_error_contact_phase"][which == i])),
+                 "contact_loss_contact_phase_pct": float(np.nanmean(pi["contact_loss_contact_phase_pct"][which == i]))}
+                for i in range(4) if np.any(which == i)])
         # instances that left the nominal regime, per scenario: any tick on the unstable fallback; a non-finite summary
         ui, ri = fleet.SUMMARY_KEYS.index("unstable_ticks"), fleet.SUMMARY_KEYS.index("rms_3d_error")
         line["diverged"] = {str(s): {"unstable_instances": int(np.sum(m[names == s, ui] > 0)),
