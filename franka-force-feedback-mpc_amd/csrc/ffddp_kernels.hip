@@ -22,7 +22,6 @@
 //               next k_node reads it and writes it into xs / us; k_commit at
 //               the end of the solve for the rest).
 #include <hip/hip_runtime.h>
-#include <sched.h>
 
 #include <cmath>
 #include <cstdio>
@@ -30,9 +29,7 @@
 #include <cstring>
 #include <new>
 #include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <functional>
 #include <mutex>
 #include <string>
@@ -41,6 +38,7 @@
 #include <vector>
 
 #include "ffddp_consts.hpp"
+#include "ffddp_copy_pool.hpp"
 #include "ffddp_group.hpp"
 #include "ffddp_inject.hpp"
 #include "ffddp_metrics.hpp"
@@ -3019,109 +3017,6 @@ struct HostIO {
   // stages that slice's pageable inputs); with it the slices are enqueued
   // one after the other instead of iteration by iteration
   std::function<int(int)> stage;
-  // optional: xs / us / K are not copied down by launch_solve_t and done[k]
-  // is not recorded there (the caller enqueues both later on ss[k], from the
-  // slice's device buffers dxs / dus / dK)
-  bool defer_out = false;
-  hipStream_t ss[8] = {};
-  const double *dxs[8] = {}, *dus[8] = {}, *dK[8] = {};
-};
-
-// Host memcpy / zero-fill pool of the host entry point: persistent threads
-// (FFDDP_COPY_THREADS, default the CPUs this process may use, at most 16)
-// that split a list of jobs into 1 MiB pieces with the calling thread.
-struct CopyJob {
-  void* dst;
-  const void* src;  // nullptr: zero-fill dst (first touch of fresh output pages)
-  size_t n;
-};
-class CopyPool {
- public:
-  explicit CopyPool(int nthreads) {
-    // no exception may cross the C ABI: with fewer threads than asked (or
-    // none) the calling thread does the rest of the copies
-    try {
-      for (int i = 1; i < nthreads; ++i) th_.emplace_back([this] { worker(); });
-    } catch (...) {
-    }
-  }
-  ~CopyPool() {
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      stop_ = true;
-    }
-    cv_.notify_all();
-    for (std::thread& t : th_) t.join();
-  }
-  int threads() const { return (int)th_.size() + 1; }
-  void run(const std::vector<CopyJob>& jobs) {
-    constexpr size_t kPiece = size_t(1) << 20;
-    std::vector<CopyJob> pieces;
-    size_t tot = 0;
-    for (const CopyJob& j : jobs) {
-      for (size_t o = 0; o < j.n; o += kPiece)
-        pieces.push_back(CopyJob{(char*)j.dst + o, j.src ? (const char*)j.src + o : nullptr, std::min(kPiece, j.n - o)});
-      tot += j.n;
-    }
-    if (pieces.empty()) return;
-    if (th_.empty() || tot < 4 * kPiece) {  // small: the calling thread alone
-      for (const CopyJob& c : pieces) exec(c);
-      return;
-    }
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      work_ = &pieces;
-      next_.store(0);
-      left_ = pieces.size();
-      ++gen_;
-    }
-    cv_.notify_all();
-    drain();
-    std::unique_lock<std::mutex> lk(mu_);
-    done_cv_.wait(lk, [&] { return left_ == 0; });
-    work_ = nullptr;
-  }
-
- private:
-  static void exec(const CopyJob& c) {
-    if (c.src)
-      std::memcpy(c.dst, c.src, c.n);
-    else
-      std::memset(c.dst, 0, c.n);
-  }
-  void drain() {
-    size_t did = 0;
-    const std::vector<CopyJob>* w = work_;
-    for (size_t i = next_++; i < w->size(); i = next_++) {
-      exec((*w)[i]);
-      ++did;
-    }
-    if (did) {
-      std::lock_guard<std::mutex> lk(mu_);
-      left_ -= did;
-      if (left_ == 0) done_cv_.notify_all();
-    }
-  }
-  void worker() {
-    uint64_t seen = 0;
-    for (;;) {
-      {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [&] { return stop_ || (gen_ != seen && work_ != nullptr); });
-        if (stop_) return;
-        seen = gen_;
-      }
-      drain();
-    }
-  }
-  std::vector<std::thread> th_;
-  std::mutex mu_;
-  std::condition_variable cv_, done_cv_;
-  const std::vector<CopyJob>* work_ = nullptr;
-  std::atomic<size_t> next_{0};
-  size_t left_ = 0;
-  uint64_t gen_ = 0;
-  bool stop_ = false;
 };
 
 struct ffddp_handle {
@@ -3538,21 +3433,15 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
     // host entry point: page-locked host memory, the slice's results go
     // down as soon as it finishes (the device entry point solved in place)
     if (io) {
-      io->ss[k] = ss;
-      io->dxs[k] = d.xs;
-      io->dus[k] = d.us;
-      io->dK[k] = d.K;
-      if (!io->defer_out) {
-        HIPCHK(h, hipMemcpyAsync(a.xs + b0 * N1 * nxl, d.xs, bxs * Bk, hipMemcpyDefault, ss));
-        HIPCHK(h, hipMemcpyAsync(a.us + b0 * (long)N * NU, d.us, bus * Bk, hipMemcpyDefault, ss));
-        HIPCHK(h, hipMemcpyAsync(a.K + b0 * (long)N * NU * nx, d.K, bks * Bk, hipMemcpyDefault, ss));
-      }
+      HIPCHK(h, hipMemcpyAsync(a.xs + b0 * N1 * nxl, d.xs, bxs * Bk, hipMemcpyDefault, ss));
+      HIPCHK(h, hipMemcpyAsync(a.us + b0 * (long)N * NU, d.us, bus * Bk, hipMemcpyDefault, ss));
+      HIPCHK(h, hipMemcpyAsync(a.K + b0 * (long)N * NU * nx, d.K, bks * Bk, hipMemcpyDefault, ss));
       for (int i = 0; i < io->n_out; ++i) {
         const size_t o = (size_t)b0 * io->out[i].per_inst;
         HIPCHK(h, hipMemcpyAsync((char*)io->out[i].host + o, (const char*)io->out[i].dev + o,
                                  (size_t)Bk * io->out[i].per_inst, hipMemcpyDeviceToHost, ss));
       }
-      if (!io->defer_out) HIPCHK(h, hipEventRecord(io->done[k], ss));
+      HIPCHK(h, hipEventRecord(io->done[k], ss));
     }
     return 0;
   };
@@ -3685,19 +3574,6 @@ bool host_pinned(const void* p) {
     return false;
   }
   return a.type == hipMemoryTypeHost;
-}
-
-// the host-copy pool's size: FFDDP_COPY_THREADS, else the CPUs this process
-// may run on (the GPU box grants 16 per GPU), at most 16
-int copy_threads() {
-  if (const char* e = std::getenv("FFDDP_COPY_THREADS")) {
-    const int v = std::atoi(e);
-    return v < 1 ? 1 : (v > 64 ? 64 : v);
-  }
-  cpu_set_t cs;
-  int n = 8;
-  if (sched_getaffinity(0, sizeof(cs), &cs) == 0) n = CPU_COUNT(&cs);
-  return n < 1 ? 1 : (n > 16 ? 16 : n);
 }
 
 bool valid_cfg(const ffddp_ocp_config& c) {
@@ -4075,12 +3951,6 @@ int ffddp_solve_batch(ffddp_handle* h, int B, const double* x0, const double* no
     any_in |= stin[i];
     io.in[io.n_in++] = HostIO::In{din[i], stin[i] ? (const void*)(h->stage + off[i]) : uin[i], per[i]};
   }
-  // FFDDP_HOSTIO_REGISTER=1: page-lock the pageable xs / us / K for the call
-  // (see below) instead of draining them through the staging buffer
-  {
-    const char* r = std::getenv("FFDDP_HOSTIO_REGISTER");
-    io.defer_out = r && std::atoi(r) != 0 && (!host_pinned(xs) || !host_pinned(us) || !host_pinned(K));
-  }
   double tst[8] = {0};
   if (any_in)
     io.stage = [&](int k) {
@@ -4130,42 +4000,6 @@ int ffddp_solve_batch(ffddp_handle* h, int B, const double* x0, const double* no
     for (int i = 0; i < 8; ++i)
       if (staged[i]) jobs.push_back(CopyJob{uout[i], nullptr, (size_t)B * per[6 + i]});
     pool.run(jobs);
-  }
-  // register mode: the (now resident) pageable xs / us / K are page-locked
-  // for this call and copied into by DMA directly, slice by slice (no host
-  // copy after the solve); an array the runtime will not register goes
-  // through the staging buffer as usual
-  struct Registered {
-    void* p[3] = {nullptr, nullptr, nullptr};
-    ~Registered() {
-      for (void* q : p)
-        if (q) (void)hipHostUnregister(q);
-    }
-  } regd;
-  if (io.defer_out) {
-    for (int i = 0; i < 3; ++i) {
-      if (!staged[i]) continue;
-      if (hipHostRegister(uout[i], (size_t)B * per[6 + i], hipHostRegisterDefault) == hipSuccess) {
-        regd.p[i] = uout[i];
-        staged[i] = false;  // DMA straight into the caller's array
-        hout[i] = uout[i];
-      } else {
-        (void)hipGetLastError();
-      }
-    }
-    for (int k = 0; k < io.ns; ++k) {
-      const size_t b0 = (size_t)io.b0[k], bk = (size_t)io.bk[k];
-      const double* dsrc[3] = {io.dxs[k], io.dus[k], io.dK[k]};
-      for (int i = 0; i < 3; ++i) {
-        const hipError_t e = hipMemcpyAsync((char*)hout[i] + b0 * per[6 + i], dsrc[i], bk * per[6 + i],
-                                            hipMemcpyDefault, io.ss[k]);
-        if (e != hipSuccess)
-          return drain_host_solve(h, fail(h, FFDDP_E_DEVICE, std::string("hipMemcpyAsync: ") + hipGetErrorString(e)));
-      }
-      const hipError_t e = hipEventRecord(io.done[k], io.ss[k]);
-      if (e != hipSuccess)
-        return drain_host_solve(h, fail(h, FFDDP_E_DEVICE, std::string("hipEventRecord: ") + hipGetErrorString(e)));
-    }
   }
   const double t3 = tm ? now() : 0.0;
   // drain the slices in the order they finish

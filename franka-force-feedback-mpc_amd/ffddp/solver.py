@@ -16,6 +16,7 @@ per-iteration record of instance 0 after each solve (ffddp.callbacks).
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import threading
 import weakref
@@ -57,14 +58,31 @@ class _RecycledPinned:
     nor unmaps ~118 MB of output pages (B = 4096), and ffddp_solve_batch
     copies into them by DMA as each slice finishes (no staging copy).  At
     most `cap` bytes are page-locked; past that solve() falls back to plain
-    numpy arrays."""
+    numpy arrays.
+
+    The finalizer can run wherever the interpreter allocates (a cyclic GC
+    pass), also inside arrays() or close() on the thread that holds the lock,
+    so it takes no lock: it only appends the block to `returned` (atomic),
+    and arrays() and close() fold `returned` into the free list under the
+    lock.  After close() nobody folds any more and the finalizer frees the
+    block itself; a block that races close() into `returned` is freed by
+    whichever of the two pops it."""
 
     def __init__(self, cap: int):
         self.cap = int(cap)
-        self.total = 0
-        self.free = {}  # nbytes -> [addresses]
+        self.total = 0  # bytes page-locked while open (under the lock)
+        self.free = {}  # nbytes -> [addresses] (under the lock)
+        self.returned = collections.deque()  # (nbytes, address) from finalizers, not yet in `free`
         self.closed = False
         self.lock = threading.Lock()
+
+    def _fold(self):
+        while True:
+            try:
+                tot, p = self.returned.popleft()
+            except IndexError:
+                return
+            self.free.setdefault(tot, []).append(p)
 
     def arrays(self, specs):
         offs, tot = {}, 0
@@ -73,6 +91,8 @@ class _RecycledPinned:
             tot += (int(np.prod(shape)) * np.dtype(dt).itemsize + 255) // 256 * 256
         tot = max(tot, 1)
         with self.lock:
+            if not self.closed:
+                self._fold()
             lst = self.free.get(tot)
             p = lst.pop() if lst else None
             if p is None and self.total + tot <= self.cap:
@@ -93,22 +113,29 @@ class _RecycledPinned:
                 for k, (shape, dt) in specs.items()}
 
     def _give_back(self, tot, p):
-        with self.lock:
-            if not self.closed:
-                self.free.setdefault(tot, []).append(p)
+        self.returned.append((tot, p))
+        if self.closed:
+            self._free_returned()
+
+    def _free_returned(self):
+        lib = _abi.load()
+        while True:
+            try:
+                _, p = self.returned.popleft()
+            except IndexError:
                 return
-            self.total -= tot
-        _abi.load().ffddp_host_free(C.c_void_p(p))
+            lib.ffddp_host_free(C.c_void_p(p))
 
     def close(self):
         with self.lock:
-            self.closed = True
-            blocks = [(t, p) for t, lst in self.free.items() for p in lst]
-            self.free = {}
-            self.total -= sum(t for t, _ in blocks)
+            self.closed = True  # from here on a finalizer frees what it appends
+            self._fold()
+            free, self.free = self.free, {}
         lib = _abi.load()
-        for _, p in blocks:
-            lib.ffddp_host_free(C.c_void_p(p))
+        for lst in free.values():
+            for p in lst:
+                lib.ffddp_host_free(C.c_void_p(p))
+        self._free_returned()
 
 
 class BatchedBoxFDDP:

@@ -164,10 +164,9 @@ def test_pinned_outputs_bit_identical():
     r.close()
 
 
-def test_host_output_modes_bit_identical(monkeypatch):
+def test_host_output_modes_bit_identical():
     """The host entry point's output paths at a multi-slice and a one-slice
-    batch: fresh pageable outputs (staging buffer), outputs page-locked for the
-    call (FFDDP_HOSTIO_REGISTER=1, read at each call) and recycled page-locked
+    batch: fresh pageable outputs (staging buffer) and recycled page-locked
     outputs give the same bits as the device entry point."""
     import torch
 
@@ -190,17 +189,12 @@ def test_host_output_modes_bit_identical(monkeypatch):
         torch.cuda.synchronize(dev)
         ref = {k: t[k].cpu().numpy() for k in ("xs", "us", "K", "cost", "stats")}
         d.close()
-        for outputs, env in (("fresh", None), ("fresh", "1"), ("recycled", None)):
-            if env is None:
-                monkeypatch.delenv("FFDDP_HOSTIO_REGISTER", raising=False)
-            else:
-                monkeypatch.setenv("FFDDP_HOSTIO_REGISTER", env)
+        for outputs, env in (("fresh", None), ("recycled", None)):
             s = BatchedBoxFDDP(cfg, max_batch=B, outputs=outputs)
             s.solve(batch, maxiter=10)
             for k, v in ref.items():
                 assert np.array_equal(getattr(s, k), v, equal_nan=True), (B, outputs, env, k)
             s.close()
-        monkeypatch.delenv("FFDDP_HOSTIO_REGISTER", raising=False)
 
 
 def test_feasible_warm_start_matches_oracle():

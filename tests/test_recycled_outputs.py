@@ -6,6 +6,8 @@ page-locked cap, and the frees at close."""
 from __future__ import annotations
 
 import ctypes as C
+import gc
+import threading
 
 import numpy as np
 import pytest
@@ -83,3 +85,58 @@ def test_views_keep_the_block(fake):
     c = pool.arrays(SPECS)
     assert c["xs"].ctypes.data == addr
     pool.close()
+
+
+class _GcWhileLocked:
+    """Stand-in for the pool's lock: the cyclic collector is enabled exactly
+    while the lock is held, so a pending cycle is collected at the first
+    allocation inside a locked region, not somewhere before it."""
+
+    def __init__(self):
+        self._lock = threading.Lock()
+
+    def __enter__(self):
+        self._lock.acquire()
+        gc.enable()
+
+    def __exit__(self, *exc):
+        gc.disable()
+        self._lock.release()
+
+
+def test_finalizer_inside_a_locked_region_does_not_deadlock(fake):
+    """A block whose arrays sit in an unreachable reference cycle is given back
+    by a cyclic GC pass, which starts at any container allocation, also one
+    made while the pool's lock is held by the same thread (give-back of
+    another block, close()).  Neither may block, and every block is freed
+    once."""
+    was_enabled, thresholds = gc.isenabled(), gc.get_threshold()
+    gc.disable()
+    try:
+        pool = S._RecycledPinned(cap=10 ** 6)
+        pool.lock = _GcWhileLocked()
+        a = pool.arrays(SPECS)
+        b = pool.arrays(SPECS)
+        assert fake.allocs == 2
+        cycle = [a]
+        cycle.append(cycle)
+        del a, cycle  # block 1: unreachable, pending until a GC pass
+        held = [b]
+        del b
+        gc.set_threshold(1, 1, 1)
+        # daemon threads: a deadlock fails the joins below instead of hanging the suite
+        drop = threading.Thread(target=held.clear, daemon=True)  # the last reference to block 2
+        drop.start()
+        drop.join(5.0)
+        close = threading.Thread(target=pool.close, daemon=True)
+        close.start()
+        close.join(5.0)
+        assert not drop.is_alive() and not close.is_alive()
+        gc.collect()  # block 1's cycle, had no pass collected it yet
+        assert fake.frees == 2 and not fake.live
+    finally:
+        gc.set_threshold(*thresholds)
+        if was_enabled:
+            gc.enable()
+        else:
+            gc.disable()

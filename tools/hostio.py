@@ -30,12 +30,10 @@ T = dict(x0=torch.tensor(b.x0, **f64), node_ref=torch.tensor(b.node_ref, **f64),
          iters=torch.zeros(B, dtype=torch.int32, device="cuda"), ok=torch.zeros(B, dtype=torch.uint8, device="cuda"),
          fn_pred=torch.zeros((B, 2), **f64), stats=torch.zeros((B, _abi.NSTATS), dtype=torch.int32, device="cuda"))
 stream = torch.cuda.current_stream().cuda_stream
-# name:dbg[:ENV=VAL...]  (e.g. pageable_reg:0:FFDDP_HOSTIO_REGISTER=1)
+# name:label[:ENV=VAL...]  (e.g. pageable_4t:0:FFDDP_COPY_THREADS=4)
 configs = [c.split(":") for c in (os.environ.get("HOSTIO_CONFIGS") or "pageable:0,pinned:0").split(",")]
 for name, dbg, *envs in configs:
-    os.environ["FFDDP_HOSTIO_DBG"] = dbg
-    for k in ("FFDDP_HOSTIO_REGISTER", "FFDDP_COPY_THREADS"):
-        os.environ.pop(k, None)
+    os.environ.pop("FFDDP_COPY_THREADS", None)
     for e in envs:
         k, v = e.split("=", 1)
         os.environ[k] = v
