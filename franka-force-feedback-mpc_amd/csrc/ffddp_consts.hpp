@@ -44,14 +44,31 @@ inline void torque_limit_consts(const double* tau_limits, double margin, TorqueL
 
 // One instance's torque-limit row (ffddp.h FFDDP_TAU_LIM_W, joint-major):
 // entry 4j u_ub[j], 4j + 1 ts_ub[j], 4j + 2 ws_lim[j], the rest zero padding.
+// The one place that knows the layout: u_ub, ts_ub and ws_lim (seven each) into a row.
+inline void torque_limit_row_pack(const double* u_ub, const double* ts_ub, const double* ws_lim, double* row) {
+  for (int e = 0; e < FFDDP_TAU_LIM_W; ++e) row[e] = 0.0;
+  for (int j = 0; j < 7; ++j) {
+    row[4 * j + 0] = u_ub[j];
+    row[4 * j + 1] = ts_ub[j];
+    row[4 * j + 2] = ws_lim[j];
+  }
+}
 inline void torque_limit_row(const double* tau_limits, double margin, double* row) {
   TorqueLimitConsts tl;
   torque_limit_consts(tau_limits, margin, tl);
-  for (int e = 0; e < FFDDP_TAU_LIM_W; ++e) row[e] = 0.0;
+  torque_limit_row_pack(tl.u_ub, tl.ts_ub, tl.ws_lim, row);
+}
+
+// One instance's link-model row (ffddp.h FFDDP_LINK_W, joint-major): entry 16j
+// mass[j], 16j + 1..3 com[j], 16j + 4..12 inertia[j] row-major as the struct
+// holds it, the rest zero padding.  Plain copies, so a row of the handle's
+// robot is the handle's constants by construction.
+inline void link_model_row(const ffddp_robot& rb, double* row) {
+  for (int e = 0; e < FFDDP_LINK_W; ++e) row[e] = 0.0;
   for (int j = 0; j < 7; ++j) {
-    row[4 * j + 0] = tl.u_ub[j];
-    row[4 * j + 1] = tl.ts_ub[j];
-    row[4 * j + 2] = tl.ws_lim[j];
+    row[16 * j] = rb.mass[j];
+    for (int e = 0; e < 3; ++e) row[16 * j + 1 + e] = rb.com[j][e];
+    for (int e = 0; e < 9; ++e) row[16 * j + 4 + e] = rb.inertia[j][e];
   }
 }
 

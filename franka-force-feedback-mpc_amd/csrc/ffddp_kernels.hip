@@ -121,6 +121,8 @@ struct Dev {
   const double* ul;    // [B][FFDDP_TAU_LIM_W] torque-limit rows (ffddp_solve_batch_lim_dev), read by the UL
                        //          instantiations of k_node / k_forward_g8 and by the backward pass's fill of its
                        //          BoxQP bounds; null: C's limits
+  const double* md;    // [B][FFDDP_LINK_W] link-model rows (ffddp_solve_batch_mdl_dev), read by the MD
+                       //          instantiations of k_node / k_forward_g8 only; null: C.rb's inertial parameters
 };
 
 // Active-instance compaction.  Iteration it reads list (it & 1): the
@@ -279,7 +281,9 @@ struct NodeShared {
 // constants FFDDP_CW_* of ffddp.h) instead of C; which terms exist stays C's.
 // UL: the torque soft-limit bounds and the w soft limit come from the
 // instance's row d.ul[b] (ffddp.h FFDDP_TAU_LIM_W), read where C's were.
-template <int NC, bool FF, bool FR, bool CW, bool UL>
+// MD: the links' mass, centre of mass and rotational inertia come from the
+// instance's row d.md[b] (ffddp.h FFDDP_LINK_W), read where C.rb's were.
+template <int NC, bool FF, bool FR, bool CW, bool UL, bool MD>
 __device__ __forceinline__ void primal_group(const DevConsts& C, const Dev& d, const double* __restrict__ x0,
                                              const double* __restrict__ node_ref, const double* __restrict__ inst_ref,
                                              const uint8_t* __restrict__ surface, int b, int t, Primal* P,
@@ -319,8 +323,9 @@ __device__ __forceinline__ void primal_group(const DevConsts& C, const Dev& d, c
   double lam[3];
   const double* cw = CW ? d.cw + (long)b * FFDDP_COST_W : nullptr;
   const double* ul = UL ? d.ul + (long)b * FFDDP_TAU_LIM_W : nullptr;
-  const double pc = node_primal_g8<NC, FR, CW, UL>(C, mode, surf, q, v, u, xreg[ji], xreg[7 + ji], xreg[14 + ji], ref,
-                                                   P, lk, lam, FR ? d.fref + ((long)b * (N + 1) + t) : nullptr, cw, ul);
+  const double* md = MD ? d.md + (long)b * FFDDP_LINK_W : nullptr;
+  const double pc = node_primal_g8<NC, FR, CW, UL, MD>(C, mode, surf, q, v, u, xreg[ji], xreg[7 + ji], xreg[14 + ji], ref, P,
+                                                       lk, lam, FR ? d.fref + ((long)b * (N + 1) + t) : nullptr, cw, ul, md);
   double* rec = d.rec_buf + ((long)b * (N + 1) + t) * d.rec;
   // node cost (IAM scaling, FF augmentation terms): per-lane shares summed over the group
   double c = FF ? C.dt * pc : (terminal ? pc : C.dt * pc);
@@ -407,7 +412,10 @@ __device__ __forceinline__ double fquad(const double* a, const double* Dd, const
 // UL: the torque soft-limit bounds and the w soft limit are those of the
 // instance's row d.ul[b] (a solve with tau_lim), each read where C's was;
 // UL = false is the kernel as it was.
-template <int NC, bool FF, bool FR = false, bool CW = false, bool UL = false>
+// MD: the calc's link inertial parameters are those of the instance's row
+// d.md[b] (a solve with link_rows), read where C.rb's were; the tangents read
+// only what the calc wrote.  MD = false is the kernel as it was.
+template <int NC, bool FF, bool FR = false, bool CW = false, bool UL = false, bool MD = false>
 __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE_WAVES))) void k_node(const DevConsts* __restrict__ Cg, Dev d,
                                                       const double* __restrict__ x0,
                                                       const double* __restrict__ node_ref,
@@ -446,7 +454,7 @@ __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE
   const double* ref = node_ref + ((long)b * (N + 1) + t) * 6;
   NodeGroupShared& G = S.g[grp];
   Primal& P = G.P;
-  if (active && lane < G8) primal_group<NC, FF, FR, CW, UL>(C, d, x0, node_ref, inst_ref, surface, b, t, &P, G.lk, xsrc, usrc);
+  if (active && lane < G8) primal_group<NC, FF, FR, CW, UL, MD>(C, d, x0, node_ref, inst_ref, surface, b, t, &P, G.lk, xsrc, usrc);
   __syncthreads();
   const bool need_u = mode != MODE_TERMINAL_X;
   // control directions first, their results stored at once (neither touches
@@ -2047,7 +2055,12 @@ __device__ __forceinline__ int ls_row_bcast0(int v) {  // lane 0 of the row into
 // the lane's three entries of the instance's row d.ul[b], held in registers
 // next to W in place of LaneK's (per block, while a block's groups belong to
 // different instances).  The EE lane takes joint 6's, as LaneK gives it.
-template <int NC, bool FF, bool ROW, bool FR = false, bool CW = false, bool UL = false>
+// MD: the link's mass, centre of mass and rotational inertia are the joint
+// lane's 13 entries of the instance's row d.md[b], held in registers next to W
+// and L in place of LaneK's for the same reason (the kernel runs one wave per
+// SIMD, so the registers are there: DESIGN.md §21).  The EE lane and the ROW
+// layout's phantom lanes hold zeros, as LaneK gives them.
+template <int NC, bool FF, bool ROW, bool FR = false, bool CW = false, bool UL = false, bool MD = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW_WPE))) void k_forward_g8(const DevConsts* __restrict__ Cg, Dev d,
                                                    const double* __restrict__ x0,
                                                    const double* __restrict__ node_ref,
@@ -2143,6 +2156,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
     L.tsub = (fl & RF_TSOFT) ? ulr[1] : 0.0;
     L.wslim = (FF && C.w_ws > 0.0) ? ulr[2] : K.wslim;
   }
+  LsM M;
+  if constexpr (MD) {
+    // the EE lane and the phantom group: exact zeros (the unmasked suffix sums rely on it)
+    const bool lnk = J && real;
+    const double* mdr = d.md + (long)b * FFDDP_LINK_W + 16 * ji;
+    M.m = lnk ? mdr[0] : 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) M.com[k] = lnk ? mdr[1 + k] : 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) M.I[k] = lnk ? mdr[4 + k] : 0.0;
+  }
   // FF augmentation weights (joint lanes) at their use: a term the handle does not build keeps C's zero
   auto w_y = [&]() { return (CW && C.w_y > 0.0) ? W.w[FFDDP_CW_Y - FFDDP_CW_JOINT0] : C.w_y; };
   auto w_w = [&]() { return (CW && C.w_w > 0.0) ? W.w[FFDDP_CW_W - FFDDP_CW_JOINT0] : C.w_w; };
@@ -2211,7 +2235,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
       double qn, vn, cp, lam[3];
       const double uin = FF ? xt_t : u;
       PP(8);
-      ls_node_calc<NC, ROW, FR, CW, UL>(C, fl, K, W, L, MODE_RUNNING, surf, xq_t, xv_t, uin, xq, xv, tref, ref, fnr, qn, vn, cp, lam
+      ls_node_calc<NC, ROW, FR, CW, UL, MD>(C, fl, K, W, L, M, MODE_RUNNING, surf, xq_t, xv_t, uin, xq, xv, tref, ref, fnr, qn, vn, cp, lam
 #ifdef FFDDP_PHASE_PROF
                             , pp_acc, pp_last
 #endif
@@ -2244,7 +2268,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
       double qn, vn, cp, lam[3];
       const int mode = FF ? MODE_TERMINAL_U : MODE_TERMINAL_X;
       PP(8);
-      ls_node_calc<NC, ROW, FR, CW, UL>(C, fl, K, W, L, mode, surf, xq_t, xv_t, FF ? xt_t : 0.0, xq, xv, tref, ref, fnr, qn, vn, cp, lam
+      ls_node_calc<NC, ROW, FR, CW, UL, MD>(C, fl, K, W, L, M, mode, surf, xq_t, xv_t, FF ? xt_t : 0.0, xq, xv, tref, ref, fnr, qn, vn, cp, lam
 #ifdef FFDDP_PHASE_PROF
                             , pp_acc, pp_last
 #endif
@@ -2424,7 +2448,9 @@ __global__ __launch_bounds__(64) void k_commit(const DevConsts* __restrict__ Cg,
 }
 
 // solution read-back helpers: iter/ok, contact force at knots 0 and 1
-template <int NC, bool FF>
+// MD: the predicted contact force is computed under the instance's own link model, its row d.md[b] (a solve with
+// link_rows), which rb_pass reads in place of C.rb's inertial parameters; MD = false is the kernel as it was.
+template <int NC, bool FF, bool MD = false>
 __global__ __launch_bounds__(64) void k_finalize(const DevConsts* __restrict__ Cg, Dev d, int maxiter, const double* __restrict__ x0,
                            const double* __restrict__ node_ref, const double* __restrict__ inst_ref,
                            const uint8_t* __restrict__ surface, double* cost, int32_t* iters, uint8_t* ok,
@@ -2466,7 +2492,12 @@ __global__ __launch_bounds__(64) void k_finalize(const DevConsts* __restrict__ C
   const double* xreg = inst_ref + (long)b * 21;
   Primal P;
   double yn[21], c;
-  node_calc<NC, FF>(C, false, true, y, u, ref, xreg, xreg + 14, x0 + (long)b * nx, P, yn, c);
+  if constexpr (MD) {
+    node_calc<NC, FF>(C, false, true, y, u, ref, xreg, xreg + 14, x0 + (long)b * nx, P, yn, c, nullptr,
+                      d.md + (long)b * FFDDP_LINK_W);
+  } else {
+    node_calc<NC, FF>(C, false, true, y, u, ref, xreg, xreg + 14, x0 + (long)b * nx, P, yn, c);
+  }
   fn_pred[(long)b * 2 + knot] = (NC == 1) ? P.lam[0] : P.lam[2];
 }
 
@@ -2523,6 +2554,14 @@ __global__ __launch_bounds__(64) void k_gravity(const ffddp_robot* __restrict__ 
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   gravity_torque(*rb, q + (long)b * NQ, tau + (long)b * NQ);
+}
+
+// ffddp_gravity_torque_mdl_dev: k_gravity with each instance's own link-model row
+__global__ __launch_bounds__(64) void k_gravity_mdl(const ffddp_robot* __restrict__ rb, int B, const double* __restrict__ q,
+                                                    const double* __restrict__ link, double* __restrict__ tau) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  gravity_torque(*rb, q + (long)b * NQ, tau + (long)b * NQ, link + (long)b * FFDDP_LINK_W);
 }
 
 // ---------------------------------------------------------------------------
@@ -2717,6 +2756,9 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_keep(
 // node1 / hint1.  The flag is two comparisons, so every wave derives it with
 // the rest of the old state; the knots are spread over the threads.  TASK =
 // false compiles the code as it was (T, dt_ocp unused).
+//
+// link (ffddp_fleet_pre_mdl_dev): the gravity torque reference is computed with
+// the instance's own mass / com / inertia, its link-model row; null: *rb's.
 template <bool SCHED, bool TASK>
 __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_pre(
     const ffddp_robot* __restrict__ rb, int N, int nx, ffddp_fleet_params P, ffddp_fleet_state S, ffddp_fleet_sched Q,
@@ -2725,7 +2767,7 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_pre(
     const double* __restrict__ tau_hat, long ld_th, const double* __restrict__ q_nom, const double* __restrict__ node1, int hint1,
     double* __restrict__ x0, uint8_t* __restrict__ surface, double* __restrict__ inst_ref,
     double* __restrict__ node_ref, double* __restrict__ xs_init, double* __restrict__ us_init, ffddp_fleet_tasks T,
-    double dt_ocp) {
+    double dt_ocp, const double* __restrict__ link) {
   const long b = blockIdx.x;
   const int tid = threadIdx.x;
   const bool ff = nx == 21;
@@ -2776,7 +2818,11 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_pre(
   } else if (tid == 64) {  // wave 1, so wave 0's lanes go on with the copies
     double qq[NQ], g[NQ];
     for (int i = 0; i < NQ; ++i) qq[i] = P.torque_mode == 1 ? qn[i] : qb[i];
-    gravity_torque(*rb, qq, g);
+    if (link) {
+      gravity_torque(*rb, qq, g, link + b * FFDDP_LINK_W);
+    } else {
+      gravity_torque(*rb, qq, g);
+    }
     for (int i = 0; i < NQ; ++i) ir[14 + i] = g[i];
   }
   const int nref = (N + 1) * 6, nxs = (N + 1) * nx, nus = N * NU;
@@ -3055,6 +3101,9 @@ struct ffddp_handle {
   // [max_batch][FFDDP_COST_W] rows of the configuration's weights: the cost weights of a solve with torque
   // limits and no cost_w of its own (first such solve)
   double* cw_const = nullptr;
+  // [max_batch][FFDDP_TAU_LIM_W] rows of the configuration's limits: the torque limits of a solve with link
+  // rows and no tau_lim of its own (first such solve)
+  double* ul_const = nullptr;
   // sub-batch streams: the batch is split into nstreams slices solved on their
   // own HIP streams, so latency-bound phases of one slice overlap with the
   // throughput-bound phases of another (FFDDP_STREAMS, default 4: three
@@ -3138,6 +3187,7 @@ void free_all(ffddp_handle* h) {
   if (h->trace) (void)hipFree(h->trace);
   if (h->fref_const) (void)hipFree(h->fref_const);
   if (h->cw_const) (void)hipFree(h->cw_const);
+  if (h->ul_const) (void)hipFree(h->ul_const);
   if (h->stage) (void)hipHostFree(h->stage);
 }
 
@@ -3191,6 +3241,7 @@ Dev dev_slice(const Dev& d0, int b0, int Bk, int k) {
   if (d.fref) d.fref += (long)b0 * (N + 1);
   if (d.cw) d.cw += (long)b0 * FFDDP_COST_W;
   if (d.ul) d.ul += (long)b0 * FFDDP_TAU_LIM_W;
+  if (d.md) d.md += (long)b0 * FFDDP_LINK_W;
   return d;
 }
 
@@ -3208,10 +3259,10 @@ struct SolveArgs {
   double* fn_pred;
   int32_t* stats;
   const uint8_t* active;
-  const double *fref, *cw, *ul;
+  const double *fref, *cw, *ul, *md;
 };
 
-template <int NC, bool FF, bool FR, bool CW, bool UL>
+template <int NC, bool FF, bool FR, bool CW, bool UL, bool MD>
 int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* io) {
   const int B = a.B, maxiter = a.maxiter;
   const int N = h->hc.N, nx = h->hc.nx;
@@ -3249,6 +3300,7 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
   dbase.fref = FR ? a.fref : nullptr;
   dbase.cw = CW ? a.cw : nullptr;
   dbase.ul = UL ? a.ul : nullptr;
+  dbase.md = MD ? a.md : nullptr;
   if (!io) {
     dbase.xs = a.xs;
     dbase.us = a.us;
@@ -3312,7 +3364,7 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
     if (it == 0 && stagger == 2 && k + 1 < S) HIPCHK(h, hipEventRecord(h->stg[k], ss));
     {
       ProfScope p(h, ss, KC_NODE);
-      hipLaunchKernelGGL((k_node<NC, FF, FR, CW, UL>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, ss,
+      hipLaunchKernelGGL((k_node<NC, FF, FR, CW, UL, MD>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, ss,
                          h->dc, d, x0k, nrefk, irefk, surfk, 0, it & 1);
     }
     if (it == 0 && stagger == 1 && k + 1 < S) HIPCHK(h, hipEventRecord(h->stg[k], ss));
@@ -3383,13 +3435,13 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
         const long groups = more ? (long)Bk * ntr : g1;
         if (!row_only) {
           const dim3 grid((unsigned)((groups * G8 + 63) / 64));
-          hipLaunchKernelGGL((k_forward_g8<NC, FF, false, FR, CW, UL>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
+          hipLaunchKernelGGL((k_forward_g8<NC, FF, false, FR, CW, UL, MD>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
                              surfk, tr0, ntr, more, it & 1, wide, row_max);
         }
         if (row_max > 0) {
           const long rg = std::min(groups, (long)row_max);  // the row layout runs only when they fit
           const dim3 grid((unsigned)((rg * 16 + 63) / 64));
-          hipLaunchKernelGGL((k_forward_g8<NC, FF, true, FR, CW, UL>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
+          hipLaunchKernelGGL((k_forward_g8<NC, FF, true, FR, CW, UL, MD>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
                              surfk, tr0, ntr, more, it & 1, wide, row_max);
         }
       };
@@ -3425,7 +3477,7 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
     }
     {
       ProfScope p(h, ss, KC_FINALIZE);
-      hipLaunchKernelGGL((k_finalize<NC, FF>), dim3((2 * Bk + 63) / 64), dim3(64), 0, ss, h->dc, d, maxiter,
+      hipLaunchKernelGGL((k_finalize<NC, FF, MD>), dim3((2 * Bk + 63) / 64), dim3(64), 0, ss, h->dc, d, maxiter,
                          a.x0 + b0 * nxl, a.nref + b0 * N1 * 6, a.iref + b0 * 21, a.surf + b0, a.cost + b0, a.iters + b0,
                          a.ok + b0, a.fn_pred ? a.fn_pred + 2 * b0 : nullptr,
                          a.stats ? a.stats + b0 * FFDDP_NSTATS : nullptr, a.active ? a.active + b0 : nullptr);
@@ -3482,34 +3534,41 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
   return 0;
 }
 
-// The one (nc, variant, force reference, cost weights, torque limits) -> template constants decision, for the solve
-// and for ffddp_calc_diff_lim: f(NC, FF, FR, CW, UL) is called with std::integral_constant arguments.  fr: there is
+// The one (nc, variant, force reference, cost weights, torque limits, link model) -> template constants decision, for
+// the solve and for ffddp_calc_diff_mdl: f(NC, FF, FR, CW, UL, MD) is called with std::integral_constant arguments.  fr: there is
 // a force reference; without one the kernels are the FR = false instantiations.  cw: there are cost-weight rows.
 // The CW kernels exist with FR only (the caller supplies a force reference of fn_des where the user gave none: the
 // same bits), so the build does not double.  ul: there are torque-limit rows; the UL kernels exist with FR and CW
-// only (the caller supplies rows of the configuration's weights likewise).
-template <class F> int dispatch_variant(ffddp_handle* h, bool fr, bool cw, bool ul, F&& f) {
+// only (the caller supplies rows of the configuration's weights likewise).  md: there are link-model rows; the MD
+// kernels exist with FR, CW and UL only (the caller supplies rows of the configuration's limits likewise).
+template <class F> int dispatch_variant(ffddp_handle* h, bool fr, bool cw, bool ul, bool md, F&& f) {
   if (cw && !fr) return fail(h, FFDDP_E_INVALID, "cost weights without a force reference");
   if (ul && !cw) return fail(h, FFDDP_E_INVALID, "torque limits without cost weights");
+  if (md && !ul) return fail(h, FFDDP_E_INVALID, "link model without torque limits");
   using NC1 = std::integral_constant<int, 1>;
   using NC3 = std::integral_constant<int, 3>;
   const bool ff = h->hc.variant == FFDDP_FORCE_FEEDBACK;
-  auto nc_ff = [&](auto FR, auto CW, auto UL) -> int {
-    if (h->hc.nc == 1) return ff ? f(NC1{}, std::true_type{}, FR, CW, UL) : f(NC1{}, std::false_type{}, FR, CW, UL);
-    return ff ? f(NC3{}, std::true_type{}, FR, CW, UL) : f(NC3{}, std::false_type{}, FR, CW, UL);
+  auto nc_ff = [&](auto FR, auto CW, auto UL, auto MD) -> int {
+    if (h->hc.nc == 1)
+      return ff ? f(NC1{}, std::true_type{}, FR, CW, UL, MD) : f(NC1{}, std::false_type{}, FR, CW, UL, MD);
+    return ff ? f(NC3{}, std::true_type{}, FR, CW, UL, MD) : f(NC3{}, std::false_type{}, FR, CW, UL, MD);
   };
-  if (ul) return nc_ff(std::true_type{}, std::true_type{}, std::true_type{});
-  if (cw) return nc_ff(std::true_type{}, std::true_type{}, std::false_type{});
-  if (fr) return nc_ff(std::true_type{}, std::false_type{}, std::false_type{});
-  return nc_ff(std::false_type{}, std::false_type{}, std::false_type{});
+  const std::true_type T{};
+  const std::false_type F_{};
+  if (md) return nc_ff(T, T, T, T);
+  if (ul) return nc_ff(T, T, T, F_);
+  if (cw) return nc_ff(T, T, F_, F_);
+  if (fr) return nc_ff(T, F_, F_, F_);
+  return nc_ff(F_, F_, F_, F_);
 }
 
 // io: the host entry point's copies (nullptr: the device entry points and the plan capture)
 int launch_solve(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* io) {
-  return dispatch_variant(h, a.fref != nullptr, a.cw != nullptr, a.ul != nullptr,
-                          [&](auto NC, auto FF, auto FR, auto CW, auto UL) {
+  return dispatch_variant(h, a.fref != nullptr, a.cw != nullptr, a.ul != nullptr, a.md != nullptr,
+                          [&](auto NC, auto FF, auto FR, auto CW, auto UL, auto MD) {
                             return launch_solve_t<decltype(NC)::value, decltype(FF)::value, decltype(FR)::value,
-                                                  decltype(CW)::value, decltype(UL)::value>(h, a, s, io);
+                                                  decltype(CW)::value, decltype(UL)::value, decltype(MD)::value>(h, a, s,
+                                                                                                                  io);
                           });
 }
 
@@ -3821,6 +3880,38 @@ int ffddp_torque_limit_rows(const ffddp_ocp_config* cfg, int B, const double* ta
   return 0;
 }
 
+// the handle's constant torque-limit rows (the configuration's limits in every row, packed by torque_limit_row's
+// own code from the constants fill_consts derived), made on first use: the MD kernels are instantiated with UL only, and rows of the handle's limits reproduce the
+// constants' bits (the lower bounds are the exact negations)
+static int const_limit_rows(ffddp_handle* h) {
+  if (h->ul_const) return 0;
+  const DevConsts& c = h->hc;
+  double row[FFDDP_TAU_LIM_W];
+  torque_limit_row_pack(c.u_ub, c.ts_ub, c.ws_lim, row);
+  const size_t n = (size_t)h->max_batch * FFDDP_TAU_LIM_W;
+  std::vector<double> v(n);
+  for (size_t i = 0; i < n; ++i) v[i] = row[i % FFDDP_TAU_LIM_W];
+  if (int rc = dalloc(h, &h->ul_const, n)) return rc;
+  HIPCHK(h, hipMemcpy(h->ul_const, v.data(), n * 8, hipMemcpyHostToDevice));
+  return 0;
+}
+
+int ffddp_link_model_rows(const ffddp_robot* robots, int B, double* rows) {
+  if (B < 0 || (B > 0 && (!robots || !rows))) return FFDDP_E_INVALID;
+  for (long b = 0; b < B; ++b) {
+    const ffddp_robot& r = robots[b];
+    for (int j = 0; j < 7; ++j) {
+      if (!(std::isfinite(r.mass[j]) && r.mass[j] > 0.0)) return FFDDP_E_INVALID;
+      for (int e = 0; e < 3; ++e)
+        if (!std::isfinite(r.com[j][e])) return FFDDP_E_INVALID;
+      for (int e = 0; e < 9; ++e)
+        if (!std::isfinite(r.inertia[j][e])) return FFDDP_E_INVALID;
+    }
+  }
+  for (long b = 0; b < B; ++b) link_model_row(robots[b], rows + b * FFDDP_LINK_W);
+  return 0;
+}
+
 int ffddp_solve_batch_wts_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
                               const double* inst_ref, const uint8_t* surface, const double* xs_init,
                               const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
@@ -3836,15 +3927,30 @@ int ffddp_solve_batch_lim_dev(ffddp_handle* h, int B, const double* x0, const do
                               double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
                               const uint8_t* active, const double* force_ref, const double* cost_w,
                               const double* tau_lim, void* stream) {
+  return ffddp_solve_batch_mdl_dev(h, B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs,
+                                   us, K, cost, iters, ok, fn_pred, stats, active, force_ref, cost_w, tau_lim, nullptr,
+                                   stream);
+}
+
+int ffddp_solve_batch_mdl_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                              const double* inst_ref, const uint8_t* surface, const double* xs_init,
+                              const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
+                              double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
+                              const uint8_t* active, const double* force_ref, const double* cost_w,
+                              const double* tau_lim, const double* link_rows, void* stream) {
   SolveArgs a{B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs, us, K, cost, iters, ok,
-              fn_pred, stats, active, force_ref, cost_w, tau_lim};
+              fn_pred, stats, active, force_ref, cost_w, tau_lim, link_rows};
   if (int rc = solve_args_check(h, a)) return rc;
   if (B == 0) return 0;
   HIPCHK(h, hipSetDevice(h->device));
   // the handle's workspace is shared by every solve: a solve enqueued on
   // another (possibly non-blocking) stream must finish before this one starts
   if (h->last_done_set) HIPCHK(h, hipStreamWaitEvent((hipStream_t)stream, h->last_done, 0));
-  if (tau_lim && !cost_w) {
+  if (link_rows && !tau_lim) {
+    if (int rc = const_limit_rows(h)) return rc;
+    a.ul = h->ul_const;
+  }
+  if (a.ul && !cost_w) {
     if (int rc = const_cost_rows(h)) return rc;
     a.cw = h->cw_const;
   }
@@ -3896,9 +4002,9 @@ int ffddp_solve_batch(ffddp_handle* h, int B, const double* x0, const double* no
                       const uint8_t* surface, const double* xs_init, const double* us_init, int maxiter,
                       int is_feasible, double* xs, double* us, double* K, double* cost, int32_t* iters, uint8_t* ok,
                       double* fn_pred, int32_t* stats) {
-  // the caller's host arrays; no active mask, force reference, cost weights or torque limits on this path
+  // the caller's host arrays; no active mask, force reference, cost weights, torque limits or link model on this path
   const SolveArgs user{B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs, us, K, cost,
-                       iters, ok, fn_pred, stats, nullptr, nullptr, nullptr, nullptr};
+                       iters, ok, fn_pred, stats, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (int rc = solve_args_check(h, user)) return rc;
   if (B == 0) return 0;
   HIPCHK(h, hipSetDevice(h->device));
@@ -3989,7 +4095,7 @@ int ffddp_solve_batch(ffddp_handle* h, int B, const double* x0, const double* no
   // the solve itself works on the handle's device buffers; xs / us / K: where launch_solve_t copies them down to
   const SolveArgs a{B, h->in_x0, h->in_nref, h->in_iref, h->in_surf, h->in_xs, h->in_us, maxiter, is_feasible,
                     (double*)hout[0], (double*)hout[1], (double*)hout[2], h->out_cost, h->out_iters, h->out_ok,
-                    h->out_fn, h->out_stats, nullptr, nullptr, nullptr, nullptr};
+                    h->out_fn, h->out_stats, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (int rc = launch_solve(h, a, cs, &io)) return drain_host_solve(h, rc);
   const double t2 = tm ? now() : 0.0;
   // while the device solves: the first touch of the caller's pageable output
@@ -4149,7 +4255,7 @@ int ffddp_plan_create(ffddp_handle* h, int B, int maxiter, int is_feasible, ffdd
                     (const uint8_t*)(di + L.surf), (const double*)(di + L.xs_init), (const double*)(di + L.us_init),
                     maxiter, is_feasible, (double*)(dq + L.xs), (double*)(dq + L.us), (double*)(dq + L.K),
                     (double*)(dq + L.cost), (int32_t*)(dq + L.iters), (uint8_t*)(dq + L.ok), (double*)(dq + L.fn),
-                    (int32_t*)(dq + L.stats), nullptr, nullptr, nullptr, nullptr};
+                    (int32_t*)(dq + L.stats), nullptr, nullptr, nullptr, nullptr, nullptr};
   int rc = 0;
   hipError_t e = hipStreamBeginCapture(p->s, hipStreamCaptureModeThreadLocal);
   if (e == hipSuccess) {
@@ -4349,6 +4455,15 @@ int ffddp_calc_diff_lim(ffddp_handle* h, int B, const double* x0, const double* 
                         const uint8_t* surface, const double* xs, const double* us, const double* force_ref,
                         const double* cost_w, const double* tau_lim, double* Fx, double* Fu, double* Lx, double* Lu,
                         double* Lxx, double* Lxu, double* Luu, double* cost, double* xnext, double* lam) {
+  return ffddp_calc_diff_mdl(h, B, x0, node_ref, inst_ref, surface, xs, us, force_ref, cost_w, tau_lim, nullptr, Fx, Fu,
+                             Lx, Lu, Lxx, Lxu, Luu, cost, xnext, lam);
+}
+
+int ffddp_calc_diff_mdl(ffddp_handle* h, int B, const double* x0, const double* node_ref, const double* inst_ref,
+                        const uint8_t* surface, const double* xs, const double* us, const double* force_ref,
+                        const double* cost_w, const double* tau_lim, const double* link_rows, double* Fx, double* Fu,
+                        double* Lx, double* Lu, double* Lxx, double* Lxu, double* Luu, double* cost, double* xnext,
+                        double* lam) {
   if (!h) return FFDDP_E_INVALID;
   if (B < 1 || B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "bad B");
   if (force_ref && !(h->hc.w_fn > 0.0))
@@ -4360,19 +4475,26 @@ int ffddp_calc_diff_lim(ffddp_handle* h, int B, const double* x0, const double* 
     ~Tmp() {
       if (p) (void)hipFree(p);
     }
-  } fref, cw, ul;
-  const bool with_cw = cost_w || tau_lim;
+  } fref, cw, ul, md;
+  const bool with_ul = tau_lim || link_rows;
+  const bool with_cw = cost_w || with_ul;
   if (force_ref) {
     HIPCHK(h, hipMalloc((void**)&fref.p, (size_t)B * (h->hc.N + 1) * 8));
     HIPCHK(h, hipMemcpy(fref.p, force_ref, (size_t)B * (h->hc.N + 1) * 8, hipMemcpyHostToDevice));
   } else if (with_cw) {
     if (int rc = const_force_ref(h)) return rc;
   }
+  if (with_ul && !cost_w)
+    if (int rc = const_cost_rows(h)) return rc;
   if (tau_lim) {
-    if (!cost_w)
-      if (int rc = const_cost_rows(h)) return rc;
     HIPCHK(h, hipMalloc((void**)&ul.p, (size_t)B * FFDDP_TAU_LIM_W * 8));
     HIPCHK(h, hipMemcpy(ul.p, tau_lim, (size_t)B * FFDDP_TAU_LIM_W * 8, hipMemcpyHostToDevice));
+  } else if (link_rows) {
+    if (int rc = const_limit_rows(h)) return rc;
+  }
+  if (link_rows) {
+    HIPCHK(h, hipMalloc((void**)&md.p, (size_t)B * FFDDP_LINK_W * 8));
+    HIPCHK(h, hipMemcpy(md.p, link_rows, (size_t)B * FFDDP_LINK_W * 8, hipMemcpyHostToDevice));
   }
   if (cost_w) {
     HIPCHK(h, hipMalloc((void**)&cw.p, (size_t)B * FFDDP_COST_W * 8));
@@ -4383,8 +4505,9 @@ int ffddp_calc_diff_lim(ffddp_handle* h, int B, const double* x0, const double* 
   Dev d = h->d;
   d.B = B;
   d.fref = fref.p ? fref.p : (with_cw ? h->fref_const : nullptr);
-  d.cw = cw.p ? cw.p : (tau_lim ? h->cw_const : nullptr);
-  d.ul = ul.p;
+  d.cw = cw.p ? cw.p : (with_ul ? h->cw_const : nullptr);
+  d.ul = ul.p ? ul.p : (link_rows ? h->ul_const : nullptr);
+  d.md = md.p;
   HIPCHK(h, hipMemcpy(h->in_x0, x0, (size_t)B * nx * 8, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->in_nref, node_ref, (size_t)B * (N + 1) * 6 * 8, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->in_iref, inst_ref, (size_t)B * 21 * 8, hipMemcpyHostToDevice));
@@ -4393,11 +4516,11 @@ int ffddp_calc_diff_lim(ffddp_handle* h, int B, const double* x0, const double* 
   HIPCHK(h, hipMemcpy(h->in_us, us, (size_t)B * N * NU * 8, hipMemcpyHostToDevice));
   // node kernel reads (xs, us) from the solver state: initialise it from the inputs
   hipLaunchKernelGGL(k_init<false>, dim3(1024), dim3(INIT_BLOCK), 0, nullptr, h->dc, d, h->in_xs, h->in_us, 0, nullptr);
-  const int rc = dispatch_variant(h, d.fref != nullptr, d.cw != nullptr, d.ul != nullptr,
-                                  [&](auto NC, auto FF, auto FR, auto CW, auto UL) {
+  const int rc = dispatch_variant(h, d.fref != nullptr, d.cw != nullptr, d.ul != nullptr, d.md != nullptr,
+                                  [&](auto NC, auto FF, auto FR, auto CW, auto UL, auto MD) {
     const long nodes = (long)B * (N + 1);
     hipLaunchKernelGGL((k_node<decltype(NC)::value, decltype(FF)::value, decltype(FR)::value, decltype(CW)::value,
-                               decltype(UL)::value>),
+                               decltype(UL)::value, decltype(MD)::value>),
                        dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, nullptr, h->dc, d, h->in_x0,
                        h->in_nref, h->in_iref, h->in_surf, 1, 0);
     return 0;
@@ -4473,6 +4596,17 @@ int ffddp_gravity_torque_dev(ffddp_handle* h, int B, const double* q, double* ta
   if (B == 0) return 0;
   HIPCHK(h, hipSetDevice(h->device));
   hipLaunchKernelGGL(k_gravity, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->drb, B, q, tau);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int ffddp_gravity_torque_mdl_dev(ffddp_handle* h, int B, const double* q, const double* link_rows, double* tau,
+                                 void* stream) {
+  if (!link_rows) return ffddp_gravity_torque_dev(h, B, q, tau, stream);
+  if (!h || B < 0) return FFDDP_E_INVALID;
+  if (B == 0) return 0;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_gravity_mdl, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->drb, B, q, link_rows, tau);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -4555,15 +4689,16 @@ static int fleet_sched_check(ffddp_handle* h, const ffddp_fleet_sched& c, const 
   return 0;
 }
 
-// The body of ffddp_fleet_pre_dev, _pre_sched_dev and _pre_task_dev; `name`: the entry point called, for the
-// messages.  sched: the scheduled tick (the SCHED instantiations).  tasks: per-instance tasks (the TASK
-// instantiations) in place of node_ref1 / contact_hint.
+// The body of ffddp_fleet_pre_dev, _pre_sched_dev, _pre_task_dev and _pre_mdl_dev; `name`: the entry point called,
+// for the messages.  sched: the scheduled tick (the SCHED instantiations).  tasks: per-instance tasks (the TASK
+// instantiations) in place of node_ref1 / contact_hint.  link: per-instance link-model rows or null.
 static int fleet_pre(ffddp_handle* h, const char* name, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
                      const double* q, const double* v, const double* fn_meas, const double* contact,
                      const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
                      const double* q_nom, const double* node_ref1, int contact_hint, double* x0, uint8_t* surface,
                      double* inst_ref, double* node_ref, double* xs_init, double* us_init,
-                     const ffddp_fleet_sched* sched, const ffddp_fleet_tasks* tasks, void* stream) {
+                     const ffddp_fleet_sched* sched, const ffddp_fleet_tasks* tasks, const double* link,
+                     void* stream) {
   if (!h) return FFDDP_E_INVALID;
   const std::string who(name);
   if (B <= 0) return fail(h, FFDDP_E_INVALID, who + ": B must be positive");
@@ -4583,7 +4718,7 @@ static int fleet_pre(ffddp_handle* h, const char* name, int B, const ffddp_fleet
   hipLaunchKernelGGL(kern, dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx, *p, *s,
                      sched ? *sched : ffddp_fleet_sched{}, q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar,
                      tau_hat, (long)ld_tau_hat, q_nom, node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init,
-                     us_init, tasks ? *tasks : ffddp_fleet_tasks{}, tasks ? h->hc.dt : 0.0);
+                     us_init, tasks ? *tasks : ffddp_fleet_tasks{}, tasks ? h->hc.dt : 0.0, link);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -4596,7 +4731,7 @@ int ffddp_fleet_pre_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, con
                         double* node_ref, double* xs_init, double* us_init, void* stream) {
   return fleet_pre(h, "ffddp_fleet_pre_dev", B, p, s, q, v, fn_meas, contact, ee_z, ld_qv, ld_scalar, tau_hat, ld_tau_hat,
                    q_nom, node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init, nullptr, nullptr,
-                   stream);
+                   nullptr, stream);
 }
 
 int ffddp_fleet_pre_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
@@ -4607,7 +4742,7 @@ int ffddp_fleet_pre_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params* 
                               ffddp_fleet_sched sched, void* stream) {
   return fleet_pre(h, "ffddp_fleet_pre_sched_dev", B, p, s, q, v, fn_meas, contact, ee_z, ld_qv, ld_scalar, tau_hat,
                    ld_tau_hat, q_nom, node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init, &sched,
-                   nullptr, stream);
+                   nullptr, nullptr, stream);
 }
 
 // The body of ffddp_fleet_post_dev, _post_sched_dev and _post_lim_dev (sched: the scheduled tick, the SCHED
@@ -4712,7 +4847,19 @@ int ffddp_fleet_pre_task_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p
                              double* inst_ref, double* node_ref, double* xs_init, double* us_init,
                              const ffddp_fleet_sched* sched, void* stream) {
   return fleet_pre(h, "ffddp_fleet_pre_task_dev", B, p, s, q, v, fn_meas, contact, ee_z, ld_qv, ld_scalar, tau_hat,
-                   ld_tau_hat, q_nom, nullptr, 0, x0, surface, inst_ref, node_ref, xs_init, us_init, sched, &tasks, stream);
+                   ld_tau_hat, q_nom, nullptr, 0, x0, surface, inst_ref, node_ref, xs_init, us_init, sched, &tasks, nullptr,
+                   stream);
+}
+
+int ffddp_fleet_pre_mdl_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                            const double* q, const double* v, const double* fn_meas, const double* contact,
+                            const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
+                            const double* q_nom, ffddp_fleet_tasks tasks, const double* node_ref1, int contact_hint,
+                            double* x0, uint8_t* surface, double* inst_ref, double* node_ref, double* xs_init,
+                            double* us_init, const ffddp_fleet_sched* sched, const double* link_rows, void* stream) {
+  return fleet_pre(h, "ffddp_fleet_pre_mdl_dev", B, p, s, q, v, fn_meas, contact, ee_z, ld_qv, ld_scalar, tau_hat,
+                   ld_tau_hat, q_nom, node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init, sched,
+                   tasks.rec ? &tasks : nullptr, link_rows, stream);
 }
 
 // the sweep's task metrics (ffddp_metrics.hpp): one record per instance folded into acc [W][ld]

@@ -259,9 +259,11 @@ template <int NC> FFD_HD void force_world(const double* lam, double* fw) {
 template <int NC>
 FFD_HD void node_primal(const DevConsts& C, int mode, bool surface, const double* x, const double* u,
                         const double* ref, const double* xreg, const double* tauref, Primal& P,
-                        Primal* gout = nullptr, const double* fnr = nullptr) {
+                        Primal* gout = nullptr, const double* fnr = nullptr, const double* lrow = nullptr) {
   // fnr: this node's normal-force reference (the solve's force_ref entry) in
   // place of C.fn_ref[NC - 1]; null: C's
+  // lrow: the instance's link-model row in place of C.rb's inertial parameters
+  // (k_finalize's MD instantiations); null: C.rb's
   // gout: each block of fields is stored as soon as it is final, so the
   // registers holding it can be reused (a whole-struct copy at the end would
   // keep all ~225 words live to the last instruction).
@@ -274,9 +276,9 @@ FFD_HD void node_primal(const DevConsts& C, int mode, bool surface, const double
   RBOut<double> K;
   double M[28];
   if (with_dyn) {
-    rb_pass<double, true, true>(C.rb, q, v, zero, nullptr, K, M);
+    rb_pass<double, true, true>(C.rb, q, v, zero, nullptr, K, M, lrow);
   } else {
-    rb_pass<double, false, false>(C.rb, q, v, zero, nullptr, K, nullptr);
+    rb_pass<double, false, false>(C.rb, q, v, zero, nullptr, K, nullptr, lrow);
   }
   #pragma unroll
   for (int i = 0; i < NQ; ++i) {
@@ -955,9 +957,9 @@ FFD_HD void node_tangent_control(const DevConsts& C, bool surface, const Primal&
 template <int NC, bool FF>
 FFD_HD void node_calc(const DevConsts& C, bool terminal, bool surface, const double* y, const double* w,
                       const double* ref, const double* xreg, const double* tauref, const double* yref, Primal& P,
-                      double* ynext, double& cost, const double* fnr = nullptr) {
+                      double* ynext, double& cost, const double* fnr = nullptr, const double* lrow = nullptr) {
   if (!FF) {
-    node_primal<NC>(C, terminal ? MODE_TERMINAL_X : MODE_RUNNING, surface, y, w, ref, xreg, tauref, P, nullptr, fnr);
+    node_primal<NC>(C, terminal ? MODE_TERMINAL_X : MODE_RUNNING, surface, y, w, ref, xreg, tauref, P, nullptr, fnr, lrow);
     for (int i = 0; i < 14; ++i) ynext[i] = P.xnext[i];
     cost = terminal ? P.cost : C.dt * P.cost;
     return;
@@ -965,7 +967,7 @@ FFD_HD void node_calc(const DevConsts& C, bool terminal, bool surface, const dou
   const double* tau = y + 14;
   double wz[7] = {0, 0, 0, 0, 0, 0, 0};
   const double* ww = terminal ? wz : w;
-  node_primal<NC>(C, terminal ? MODE_TERMINAL_U : MODE_RUNNING, surface, y, tau, ref, xreg, tauref, P, nullptr, fnr);
+  node_primal<NC>(C, terminal ? MODE_TERMINAL_U : MODE_RUNNING, surface, y, tau, ref, xreg, tauref, P, nullptr, fnr, lrow);
   for (int i = 0; i < 14; ++i) ynext[i] = P.xnext[i];
   for (int i = 0; i < 7; ++i) ynext[14 + i] = C.alpha * tau[i] + C.beta * ww[i];
   double c = C.dt * P.cost;

@@ -80,13 +80,18 @@ __device__ __forceinline__ double friction_cone_w(const DevConsts& C, const doub
 // UL: the torque soft-limit barrier's bounds are +-ulr[4 j + 1] (the instance's
 // torque-limit row, ffddp.h FFDDP_TAU_LIM_W) instead of C.ts_lb / ts_ub, read
 // by the joint lane at the barrier, for the same reason.
-template <int NC, bool FR = false, bool CW = false, bool UL = false>
+// MD: the joint lane's mass, centre of mass and rotational inertia are the 13
+// values of its block mdr[16 j ..] of the instance's link-model row (ffddp.h
+// FFDDP_LINK_W) instead of C.rb's, read where the link inertia is formed, for
+// the same reason; the expressions are the same.
+template <int NC, bool FR = false, bool CW = false, bool UL = false, bool MD = false>
 __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, bool surface, double q, double v, double u,
                                                  double xq, double xv, double tr, const double* ref,
                                                  Primal* __restrict__ gp, double* __restrict__ lk, double (&lam)[3],
                                                  const double* __restrict__ fnp = nullptr,
                                                  const double* __restrict__ cwr = nullptr,
-                                                 const double* __restrict__ ulr = nullptr) {
+                                                 const double* __restrict__ ulr = nullptr,
+                                                 const double* __restrict__ mdr = nullptr) {
   const ffddp_robot& rb = C.rb;
   const int li = g8_lane();
   const bool J = li < NQ;
@@ -225,11 +230,12 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
   // ---- per-link inertia (world) : m, h = m c, I_O, and Iw for the link forces ----
   double m = 0.0, cw[3] = {0, 0, 0}, Iw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (J) {
-    m = rb.mass[ji];
-    const double* Ic = rb.inertia[ji];
+    m = MD ? mdr[16 * ji] : rb.mass[ji];
+    const double* Ic = MD ? mdr + 16 * ji + 4 : rb.inertia[ji];
+    const double* cm = MD ? mdr + 16 * ji + 1 : rb.com[ji];
 #pragma unroll
     for (int r = 0; r < 3; ++r)
-      cw[r] = o[r] + (R[3 * r + 0] * rb.com[ji][0] + R[3 * r + 1] * rb.com[ji][1] + R[3 * r + 2] * rb.com[ji][2]);
+      cw[r] = o[r] + (R[3 * r + 0] * cm[0] + R[3 * r + 1] * cm[1] + R[3 * r + 2] * cm[2]);
     double IcR[9];
 #pragma unroll
     for (int r = 0; r < 3; ++r)

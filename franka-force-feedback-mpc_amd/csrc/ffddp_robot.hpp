@@ -30,10 +30,12 @@ template <class T> struct RBOut {
 
 // a: joint acceleration (fixed, no tangent);  lam_w: world-aligned linear
 // contact force on the robot at the EE origin (or nullptr);  M: 28 packed
-// lower-triangular entries (only when WITH_M).
+// lower-triangular entries (only when WITH_M).  lrow: an instance's link-model
+// row (ffddp.h FFDDP_LINK_W: 16 i mass, 16 i + 1 com, 16 i + 4 inertia), read in
+// place of rb.mass / com / inertia; null: rb's.
 template <class T, bool WITH_TAU, bool WITH_M>
 FFD_HD void rb_pass(const ffddp_robot& rb, const T* q, const T* v, const double* a, const double* lam_w,
-                    RBOut<T>& out, double* M) {
+                    RBOut<T>& out, double* M, const double* lrow = nullptr) {
   M3<T> Rprev = m3eye<T>();
   V3<T> oprev = v3zero<T>();
   V3<T> vO = v3zero<T>(), w = v3zero<T>(), aO = v3zero<T>(), al = v3zero<T>();
@@ -68,12 +70,14 @@ FFD_HD void rb_pass(const ffddp_robot& rb, const T* q, const T* v, const double*
     out.z[i] = z;
     out.o[i] = o;
     if (WITH_TAU || WITH_M) {
-      const double m = rb.mass[i];
-      const V3<T> cw = o + mulc_v(R, rb.com[i]);
+      const double m = lrow ? lrow[16 * i] : rb.mass[i];
+      const double* lcom = lrow ? lrow + 16 * i + 1 : rb.com[i];
+      const double* lI = lrow ? lrow + 16 * i + 4 : rb.inertia[i];
+      const V3<T> cw = o + mulc_v(R, lcom);
       if (WITH_TAU) {
         // Icw x = R (Ic (R^T x))
-        const V3<T> Iw = mul(R, cmul(rb.inertia[i], mulT(R, w)));
-        const V3<T> Ial = mul(R, cmul(rb.inertia[i], mulT(R, al)));
+        const V3<T> Iw = mul(R, cmul(lI, mulT(R, w)));
+        const V3<T> Ial = mul(R, cmul(lI, mulT(R, al)));
         const V3<T> hl = scale(vO - cross(cw, w), m);
         const V3<T> ha = cross(cw, hl) + Iw;
         const V3<T> ag = aO - g;
@@ -94,8 +98,7 @@ FFD_HD void rb_pass(const ffddp_robot& rb, const T* q, const T* v, const double*
         double IcR[9];  // Ic R^T
         for (int r = 0; r < 3; ++r)
           for (int cc = 0; cc < 3; ++cc)
-            IcR[3 * r + cc] = rb.inertia[i][3 * r + 0] * Rd[3 * cc + 0] + rb.inertia[i][3 * r + 1] * Rd[3 * cc + 1] +
-                              rb.inertia[i][3 * r + 2] * Rd[3 * cc + 2];
+            IcR[3 * r + cc] = lI[3 * r + 0] * Rd[3 * cc + 0] + lI[3 * r + 1] * Rd[3 * cc + 1] + lI[3 * r + 2] * Rd[3 * cc + 2];
         double Iw[9];
         for (int r = 0; r < 3; ++r)
           for (int cc = 0; cc < 3; ++cc)
@@ -267,10 +270,11 @@ FFD_HD void rb_links(const ffddp_robot& rb, const double* q, const double* v, co
 }
 
 // gravity torque rnea(q, 0, 0) (crocoddyl_classical.py:447-451)
-FFD_HD void gravity_torque(const ffddp_robot& rb, const double* q, double* tau) {
+// lrow: the instance's link-model row in place of rb's inertial parameters; null: rb's
+FFD_HD void gravity_torque(const ffddp_robot& rb, const double* q, double* tau, const double* lrow = nullptr) {
   double zero[FFDDP_NQ] = {0, 0, 0, 0, 0, 0, 0};
   RBOut<double> o;
-  rb_pass<double, true, false>(rb, q, zero, zero, nullptr, o, nullptr);
+  rb_pass<double, true, false>(rb, q, zero, zero, nullptr, o, nullptr, lrow);
   for (int i = 0; i < FFDDP_NQ; ++i) tau[i] = o.tau[i];
 }
 

@@ -168,6 +168,14 @@ struct LsW {
 struct LsL {
   double uub, tsub, wslim;
 };
+// A joint lane's block of its instance's link-model row (ffddp.h
+// FFDDP_LINK_W): mass, centre of mass and rotational inertia, loaded once
+// before the node loop and held in registers for the same reason.  The EE lane
+// and the ROW layout's phantom lanes hold exact zeros, as LaneK gives them: the
+// unmasked suffix sums rely on it.
+struct LsM {
+  double m, com[3], I[9];
+};
 
 // friction-cone cost (ffddp_node.hpp friction_cone, value only); CW: the weight is W's entry
 template <bool CW>
@@ -265,8 +273,10 @@ template <bool ROW> __device__ __forceinline__ double ls_bwd(const double (&Lt)[
 // entries and discarded, as they are discarded without CW.
 // UL: the torque soft-limit barrier's bounds are +-L.tsub (the instance's
 // torque-limit row) instead of K's; L is unused otherwise.
-template <int NC, bool ROW, bool FR = false, bool CW = false, bool UL = false>
-__device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, const LaneK& K, const LsW& W, const LsL& L, int mode, bool surface, double q,
+// MD: the link's mass, centre of mass and rotational inertia are M's (the
+// instance's link-model row) instead of K's; M is unused otherwise.
+template <int NC, bool ROW, bool FR = false, bool CW = false, bool UL = false, bool MD = false>
+__device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, const LaneK& K, const LsW& W, const LsL& L, const LsM& M, int mode, bool surface, double q,
                                              double v, double u, double xq, double xv, double tr, const double* ref,
                                              double fnr, double& qn, double& vn, double& cpart, double (&lam)[3]
 #ifdef FFDDP_PHASE_PROF
@@ -434,16 +444,17 @@ __device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, co
   if (with_dyn) {
     // ---- link forces (RNEA, qdd = 0) and CRBA tuples ----
     // every lane, unmasked: lane 7 (the EE frame) and the ROW layout's
-    // phantom lanes have zero mass and inertia in LaneK, so their link force
-    // and CRBA tuple come out zero
+    // phantom lanes have zero mass and inertia in LaneK (MD: in M), so their
+    // link force and CRBA tuple come out zero
     double sf[16];  // suffix-summed tuple: fl(3) fa(3) th(3) tI(6) tm
     {
-      const double m = K.m;
-      const double* Ic = K.I;
+      const double m = MD ? M.m : K.m;
+      const double* Ic = MD ? M.I : K.I;
+      const double* cm = MD ? M.com : K.com;
       double cw[3];
 #pragma unroll
       for (int r = 0; r < 3; ++r)
-        cw[r] = o[r] + ls_dot3(R[3 * r + 0], K.com[0], R[3 * r + 1], K.com[1], R[3 * r + 2], K.com[2]);
+        cw[r] = o[r] + ls_dot3(R[3 * r + 0], cm[0], R[3 * r + 1], cm[1], R[3 * r + 2], cm[2]);
       // world inertia Iw = R Ic R^T (symmetric: six entries)
       double IcR[9], Iw[9];
 #pragma unroll

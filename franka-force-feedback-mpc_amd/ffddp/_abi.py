@@ -72,6 +72,11 @@ SYMBOLS = (
     "ffddp_calc_diff_lim",
     "ffddp_torque_limit_rows",
     "ffddp_fleet_post_lim_dev",
+    "ffddp_solve_batch_mdl_dev",
+    "ffddp_calc_diff_mdl",
+    "ffddp_link_model_rows",
+    "ffddp_gravity_torque_mdl_dev",
+    "ffddp_fleet_pre_mdl_dev",
 )
 PLANT_OBS = 69
 # FFDDP_PLANT_ROW_*: one instance's physics row (ffddp_plant_set_instance_params)
@@ -181,6 +186,10 @@ COST_INDEX = {
 # FFDDP_TAU_LIM_W: one instance's torque-limit row (ffddp_solve_batch_lim_dev), joint-major: entry 4j u_ub[j],
 # 4j + 1 ts_ub[j], 4j + 2 ws_lim[j], the rest padding (config.torque_limit_rows builds rows)
 TAU_LIM_W = 32
+
+# FFDDP_LINK_W: one instance's link-model row (ffddp_solve_batch_mdl_dev), joint-major: entry 16j mass[j],
+# 16j + 1..3 com[j], 16j + 4..12 inertia[j] row-major, the rest padding (config.link_model_rows builds rows)
+LINK_W = 128
 
 FLEET_FORCE_W = 4  # FFDDP_FLEET_FORCE_W: doubles per force record, f0, f1, t_on, t_ramp (trajectory.force_records)
 
@@ -402,13 +411,15 @@ def _fill(arr, values):
         buf[i] = float(v)
 
 
-def make_robot() -> Robot:
+def make_robot(model=None) -> Robot:
+    """The Panda's ffddp_robot; model (robot.LinkModel): its inertial
+    parameters in place of the nominal ones, the kinematics unchanged."""
     rb = Robot()
     _fill(rb.joint_R, R.JOINT_R)
     _fill(rb.joint_p, R.JOINT_P)
-    _fill(rb.mass, R.MASS)
-    _fill(rb.com, R.COM)
-    _fill(rb.inertia, R.INERTIA)
+    _fill(rb.mass, R.MASS if model is None else model.mass)
+    _fill(rb.com, R.COM if model is None else model.com)
+    _fill(rb.inertia, R.INERTIA if model is None else model.inertia)
     _fill(rb.ee_R, R.EE_R)
     _fill(rb.ee_p, R.EE_P)
     _fill(rb.gravity, R.GRAVITY)
@@ -471,12 +482,21 @@ def load() -> C.CDLL:
     lib.ffddp_calc_diff_lim.restype = C.c_int
     lib.ffddp_torque_limit_rows.argtypes = [C.POINTER(OcpConfig), C.c_int, dp, dp]
     lib.ffddp_torque_limit_rows.restype = C.c_int
+    # ..., stats, active, force_ref, cost_w, tau_lim, link_rows, stream
+    lib.ffddp_solve_batch_mdl_dev.argtypes = dev_args[:-1] + [vp, vp, vp, vp, vp, vp]
+    lib.ffddp_solve_batch_mdl_dev.restype = C.c_int
+    lib.ffddp_calc_diff_mdl.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, up, dp, dp, dp, dp, dp, dp] + [dp] * 10
+    lib.ffddp_calc_diff_mdl.restype = C.c_int
+    lib.ffddp_link_model_rows.argtypes = [C.POINTER(Robot), C.c_int, dp]
+    lib.ffddp_link_model_rows.restype = C.c_int
     lib.ffddp_frame_placement.argtypes = [C.POINTER(Robot), dp, dp, dp]
     lib.ffddp_frame_placement.restype = C.c_int
     lib.ffddp_gravity_torque.argtypes = [C.POINTER(Robot), C.c_int, dp, dp]
     lib.ffddp_gravity_torque.restype = C.c_int
     lib.ffddp_gravity_torque_dev.argtypes = [C.c_void_p, C.c_int, vp, vp, vp]
     lib.ffddp_gravity_torque_dev.restype = C.c_int
+    lib.ffddp_gravity_torque_mdl_dev.argtypes = [C.c_void_p, C.c_int, vp, vp, vp, vp]
+    lib.ffddp_gravity_torque_mdl_dev.restype = C.c_int
     lib.ffddp_build_problem_dev.argtypes = [C.c_void_p, C.c_int, C.POINTER(Task)] + [vp] * 6
     lib.ffddp_build_problem_dev.restype = C.c_int
     lib.ffddp_profile_enable.argtypes = [C.c_void_p, C.c_int]
@@ -552,6 +572,11 @@ def load() -> C.CDLL:
     lib.ffddp_fleet_pre_task_dev.argtypes = (fl + [vp] * 5 + [C.c_int, C.c_int, vp, C.c_int, vp, FleetTasks] + [vp] * 6
                                              + [C.POINTER(FleetSched), vp])
     lib.ffddp_fleet_pre_task_dev.restype = C.c_int
+    # per-instance link models: tasks (rec NULL = node_ref1 / contact_hint), node_ref1, contact_hint, the outputs,
+    # const ffddp_fleet_sched* (NULL = unscheduled), link_rows, stream
+    lib.ffddp_fleet_pre_mdl_dev.argtypes = (fl + [vp] * 5 + [C.c_int, C.c_int, vp, C.c_int, vp, FleetTasks, vp, C.c_int]
+                                            + [vp] * 6 + [C.POINTER(FleetSched), vp, vp])
+    lib.ffddp_fleet_pre_mdl_dev.restype = C.c_int
     # the task metrics: B, ld, obs, ld_obs, tasks, rows, dt, p_ref, ts, t_phase, fn_des, info, need, plant_fail, acc
     lib.ffddp_fleet_metrics_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, vp, C.c_int, FleetTasks, C.c_int, C.c_double,
                                             vp, C.c_double, vp, C.c_double, vp, vp, vp, vp] + [vp]
@@ -632,12 +657,13 @@ def frame_placement(q) -> tuple[np.ndarray, np.ndarray]:
     return Rm.reshape(3, 3), p
 
 
-def gravity_torque(q) -> np.ndarray:
-    """rnea(q, 0, 0) for a batch (B,7) on the host via the library's model code."""
+def gravity_torque(q, robot: Robot = None) -> np.ndarray:
+    """rnea(q, 0, 0) for a batch (B,7) on the host via the library's model code;
+    robot: another ffddp_robot (make_robot(model)) than the nominal one."""
     lib = load()
     q = np.ascontiguousarray(np.atleast_2d(q), dtype=np.float64)
     out = np.zeros_like(q)
-    rc = lib.ffddp_gravity_torque(C.byref(robot_struct()), q.shape[0], dptr(q), dptr(out))
+    rc = lib.ffddp_gravity_torque(C.byref(robot_struct() if robot is None else robot), q.shape[0], dptr(q), dptr(out))
     if rc:
         raise RuntimeError(f"ffddp_gravity_torque failed ({rc})")
     return out

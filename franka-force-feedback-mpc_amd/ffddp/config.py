@@ -168,6 +168,30 @@ def torque_limit_rows(cfg, limits) -> np.ndarray:
     return rows
 
 
+def link_model_rows(models) -> np.ndarray:
+    """(B, _abi.LINK_W) float64: the link-model rows of a solve's
+    ``link_model`` (ffddp_solve_batch_mdl_dev) for B robot.LinkModel objects
+    (None: the nominal model), packed by the library's own code
+    (ffddp_link_model_rows).  A row of the handle's model repeats the handle's
+    constants.  A mass that is not finite and > 0, or a com or inertia entry
+    that is not finite, raises ValueError."""
+    import ctypes as C
+
+    from . import robot as R
+
+    models = [R.LinkModel() if m is None else m for m in models]
+    B = len(models)
+    robots = (_abi.Robot * max(B, 1))()
+    for b, m in enumerate(models):
+        robots[b] = _abi.make_robot(m)
+    rows = np.zeros((B, _abi.LINK_W))
+    rc = _abi.load().ffddp_link_model_rows(robots, B, _abi.dptr(rows))
+    if rc:
+        raise ValueError(f"link_model_rows: a mass must be finite and > 0, com and inertia finite "
+                         f"(ffddp_link_model_rows failed, {rc})")
+    return rows
+
+
 def classical_preset(horizon: int = 30, contact_model: str = "normal_1d") -> OcpConfig:
     """run_classical.py:269-315 (benchmark mode).  The reference preset uses N=36; BASELINE uses 30 (R9)."""
     return OcpConfig(variant="classical", horizon=horizon, contact_model=contact_model)

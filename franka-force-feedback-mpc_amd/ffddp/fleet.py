@@ -654,6 +654,30 @@ def sweep_limit_scales(seed, limit_spread) -> np.ndarray:
     return out
 
 
+def check_payload_spread(payload_spread) -> Tuple[float, float]:
+    """run_sweep's payload_spread, checked: (m_lo, m_hi) in kg, finite, 0 <= m_lo <= m_hi (ValueError otherwise)."""
+    try:
+        rng_ = tuple(float(x) for x in payload_spread)
+    except TypeError:
+        rng_ = ()
+    if len(rng_) != 2 or not all(np.isfinite(rng_)) or not 0.0 <= rng_[0] <= rng_[1]:
+        raise ValueError(f"run_sweep: payload_spread is (m_lo, m_hi), 0 <= m_lo <= m_hi, not {payload_spread!r}")
+    return rng_
+
+
+def sweep_payload_masses(seed, payload_spread) -> np.ndarray:
+    """The sweep's per-instance payload masses (B,) in the controllers' models:
+    instance b's is m_lo + (m_hi - m_lo) u, with u one uniform in [0, 1] from
+    default_rng([seed_b, 7]) -- a generator of its own, so no other draw of
+    the sweep moves."""
+    lo_, hi_ = check_payload_spread(payload_spread)
+    out = np.zeros(len(seed))
+    for b, s_ in enumerate(seed):
+        u = np.random.default_rng([int(s_), 7]).uniform(0.0, 1.0)
+        out[b] = lo_ + (hi_ - lo_) * u
+    return out
+
+
 def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilted_15", "actuation_uncertainty"),
               seeds: int = 256, total_time: float = 4.0, rank: int = 0, world: int = 1, device: int = 0,
               q_sigma: float = 0.02, verbose: bool = True, record: Sequence[int] = (),
@@ -666,7 +690,8 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
               uncertainty_spread: Optional[Tuple[float, int]] = None,
               force_spread: Optional[Tuple[float, float]] = None, force_ramp: Optional[float] = None,
               weight_spread: Optional[dict] = None,
-              limit_spread: Optional[Tuple[float, float]] = None) -> dict:
+              limit_spread: Optional[Tuple[float, float]] = None,
+              payload_spread: Optional[Tuple[float, float]] = None) -> dict:
     """Closed-loop sweep of len(scenarios) * seeds instances; this rank runs
     its contiguous shard.  Returns per-instance summary arrays (this shard).
     record: shard-local instance indices whose controller inputs (the plant
@@ -759,7 +784,16 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     times lo (hi / lo)^((1 + u) / 2), log-uniform, u uniform in [-1, 1] from
     default_rng([seed_b, 6]) (sweep_limit_scales; the other draws do not
     move).  The summary carries ``limit_scale`` (B,), the drawn scales, and
-    ``tau_limits`` (B, 7), the limits the solves and the command clip took."""
+    ``tau_limits`` (B, 7), the limits the solves and the command clip took.
+    payload_spread (with device_loop only, NotImplementedError otherwise: the
+    host fleets plan with the nominal model): each instance's controller plans
+    with its own rigid-body model (DeviceFleetLoop(link_models=...)), the
+    nominal arm with a point payload at the EE offset
+    (robot.LinkModel.with_payload); the plant is not changed, so this is the
+    model-mismatch sweep.  payload_spread = (m_lo, m_hi) in kg: instance b's
+    payload mass is m_lo + (m_hi - m_lo) u, u uniform in [0, 1] from
+    default_rng([seed_b, 7]) (sweep_payload_masses; the other draws do not
+    move).  The summary carries ``payload_mass`` (B,), the drawn masses."""
     variant = str(variant).strip().lower()
     if variant not in ("classical", "ff"):
         raise ValueError(f"run_sweep: unknown variant {variant!r}")
@@ -812,6 +846,11 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
         if not device_loop:
             raise NotImplementedError("run_sweep: limit_spread needs device_loop=True "
                                       "(the host fleets solve within the configuration's limits)")
+    if payload_spread is not None:
+        payload_spread = check_payload_spread(payload_spread)
+        if not device_loop:
+            raise NotImplementedError("run_sweep: payload_spread needs device_loop=True "
+                                      "(the host fleets plan with the nominal model)")
     device_refs = bool(device_refs) or task_spread is not None or stagger > 0
     if device_refs and not device_loop:
         raise NotImplementedError("run_sweep: device_refs, task_spread and stagger need device_loop=True "
@@ -887,7 +926,8 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
                                 allow_plant_fail=plant_spread is not None or uncertainty_spread is not None,
                                 force_profiles=profiles,
                                 weights=sweep_cost_weights(seed, weight_spread) if weight_spread else None,
-                                limit_scale=sweep_limit_scales(seed, limit_spread) if limit_spread else None)
+                                limit_scale=sweep_limit_scales(seed, limit_spread) if limit_spread else None,
+                                payload_mass=sweep_payload_masses(seed, payload_spread) if payload_spread else None)
         out.update(names=names, seed=seed, shard=(lo, hi), n_all=n_all)
         return out
     plant = BatchedPlant(B, timestep=0.001, n_substeps=5, device=device, physics=physics)
@@ -1029,7 +1069,7 @@ DEVICE_MEMORY: dict = {}  # the last device-loop sweep's memory figures (tools/s
 def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, total_time, neg_step_rule, device, t_cp,
                       verbose, ucfgs=None, noise=None, solve_period=1, command_filter=False, tasks=None,
                       device_summary=False, keep_logs=True, plant_physics=None, allow_plant_fail=False,
-                      force_profiles=None, weights=None, limit_scale=None) -> dict:
+                      force_profiles=None, weights=None, limit_scale=None, payload_mass=None) -> dict:
     """run_sweep's loop on the device (fleet_loop.DeviceFleetLoop) and the
     host path's summary from the downloaded logs.  tasks: per-instance
     FleetTasks in place of traj; the summary's reference position and its
@@ -1041,7 +1081,9 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     each instance's own reference at the sample's series time.  weights:
     {name: (B,) values} (sweep_cost_weights), each instance's own cost weights
     over the configuration's.  limit_scale: (B,) scales (sweep_limit_scales) of
-    the configuration's tau_limits, each instance's own torque limits."""
+    the configuration's tau_limits, each instance's own torque limits.
+    payload_mass: (B,) masses (sweep_payload_masses) of a point payload at the
+    EE offset in each instance's controller model."""
     import torch
 
     from .fleet_loop import DeviceFleetLoop
@@ -1062,7 +1104,9 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
                            plant_physics=plant_physics, force_profiles=force_profiles,
                            cost_weights=None if weights is None else
                            [{name: float(v[b]) for name, v in weights.items()} for b in range(B)],
-                           torque_limits=None if limit_scale is None else np.asarray(limit_scale, float))
+                           torque_limits=None if limit_scale is None else np.asarray(limit_scale, float),
+                           link_models=None if payload_mass is None else
+                           [R.LinkModel().with_payload(float(m), R.EE_P) for m in payload_mass])
     wall0 = time.perf_counter()
     loop.run(steps)
     torch.cuda.synchronize(loop.dev)
@@ -1094,6 +1138,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
             out.update(weights=weights, cost_rows=r["cost_rows"])
         if limit_scale is not None:
             out.update(limit_scale=np.asarray(limit_scale, float), tau_limits=loop.tau_limits)
+        if payload_mass is not None:
+            out.update(payload_mass=np.asarray(payload_mass, float))
         if tasks is not None and keep_logs:
             out.update(solved=r["solved"], surface=r["surface"] != 0)
         return out
@@ -1136,6 +1182,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
         out.update(weights=weights, cost_rows=r["cost_rows"])
     if limit_scale is not None:
         out.update(limit_scale=np.asarray(limit_scale, float), tau_limits=loop.tau_limits)
+    if payload_mass is not None:
+        out.update(payload_mass=np.asarray(payload_mass, float))
     if tasks is not None:
         out.update(solved=r["solved"], surface=r["surface"] != 0)  # (ticks, B): the per-tick solve share
     return out

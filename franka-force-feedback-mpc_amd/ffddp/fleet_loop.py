@@ -95,6 +95,15 @@ other per-instance option; there is no launch more per tick and ``state`` /
 ``load_state`` carry nothing for them.  Without the argument the loop enqueues
 exactly the calls it did.
 
+With ``link_models`` every instance plans with its own rigid-body model
+(ffddp_solve_batch_mdl_dev, ffddp_fleet_pre_mdl_dev): one robot.LinkModel per
+instance (None: the nominal one).  The rows (config.link_model_rows) are
+uploaded once and every tick's pre -- the gravity torque reference -- and solve
+take them, scheduled or not, together with every other per-instance option;
+there is no launch more per tick and ``state`` / ``load_state`` carry nothing
+for them.  The plant is not touched.  Without the argument the loop enqueues
+exactly the calls it did.
+
 Not on the device, and so not supported here: ``run_sweep``'s ``record`` and
 any per-tick host callback; ``tick()`` lets a caller look between ticks at the price of its own
 synchronisation.
@@ -107,7 +116,7 @@ import numpy as np
 
 from . import _abi
 from . import robot as R
-from .config import cost_weight_row, torque_limit_rows
+from .config import cost_weight_row, link_model_rows, torque_limit_rows
 from .controller import ff_filter_alpha
 from .fleet import Traj, fleet_ocp_config, node_ref, site_calibration
 from .trajectory import FleetTask, ForceProfile, force_records, task_records
@@ -270,6 +279,9 @@ class DeviceFleetLoop:
     torque_limits: None, a (B, 7) array of torque limits, or B scalars that
     scale the configuration's tau_limits; ``tau_limits`` (B, 7) keeps the
     limits and ``limit_rows`` (B, TAU_LIM_W) the rows as uploaded.
+    link_models: None, or one robot.LinkModel (or None, the nominal model) per
+    instance, the model its controller plans with; ``link_rows`` (B, LINK_W)
+    keeps the rows as uploaded.
 
     ``S``: the controller state, ``T``: the solve's arrays, ``P``: the plant's
     (q, v, obs, tau_app, tau_filt, plane), ``J``: the injector's (row, a, b,
@@ -286,13 +298,17 @@ class DeviceFleetLoop:
                  tasks: Optional[Sequence[FleetTask]] = None, metrics: bool = False, logs: bool = True,
                  t_contact_phase=None, plant_physics=None,
                  force_profiles: Optional[Sequence[Optional[ForceProfile]]] = None, cost_weights=None,
-                 torque_limits=None):
+                 torque_limits=None, link_models=None):
         variant = str(variant).strip().lower()
         if variant not in ("classical", "ff"):
             raise ValueError(f"DeviceFleetLoop: unknown variant {variant!r}")
         inst_limits = None
         if torque_limits is not None:
             inst_limits = instance_torque_limits(config.tau_limits, torque_limits, B)
+        if link_models is not None:
+            link_models = list(link_models)
+            if len(link_models) != int(B) or not all(m is None or isinstance(m, R.LinkModel) for m in link_models):
+                raise ValueError("DeviceFleetLoop: link_models takes one robot.LinkModel (or None) per instance")
         metrics, logs = bool(metrics), bool(logs)
         if not logs and not metrics:
             raise ValueError("DeviceFleetLoop: logs=False needs metrics=True (a run without either reports nothing)")
@@ -440,6 +456,11 @@ class DeviceFleetLoop:
             self.tau_limits = inst_limits
             self.limit_rows = torque_limit_rows(self.solver.cfg, inst_limits)
             self.ul = up(self.limit_rows)
+        # per-instance link models (ffddp_solve_batch_mdl_dev, ffddp_fleet_pre_mdl_dev): the rows, uploaded once
+        self.link_rows = self.md = None
+        if link_models is not None:
+            self.link_rows = link_model_rows(link_models)
+            self.md = up(self.link_rows)
         self.log_info = torch.full((rows, B, _abi.FLEET_INFO_W), float("nan"), **f64)
         self.log_obs = torch.full((rows + 1 if logs else 1, B, _abi.FLEET_LOG_W), float("nan"), **f64)
         self.log_fail = z(rows + 1, B, dtype=torch.int32)  # without logs: the start's row and the ticks'
@@ -581,15 +602,20 @@ class DeviceFleetLoop:
         if self.ul is not None:
             fkw = dict(fkw, torque_limits=self.ul)
             pkw = dict(torque_limits=self.ul)
+        mkw = {}
+        if self.md is not None:
+            fkw = dict(fkw, link_model=self.md)
+            mkw = dict(link_model=self.md)
         if self.sched is None:
-            self.solver.fleet_pre_dev(T, self.params, hint, stream=self._stream, tasks=self.ktasks)
+            self.solver.fleet_pre_dev(T, self.params, hint, stream=self._stream, tasks=self.ktasks, **mkw)
             if self.frec is not None:
                 self._force_refs()
             self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream, **fkw)
             self.solver.fleet_post_dev(T, self.params, lpf=LPF_ALPHA, stream=self._stream, **pkw)
         else:
             T["need"] = self.log_need[r]
-            self.solver.fleet_pre_dev(T, self.params, hint, stream=self._stream, sched=self.sched, tasks=self.ktasks)
+            self.solver.fleet_pre_dev(T, self.params, hint, stream=self._stream, sched=self.sched, tasks=self.ktasks,
+                                      **mkw)
             if self.frec is not None:
                 self._force_refs()
             self.solver.solve_dev(T, maxiter=int(self.cfg.max_iters), is_feasible=False, stream=self._stream,

@@ -70,6 +70,55 @@ _c, _s = np.cos(np.deg2rad(135.0)), np.sin(np.deg2rad(135.0))
 R_SITE_FROM_EE = np.array([[_c, -_s, 0.0], [_s, _c, 0.0], [0.0, 0.0, 1.0]])  # tool quat (:189)
 
 
+def _spread(d) -> np.ndarray:
+    """S(d) = |d|^2 I - d d^T: the parallel-axis term of a unit mass at offset d."""
+    d = np.asarray(d, float)
+    return float(d @ d) * np.eye(3) - np.outer(d, d)
+
+
+class LinkModel:
+    """The seven links' inertial parameters, what a controller believes about
+    its arm: mass (7,), com (7, 3) in the link frames, inertia (7, 3, 3) about
+    the com in the link frames.  The default is the Panda's (MASS / COM /
+    INERTIA).  The kinematics are not part of it.  Immutable by convention:
+    with_payload and scaled return new models."""
+
+    def __init__(self, mass=None, com=None, inertia=None):
+        self.mass = np.array(MASS if mass is None else mass, dtype=np.float64)
+        self.com = np.array(COM if com is None else com, dtype=np.float64)
+        self.inertia = np.array(INERTIA if inertia is None else inertia, dtype=np.float64)
+        if self.mass.shape != (7,) or self.com.shape != (7, 3) or self.inertia.shape != (7, 3, 3):
+            raise ValueError(f"LinkModel: mass (7,), com (7, 3), inertia (7, 3, 3), not {self.mass.shape}, "
+                             f"{self.com.shape}, {self.inertia.shape}")
+
+    def with_payload(self, mass: float, com=EE_P, inertia=None) -> "LinkModel":
+        """A rigid payload fixed to link 7, combined into it: `mass`, `com`
+        (link-7 frame, by default the EE offset) and `inertia` about the
+        payload's own com (link-7 axes; None: a point mass).
+        m = m7 + mp, c = (m7 c7 + mp cp) / m,
+        I = I7 + m7 S(c7 - c) + Ip + mp S(cp - c), S(d) = |d|^2 I - d d^T."""
+        mp, cp = float(mass), np.asarray(com, float).reshape(3)
+        Ip = np.zeros((3, 3)) if inertia is None else np.asarray(inertia, float).reshape(3, 3)
+        if not (np.isfinite(mp) and mp >= 0.0):
+            raise ValueError("LinkModel.with_payload: the payload mass must be finite and >= 0")
+        m7, c7, I7 = self.mass[6], self.com[6], self.inertia[6]
+        m = m7 + mp
+        c = (m7 * c7 + mp * cp) / m
+        out = LinkModel(self.mass, self.com, self.inertia)
+        out.mass[6] = m
+        out.com[6] = c
+        out.inertia[6] = I7 + m7 * _spread(c7 - c) + Ip + mp * _spread(cp - c)
+        return out
+
+    def scaled(self, mass_scale) -> "LinkModel":
+        """Every link's mass times its factor (a scalar or (7,)); the inertia
+        scales with the mass, the com is kept."""
+        f = np.broadcast_to(np.asarray(mass_scale, float), (7,))
+        if not (np.all(np.isfinite(f)) and np.all(f > 0.0)):
+            raise ValueError("LinkModel.scaled: factors must be finite and > 0")
+        return LinkModel(self.mass * f, self.com, self.inertia * f[:, None, None])
+
+
 def vertical_down_rotation_mj() -> np.ndarray:
     """_make_vertical_down_rotation_mj (crocoddyl_classical.py:241-248)."""
     z = np.array([0.0, 0.0, -1.0])

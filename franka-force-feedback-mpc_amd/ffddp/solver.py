@@ -140,8 +140,10 @@ class _RecycledPinned:
 
 class BatchedBoxFDDP:
     def __init__(self, cfg: OcpConfig, max_batch: int, device: int = 0, pinned_outputs: bool = False,
-                 outputs: str | None = None):
-        """outputs: how solve() returns xs / us / K / cost / ...:
+                 outputs: str | None = None, robot=None):
+        """robot: a robot.LinkModel, the inertial parameters this handle plans
+        with in place of the nominal Panda's (the kinematics stay).
+        outputs: how solve() returns xs / us / K / cost / ...:
           "recycled" (default): fresh numpy arrays per solve() in page-locked
               memory recycled from earlier solves whose arrays are gone
               (_RecycledPinned; up to 4 solves' worth at max_batch), filled by
@@ -153,6 +155,7 @@ class BatchedBoxFDDP:
               outlive it, as the reference does (crocoddyl_classical.py:
               382-385)."""
         self.cfg = cfg
+        self.robot = robot
         if outputs is None:
             outputs = "pinned" if pinned_outputs else "recycled"
         if outputs not in ("recycled", "fresh", "pinned"):
@@ -172,7 +175,8 @@ class BatchedBoxFDDP:
         self._cfg_struct = cfg.to_struct()
         h = C.c_void_p()
         rc = self._lib.ffddp_create(
-            C.byref(_abi.robot_struct()), C.byref(self._cfg_struct), int(device), self.max_batch, C.byref(h)
+            C.byref(_abi.robot_struct() if robot is None else _abi.make_robot(robot)), C.byref(self._cfg_struct),
+            int(device), self.max_batch, C.byref(h)
         )
         if rc != 0:
             raise FfddpError(f"ffddp_create failed with code {rc}")
@@ -326,7 +330,7 @@ class BatchedBoxFDDP:
 
     # -- solve (device-resident torch tensors; bench path) ---------------------------
     def solve_dev(self, t, maxiter: int = 10, is_feasible: bool = False, stream=None, active=None, force_ref=None,
-                  cost_weights=None, torque_limits=None):
+                  cost_weights=None, torque_limits=None, link_model=None):
         """t: dict of contiguous torch.cuda tensors with keys x0, node_ref, inst_ref,
         surface (uint8), xs_init, us_init and outputs xs, us, K, cost, iters (int32),
         ok (uint8), fn_pred, stats (int32).  Asynchronous on `stream` (hipStream_t int).
@@ -344,10 +348,16 @@ class BatchedBoxFDDP:
         torque_limits: optional (B, _abi.TAU_LIM_W) float64 device tensor, one
         torque-limit row per instance in place of the configuration's
         tau_limits (ffddp_solve_batch_lim_dev; config.torque_limit_rows builds
-        the rows); goes with or without the other three."""
+        the rows); goes with or without the other three.
+        link_model: optional (B, _abi.LINK_W) float64 device tensor, one row of
+        link inertial parameters per instance in place of the handle's robot's
+        (ffddp_solve_batch_mdl_dev; config.link_model_rows builds the rows);
+        goes with or without the other four.  t["inst_ref"] stays the caller's:
+        gravity_torque_dev(link_model=...) gives the torque reference under
+        each instance's model."""
         B = int(t["x0"].shape[0])
         p = lambda k: C.c_void_p(int(t[k].data_ptr()))
-        rc = self._lib.ffddp_solve_batch_lim_dev(
+        rc = self._lib.ffddp_solve_batch_mdl_dev(
             self._h, B, p("x0"), p("node_ref"), p("inst_ref"), p("surface"), p("xs_init"), p("us_init"),
             int(maxiter), int(bool(is_feasible)), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
             p("fn_pred"), p("stats"),
@@ -358,9 +368,26 @@ class BatchedBoxFDDP:
                          "cost_weights must be a contiguous (B, COST_W) float64 device tensor"),
             _opt_dev_ptr(torque_limits, "float64", (B, _abi.TAU_LIM_W),
                          "torque_limits must be a contiguous (B, TAU_LIM_W) float64 device tensor"),
+            _opt_dev_ptr(link_model, "float64", (B, _abi.LINK_W),
+                         "link_model must be a contiguous (B, LINK_W) float64 device tensor"),
             C.c_void_p(stream if stream else 0),
         )
-        self._check(rc, "ffddp_solve_batch_lim_dev")
+        self._check(rc, "ffddp_solve_batch_mdl_dev")
+
+    def gravity_torque_dev(self, q, tau, link_model=None, stream=None):
+        """tau (B, 7) = rnea(q, 0, 0) for q (B, 7), contiguous float64 device
+        tensors (ffddp_gravity_torque_dev), under the handle's robot; with
+        link_model, (B, _abi.LINK_W) float64 device rows, under each instance's
+        own model (ffddp_gravity_torque_mdl_dev).  Asynchronous on `stream`."""
+        B = int(q.shape[0])
+        assert tuple(q.shape) == (B, 7) and tuple(tau.shape) == (B, 7) and q.is_contiguous() and tau.is_contiguous()
+        assert q.is_cuda and tau.is_cuda and str(q.dtype) == str(tau.dtype) == "torch.float64"
+        rc = self._lib.ffddp_gravity_torque_mdl_dev(
+            self._h, B, C.c_void_p(int(q.data_ptr())),
+            _opt_dev_ptr(link_model, "float64", (B, _abi.LINK_W),
+                         "link_model must be a contiguous (B, LINK_W) float64 device tensor"),
+            C.c_void_p(int(tau.data_ptr())), C.c_void_p(stream if stream else 0))
+        self._check(rc, "ffddp_gravity_torque_mdl_dev")
 
     # -- fleet tick glue (include/ffddp.h: ffddp_fleet_warm_start_dev / ffddp_fleet_keep_dev) --
     def fleet_warm_start_dev(self, t, stream=None):
@@ -494,7 +521,7 @@ class BatchedBoxFDDP:
         self._check(rc, "ffddp_fleet_metrics_fref_dev")
 
     def fleet_pre_dev(self, t, params: _abi.FleetParams, hint: bool = False, stream=None, sched: _abi.FleetSched = None,
-                      tasks: _abi.FleetTasks = None):
+                      tasks: _abi.FleetTasks = None, link_model=None):
         """Everything a fleet tick does before the solve, for B instances in one
         launch.  Inputs t["q"], t["v"] (B, 7), t["fn_meas"], t["ee_z"] (B,),
         optionally t["contact"] (B,) and, for force feedback, t["tau_hat"]
@@ -510,7 +537,10 @@ class BatchedBoxFDDP:
         tasks (fleet_tasks): per-instance tasks (ffddp_fleet_pre_task_dev):
         every instance's references and hint are sampled from its record at
         tasks.t minus its delay; t["node_ref1"] and `hint` are not read.
-        Asynchronous on `stream`."""
+        link_model: optional (B, _abi.LINK_W) float64 device tensor, the
+        solve's link-model rows: the gravity torque reference is each
+        instance's own (ffddp_fleet_pre_mdl_dev), with or without sched and
+        tasks.  Asynchronous on `stream`."""
         B = int(t["x0"].shape[0])
         p = lambda k: C.c_void_p(int(t[k].data_ptr()) if t.get(k) is not None else 0)
         assert t["q"].stride(0) == t["v"].stride(0) and t["fn_meas"].stride(0) == t["ee_z"].stride(0)
@@ -521,6 +551,15 @@ class BatchedBoxFDDP:
                 int(t["q"].stride(0)), int(t["fn_meas"].stride(0)), p("tau_hat"),
                 int(th.stride(0)) if th is not None else 0, p("q_nom"))
         tail = (p("x0"), p("surface"), p("inst_ref"), p("node_ref"), p("xs_init"), p("us_init"))
+        if link_model is not None:
+            sp = C.byref(self._fleet_sched(t, sched)) if sched is not None else None
+            rc = self._lib.ffddp_fleet_pre_mdl_dev(
+                *head, tasks if tasks is not None else _abi.FleetTasks(), p("node_ref1"), int(bool(hint)), *tail, sp,
+                _opt_dev_ptr(link_model, "float64", (B, _abi.LINK_W),
+                             "link_model must be a contiguous (B, LINK_W) float64 device tensor"),
+                C.c_void_p(stream if stream else 0))
+            self._check(rc, "ffddp_fleet_pre_mdl_dev")
+            return
         if tasks is not None:
             sp = C.byref(self._fleet_sched(t, sched)) if sched is not None else None
             rc = self._lib.ffddp_fleet_pre_task_dev(*head, tasks, *tail, sp, C.c_void_p(stream if stream else 0))
@@ -706,13 +745,14 @@ class BatchedBoxFDDP:
         return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(_abi.KERNEL_CLASSES)}
 
     # -- problem.calcDiff(xs, us) -------------------------------------------------------
-    def calc_diff(self, batch, xs, us, force_ref=None, cost_weights=None, torque_limits=None):
+    def calc_diff(self, batch, xs, us, force_ref=None, cost_weights=None, torque_limits=None, link_model=None):
         """force_ref: optional (B, N+1) host array, the desired normal contact
         force per instance and node (ffddp_calc_diff_fref).  cost_weights:
         optional (B, _abi.COST_W) host array, the scalar cost weights per
         instance (ffddp_calc_diff_wts).  torque_limits: optional
         (B, _abi.TAU_LIM_W) host array, the torque-limit rows per instance
-        (ffddp_calc_diff_lim)."""
+        (ffddp_calc_diff_lim).  link_model: optional (B, _abi.LINK_W) host
+        array, the link-model rows per instance (ffddp_calc_diff_mdl)."""
         B = int(batch.x0.shape[0])
         N, nx = self.N, self.nx
         f = lambda a, shape: np.ascontiguousarray(np.asarray(a, np.float64).reshape(shape))
@@ -723,7 +763,7 @@ class BatchedBoxFDDP:
             lam=np.zeros((B, N + 1, 3)),
         )
         d = _abi.dptr
-        fr = cw = ul = None
+        fr = cw = ul = md = None
         if force_ref is not None:
             fr = np.asarray(force_ref, np.float64)
             if fr.shape != (B, N + 1):
@@ -739,15 +779,20 @@ class BatchedBoxFDDP:
             if ul.shape != (B, _abi.TAU_LIM_W):
                 raise ValueError("torque_limits must have shape (B, TAU_LIM_W)")
             ul = np.ascontiguousarray(ul)
-        rc = self._lib.ffddp_calc_diff_lim(
+        if link_model is not None:
+            md = np.asarray(link_model, np.float64)
+            if md.shape != (B, _abi.LINK_W):
+                raise ValueError("link_model must have shape (B, LINK_W)")
+            md = np.ascontiguousarray(md)
+        rc = self._lib.ffddp_calc_diff_mdl(
             self._h, B, d(f(batch.x0, (B, nx))), d(f(batch.node_ref, (B, N + 1, 6))), d(f(batch.inst_ref, (B, 21))),
             _abi.uptr(np.ascontiguousarray(np.asarray(batch.surface, np.uint8))), d(f(xs, (B, N + 1, nx))),
             d(f(us, (B, N, 7))), d(fr) if fr is not None else None, d(cw) if cw is not None else None,
-            d(ul) if ul is not None else None, d(out["Fx"]),
+            d(ul) if ul is not None else None, d(md) if md is not None else None, d(out["Fx"]),
             d(out["Fu"]), d(out["Lx"]), d(out["Lu"]), d(out["Lxx"]), d(out["Lxu"]), d(out["Luu"]), d(out["cost"]),
             d(out["xnext"]), d(out["lam"]),
         )
-        self._check(rc, "ffddp_calc_diff_lim")
+        self._check(rc, "ffddp_calc_diff_mdl")
         return out
 
 

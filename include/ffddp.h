@@ -317,6 +317,44 @@ int ffddp_solve_batch_lim_dev(ffddp_handle* h, int B, const double* x0, const do
  * pointer, B < 0, or a limit that is not finite and > 0. */
 int ffddp_torque_limit_rows(const ffddp_ocp_config* cfg, int B, const double* tau_limits, double* rows);
 
+/* ffddp_solve_batch_lim_dev with the controller's rigid-body model per
+ * instance: link_rows is [B][FFDDP_LINK_W] device doubles, row b the inertial
+ * parameters instance b plans with.  A row is 128 doubles (1 KiB), joint-major,
+ * so that the 13 values a joint lane needs sit in one 128-byte line:
+ *     16j + 0          mass[j]
+ *     16j + 1 .. 3     com[j]                 in the link frame
+ *     16j + 4 .. 12    inertia[j], row-major  all nine entries, as ffddp_robot
+ *                                             holds them (nothing is symmetrised)
+ *     16j + 13 .. 15, 112 .. 127   padding, which the library never reads
+ * ffddp_link_model_rows packs ffddp_robot structs into rows, so a row of the
+ * handle's robot gives the bits of the call without link_rows.  The kinematic
+ * parameters (joint placements, the EE offset, gravity) stay the handle's.
+ *
+ * Rows of unselected instances are not read.  `active`, force_ref, cost_w and
+ * tau_lim stay optional and combine freely with link_rows (without tau_lim the
+ * solve reads rows of the configuration's limits that the handle keeps,
+ * allocated by the first such call; likewise the configuration's weights
+ * without cost_w and fn_des without a force_ref).  link_rows == NULL is
+ * ffddp_solve_batch_lim_dev: same kernels, same bits.  Errors are
+ * ffddp_solve_batch_lim_dev's.  The torque reference inst_ref[14..20] is the
+ * caller's: ffddp_gravity_torque_mdl_dev gives it under each instance's model.
+ * The host-pointer entry point, solve plans and ffddp_build_problem_dev take no
+ * rows. */
+#define FFDDP_LINK_W 128
+int ffddp_solve_batch_mdl_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                              const double* inst_ref, const uint8_t* surface, const double* xs_init,
+                              const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
+                              double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
+                              const uint8_t* active, const double* force_ref, const double* cost_w,
+                              const double* tau_lim, const double* link_rows, void* stream);
+
+/* Host function: rows [B][FFDDP_LINK_W] for ffddp_solve_batch_mdl_dev,
+ * ffddp_calc_diff_mdl, ffddp_gravity_torque_mdl_dev and ffddp_fleet_pre_mdl_dev
+ * from the mass, com and inertia of B robots (the only fields read); padding
+ * is zero.  FFDDP_E_INVALID for a null pointer, B < 0, a mass that is not
+ * finite and > 0, or a com or inertia entry that is not finite. */
+int ffddp_link_model_rows(const ffddp_robot* robots, int B, double* rows);
+
 /* Solve plan for a receding-horizon loop: one solve of a fixed batch per
  * control tick (crocoddyl_classical.py:367 called every tick at
  * run_classical.py:412).  ffddp_plan_create captures the whole host-array
@@ -392,6 +430,14 @@ int ffddp_calc_diff_lim(ffddp_handle* h, int B, const double* x0, const double* 
                         const double* us, const double* force_ref, const double* cost_w, const double* tau_lim,
                         double* Fx, double* Fu, double* Lx, double* Lu, double* Lxx, double* Lxu, double* Luu,
                         double* cost, double* xnext, double* lam);
+
+/* ffddp_calc_diff_lim with host link-model rows [B][FFDDP_LINK_W]
+ * (ffddp_solve_batch_mdl_dev's array; NULL: ffddp_calc_diff_lim). */
+int ffddp_calc_diff_mdl(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                        const double* inst_ref, const uint8_t* surface, const double* xs,
+                        const double* us, const double* force_ref, const double* cost_w, const double* tau_lim,
+                        const double* link_rows, double* Fx, double* Fu, double* Lx, double* Lu, double* Lxx,
+                        double* Lxu, double* Luu, double* cost, double* xnext, double* lam);
 
 /* Host-side setup helpers (CPU, same model code): frame placement of the EE
  * (pin.forwardKinematics + updateFramePlacements, crocoddyl_classical.py:199-225)
@@ -469,6 +515,12 @@ int ffddp_profile_read(ffddp_handle* h, double* ms, int64_t* launches, int reset
 
 /* Batched gravity torque on the device (tau_ref for B instances), device pointers. */
 int ffddp_gravity_torque_dev(ffddp_handle* h, int B, const double* q, double* tau, void* stream);
+/* The same under each instance's own model: link_rows [B][FFDDP_LINK_W] device
+ * doubles (ffddp_solve_batch_mdl_dev), the kinematics and gravity the handle's.
+ * Rows of the handle's robot give ffddp_gravity_torque_dev's bits; link_rows ==
+ * NULL is that function. */
+int ffddp_gravity_torque_mdl_dev(ffddp_handle* h, int B, const double* q, const double* link_rows, double* tau,
+                                 void* stream);
 
 /* Device-side problem builder: what _build_problem (crocoddyl_classical.py:
  * 521-556; FF :776-836) feeds the action models, for B instances at once,
@@ -860,6 +912,22 @@ int ffddp_fleet_pre_task_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p
                              const double* q_nom, ffddp_fleet_tasks tasks, double* x0, uint8_t* surface,
                              double* inst_ref, double* node_ref, double* xs_init, double* us_init,
                              const ffddp_fleet_sched* sched, void* stream);
+/* The pre stage with each instance's own rigid-body model: link_rows is the
+ * solve's [B][FFDDP_LINK_W] rows (ffddp_solve_batch_mdl_dev), with which the
+ * gravity torque reference inst_ref[14..20] of torque modes 0 and 1 is
+ * computed (ffddp_gravity_torque_mdl_dev's bits); every other output is
+ * ffddp_fleet_pre_task_dev's.  tasks.rec == NULL: the shared references
+ * node_ref1 / contact_hint of ffddp_fleet_pre_dev are used instead of the
+ * per-instance tasks.  sched as in ffddp_fleet_pre_task_dev.  link_rows ==
+ * NULL gives ffddp_fleet_pre_task_dev's (with tasks.rec == NULL
+ * ffddp_fleet_pre_dev's / _pre_sched_dev's) bits.  Errors are theirs, under
+ * this function's name. */
+int ffddp_fleet_pre_mdl_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                            const double* q, const double* v, const double* fn_meas, const double* contact,
+                            const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
+                            const double* q_nom, ffddp_fleet_tasks tasks, const double* node_ref1, int contact_hint,
+                            double* x0, uint8_t* surface, double* inst_ref, double* node_ref, double* xs_init,
+                            double* us_init, const ffddp_fleet_sched* sched, const double* link_rows, void* stream);
 
 /* The sweep's task metrics accumulated on the device: one call folds one plant
  * record per instance -- the observation after a tick's command -- into

@@ -28,6 +28,8 @@ wall time, closed-loop ticks/s).
                                                                # the controller's cost weights per instance, log-uniform
   python tools/sweep_c4.py --device-loop 1 --device-refs 1 --limit-spread 0.25 1
                                                                # the torque limits per instance, scaled log-uniformly
+  python tools/sweep_c4.py --device-loop 1 --device-refs 1 --payload-spread 0 3
+                                                               # a payload (kg) in each controller's model, uniform
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/sweep_c4.py
 """
 import argparse
@@ -107,6 +109,9 @@ def build_parser():
     ap.add_argument("--limit-spread", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="with --device-loop 1: per-instance torque limits, the configuration's scaled log-uniformly "
                          "in [LO, HI]")
+    ap.add_argument("--payload-spread", type=float, nargs=2, default=None, metavar=("M_LO", "M_HI"),
+                    help="with --device-loop 1: per-instance controller models, the nominal arm with a point payload "
+                         "of M_LO..M_HI kg (uniform) at the EE offset; the plant is unchanged")
     ap.add_argument("--scenarios", nargs="+", default=list(ALL_SCENARIOS), help="scenarios to sweep (default: all 5)")
     return ap
 
@@ -141,7 +146,7 @@ def main():
                            device_summary=bool(a.device_summary), keep_logs=bool(a.keep_logs),
                            plant_spread=a.plant_spread, uncertainty_spread=uspread,
                            force_spread=a.force_spread, force_ramp=a.force_ramp, weight_spread=wspread,
-                           limit_spread=a.limit_spread)
+                           limit_spread=a.limit_spread, payload_spread=a.payload_spread)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -207,6 +212,19 @@ def main():
             line.update(limit_spread=a.limit_spread, rank0_limit_bins=[
                 {"scale_lo": float(edges[i]), "scale_hi": float(edges[i + 1]), "instances": int(np.sum(which == i)),
                  "scale_mean": float(np.mean(sc[which == i])),
+                 "fn_mean_contact_phase": float(np.nanmean(pi["fn_mean_contact_phase"][which == i])),
+                 "avg_abs_force_err": float(np.nanmean(pi["avg_abs_force_err"][which == i])),
+                 "rms_tangential_error_contact_phase":
+                     float(np.nanmean(pi["rms_tangential_error_contact_phase"][which == i])),
+                 "contact_loss_contact_phase_pct": float(np.nanmean(pi["contact_loss_contact_phase_pct"][which == i]))}
+                for i in range(4) if np.any(which == i)])
+        if "payload_mass" in res:  # this rank's shard by the controller model's payload mass, four linear bins
+            pi, pm = res["per_instance"], res["payload_mass"]
+            edges = np.linspace(a.payload_spread[0], a.payload_spread[1], 5)
+            which = np.clip(np.digitize(pm, edges) - 1, 0, 3)
+            line.update(payload_spread=a.payload_spread, rank0_payload_bins=[
+                {"mass_lo": float(edges[i]), "mass_hi": float(edges[i + 1]), "instances": int(np.sum(which == i)),
+                 "mass_mean": float(np.mean(pm[which == i])),
                  "fn_mean_contact_phase": float(np.nanmean(pi["fn_mean_contact_phase"][which == i])),
                  "avg_abs_force_err": float(np.nanmean(pi["avg_abs_force_err"][which == i])),
                  "rms_tangential_error_contact_phase":
