@@ -2515,9 +2515,38 @@ __device__ __forceinline__ void plant_load_row(ffddp_plant_params& P, int b, con
   for (int i = 0; i < 5; ++i) P.solimp[i] = r[(FFDDP_PLANT_ROW_SOLIMP + i) * ld];
 }
 
+// The handle's device copy of the link-model rows (ffddp_plant_set_instance_links): field-major over the
+// PLANT_LINK_USED entries a row holds apart from padding, [PLANT_LINK_USED][ld], field 13 j + k being the row's
+// entry 16 j + k, so the wave's loads of one field are consecutive doubles.
+constexpr int PLANT_LINK_PER_JOINT = 13;                   // mass, com (3), inertia (9)
+constexpr int PLANT_LINK_USED = NQ * PLANT_LINK_PER_JOINT;  // 91
+constexpr int PLANT_LINK_LOCAL = 16 * (NQ - 1) + PLANT_LINK_PER_JOINT;  // a lane's row up to its last used entry
+struct PlantLinks {
+  const double* rows;
+  long ld;
+};
+
+// A lane's link-model row in rb_pass's 16 j + k indexing; the padding entries of L are neither written nor read.
+__device__ __forceinline__ void plant_load_links(double* L, int b, PlantLinks lk) {
+  const double* __restrict__ r = lk.rows + b;
+#pragma unroll
+  for (int j = 0; j < NQ; ++j)
+#pragma unroll
+    for (int k = 0; k < PLANT_LINK_PER_JOINT; ++k) L[16 * j + k] = r[(PLANT_LINK_PER_JOINT * j + k) * lk.ld];
+}
+__device__ __forceinline__ PlantLinks plant_links_of(PlantLinks lk) { return lk; }
+__device__ __forceinline__ PlantLinks plant_links_of(const double*, long, PlantLinks lk) { return lk; }
+__device__ __forceinline__ void plant_load_row(ffddp_plant_params& P, int b, const double* __restrict__ rows, long ld,
+                                               PlantLinks) {
+  plant_load_row(P, b, rows, ld);
+}
+
 // closed-loop plant stand-in: one thread per instance (ffddp_plant.hpp).  k_plant<false>: every lane steps with
 // the handle's struct; k_plant<true, const double*, long>: the trailing arguments are (rows, ld) and the lane
 // steps with its own row.  The pack keeps the first instantiation's arguments, and so its code, what they were.
+// A PlantLinks at the end of the pack (k_plant<false, PlantLinks>, k_plant<true, const double*, long, PlantLinks>):
+// the lane integrates with its own link-model row, loaded once before the substep loop, in place of rb's masses,
+// centres of mass and inertias.
 template <bool ROWS, class... RowArgs>
 __global__ __launch_bounds__(64) void k_plant(const ffddp_robot* __restrict__ rb, const ffddp_plant_params* __restrict__ pp,
                                               int B, double* __restrict__ q, double* __restrict__ v,
@@ -2534,7 +2563,17 @@ __global__ __launch_bounds__(64) void k_plant(const ffddp_robot* __restrict__ rb
   }
   const double* pl = plane + (long)b * 6;
   bool ok;
-  if constexpr (ROWS) {
+  if constexpr ((std::is_same_v<RowArgs, PlantLinks> || ...)) {
+    double L[PLANT_LINK_LOCAL];
+    plant_load_links(L, b, plant_links_of(row_args...));
+    if constexpr (ROWS) {
+      ffddp_plant_params P = *pp;
+      plant_load_row(P, b, row_args...);
+      ok = plant_step(*rb, P, qb, vb, tb, pl, pl + 3, integrate, ob, L);
+    } else {
+      ok = plant_step(*rb, *pp, qb, vb, tb, pl, pl + 3, integrate, ob, L);
+    }
+  } else if constexpr (ROWS) {
     ffddp_plant_params P = *pp;  // timestep, n_substeps and site_R stay the handle's
     plant_load_row(P, b, row_args...);
     ok = plant_step(*rb, P, qb, vb, tb, pl, pl + 3, integrate, ob);
@@ -5014,6 +5053,10 @@ struct ffddp_plant {
   // by the first call; n_rows > 0: the rows are in force
   double* rows = nullptr;
   int n_rows = 0;
+  // per-instance link models (ffddp_plant_set_instance_links): field-major [PLANT_LINK_USED][max_batch], allocated
+  // by the first call; n_links > 0: the rows are in force
+  double* links = nullptr;
+  int n_links = 0;
 };
 
 extern "C" {
@@ -5049,7 +5092,7 @@ int ffddp_plant_create(const ffddp_robot* robot, const ffddp_plant_params* p, in
 void ffddp_plant_destroy(ffddp_plant* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  void* ps[] = {h->drb, h->dpp, h->q, h->v, h->tau, h->plane, h->obs, h->fail, h->rows};
+  void* ps[] = {h->drb, h->dpp, h->q, h->v, h->tau, h->plane, h->obs, h->fail, h->rows, h->links};
   for (void* p : ps)
     if (p) (void)hipFree(p);
   delete h;
@@ -5061,8 +5104,17 @@ int ffddp_plant_step_dev(ffddp_plant* h, int B, double* q, double* v, const doub
   if (B == 0) return 0;
   if (!q || !v || !tau || !plane || !obs) return FFDDP_E_INVALID;
   if (h->n_rows > 0 && B > h->n_rows) return FFDDP_E_INVALID;
+  if (h->n_links > 0 && B > h->n_links) return FFDDP_E_INVALID;
   if (hipSetDevice(h->device) != hipSuccess) return FFDDP_E_DEVICE;
-  if (h->n_rows > 0)
+  const PlantLinks lk = {h->links, (long)h->max_batch};
+  if (h->n_links > 0 && h->n_rows > 0)
+    hipLaunchKernelGGL((k_plant<true, const double*, long, PlantLinks>), dim3((B + 63) / 64), dim3(64), 0,
+                       (hipStream_t)stream, h->drb, h->dpp, B, q, v, tau, plane, integrate, obs, fail, h->rows,
+                       (long)h->max_batch, lk);
+  else if (h->n_links > 0)
+    hipLaunchKernelGGL((k_plant<false, PlantLinks>), dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->drb,
+                       h->dpp, B, q, v, tau, plane, integrate, obs, fail, lk);
+  else if (h->n_rows > 0)
     hipLaunchKernelGGL((k_plant<true, const double*, long>), dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream,
                        h->drb, h->dpp, B, q, v, tau, plane, integrate, obs, fail, h->rows, (long)h->max_batch);
   else
@@ -5108,6 +5160,41 @@ int ffddp_plant_set_instance_params(ffddp_plant* h, int n, const double* rows) {
       hipMemcpy(h->rows, t.data(), t.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
     return FFDDP_E_DEVICE;
   h->n_rows = n;
+  return 0;
+}
+
+int ffddp_plant_set_instance_links(ffddp_plant* h, int n, const double* link_rows) {
+  if (!h) return FFDDP_E_INVALID;
+  if (!link_rows) {  // back to the handle's robot; steps already enqueued keep the copy they were launched with
+    h->n_links = 0;
+    return 0;
+  }
+  if (n < 1 || n > h->max_batch) return FFDDP_E_INVALID;
+  // what ffddp_link_model_rows refuses; the padding entries are not looked at
+  for (int b = 0; b < n; ++b) {
+    const double* r = link_rows + (size_t)b * FFDDP_LINK_W;
+    for (int j = 0; j < NQ; ++j) {
+      if (!(std::isfinite(r[16 * j]) && r[16 * j] > 0.0)) return FFDDP_E_INVALID;
+      for (int k = 1; k < PLANT_LINK_PER_JOINT; ++k)
+        if (!std::isfinite(r[16 * j + k])) return FFDDP_E_INVALID;
+    }
+  }
+  const size_t ld = (size_t)h->max_batch;
+  std::vector<double> t(ld * PLANT_LINK_USED, 0.0);  // row-major -> field-major over the used entries
+  for (int b = 0; b < n; ++b)
+    for (int j = 0; j < NQ; ++j)
+      for (int k = 0; k < PLANT_LINK_PER_JOINT; ++k)
+        t[(size_t)(PLANT_LINK_PER_JOINT * j + k) * ld + b] = link_rows[(size_t)b * FFDDP_LINK_W + 16 * j + k];
+  if (hipSetDevice(h->device) != hipSuccess) return FFDDP_E_DEVICE;
+  if (!h->links && hipMalloc((void**)&h->links, t.size() * 8) != hipSuccess) {
+    h->links = nullptr;
+    return FFDDP_E_OOM;
+  }
+  // steps in flight read the copy: wait for them, then replace it
+  if (hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(h->links, t.data(), t.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
+    return FFDDP_E_DEVICE;
+  h->n_links = n;
   return 0;
 }
 

@@ -56,9 +56,12 @@ FFD_HD void plant_solve(const double* L, double* b) { chol_solve<FFDDP_NQ>(L, b)
 
 // One control step (n_substeps physics steps) of one instance.  q, v in/out;
 // tau applied torque (qfrc_applied); n_mj, p0_mj: table plane normal / point
-// (MuJoCo world); obs: PO_WORDS.  Returns false on a non-SPD mass matrix.
+// (MuJoCo world); obs: PO_WORDS.  lrow: the instance's link-model row (rb_pass's
+// 16 j + k indexing) in place of rb's masses, centres of mass and inertias;
+// null: rb's.  Returns false on a non-SPD mass matrix.
 FFD_HD bool plant_step(const ffddp_robot& rb, const ffddp_plant_params& P, double* q, double* v, const double* tau,
-                       const double n_mj[3], const double p0_mj[3], int integrate, double* obs) {
+                       const double n_mj[3], const double p0_mj[3], int integrate, double* obs,
+                       const double* lrow = nullptr) {
   constexpr int NQ = FFDDP_NQ;
   // MuJoCo world = R_MJ_FROM_PIN . Pinocchio/link0 world, R = diag(-1, -1, 1)
   const double n[3] = {-n_mj[0], -n_mj[1], n_mj[2]};
@@ -69,7 +72,7 @@ FFD_HD bool plant_step(const ffddp_robot& rb, const ffddp_plant_params& P, doubl
     const double zero[NQ] = {0, 0, 0, 0, 0, 0, 0};
     RBOut<double> o;
     double M[28];
-    rb_pass<double, true, true>(rb, q, v, zero, nullptr, o, M);
+    rb_pass<double, true, true>(rb, q, v, zero, nullptr, o, M, lrow);
     double fs[NQ];
     for (int i = 0; i < NQ; ++i) {
       M[tri(i, i)] += P.armature[i];

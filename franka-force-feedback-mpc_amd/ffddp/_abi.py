@@ -77,6 +77,7 @@ SYMBOLS = (
     "ffddp_link_model_rows",
     "ffddp_gravity_torque_mdl_dev",
     "ffddp_fleet_pre_mdl_dev",
+    "ffddp_plant_set_instance_links",
 )
 PLANT_OBS = 69
 # FFDDP_PLANT_ROW_*: one instance's physics row (ffddp_plant_set_instance_params)
@@ -563,6 +564,9 @@ def load() -> C.CDLL:
     lib.ffddp_fleet_inject_cmd_rows_dev.restype = C.c_int
     lib.ffddp_plant_set_instance_params.argtypes = [C.c_void_p, C.c_int, dp]
     lib.ffddp_plant_set_instance_params.restype = C.c_int
+    # per-instance link models of the plant: host rows [n][LINK_W] (NULL = the handle's robot)
+    lib.ffddp_plant_set_instance_links.argtypes = [C.c_void_p, C.c_int, dp]
+    lib.ffddp_plant_set_instance_links.restype = C.c_int
     lib.ffddp_fleet_noise_dev.argtypes = [C.c_void_p, C.c_int, vp, C.c_int, vp, vp] + [vp]
     lib.ffddp_fleet_noise_dev.restype = C.c_int
     # per-instance tasks: ffddp_fleet_tasks by value; pre_task takes it in place of node_ref1 / contact_hint

@@ -678,6 +678,24 @@ def sweep_payload_masses(seed, payload_spread) -> np.ndarray:
     return out
 
 
+def sweep_plant_payload_masses(seed, plant_payload_spread) -> np.ndarray:
+    """The sweep's per-instance payload masses (B,) on the plants' arms:
+    instance b's is m_lo + (m_hi - m_lo) u, with u one uniform in [0, 1] from
+    default_rng([seed_b, 8]) -- a generator of its own, so no other draw of
+    the sweep moves (sweep_payload_masses' included)."""
+    lo_, hi_ = check_payload_spread(plant_payload_spread)
+    out = np.zeros(len(seed))
+    for b, s_ in enumerate(seed):
+        u = np.random.default_rng([int(s_), 8]).uniform(0.0, 1.0)
+        out[b] = lo_ + (hi_ - lo_) * u
+    return out
+
+
+def payload_models(masses) -> list:
+    """One robot.LinkModel per mass: the nominal arm with a point payload at the EE offset on link 7."""
+    return [R.LinkModel().with_payload(float(m), R.EE_P) for m in masses]
+
+
 def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilted_15", "actuation_uncertainty"),
               seeds: int = 256, total_time: float = 4.0, rank: int = 0, world: int = 1, device: int = 0,
               q_sigma: float = 0.02, verbose: bool = True, record: Sequence[int] = (),
@@ -691,7 +709,8 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
               force_spread: Optional[Tuple[float, float]] = None, force_ramp: Optional[float] = None,
               weight_spread: Optional[dict] = None,
               limit_spread: Optional[Tuple[float, float]] = None,
-              payload_spread: Optional[Tuple[float, float]] = None) -> dict:
+              payload_spread: Optional[Tuple[float, float]] = None,
+              plant_payload_spread: Optional[Tuple[float, float]] = None, payload_known: bool = False) -> dict:
     """Closed-loop sweep of len(scenarios) * seeds instances; this rank runs
     its contiguous shard.  Returns per-instance summary arrays (this shard).
     record: shard-local instance indices whose controller inputs (the plant
@@ -793,7 +812,22 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     model-mismatch sweep.  payload_spread = (m_lo, m_hi) in kg: instance b's
     payload mass is m_lo + (m_hi - m_lo) u, u uniform in [0, 1] from
     default_rng([seed_b, 7]) (sweep_payload_masses; the other draws do not
-    move).  The summary carries ``payload_mass`` (B,), the drawn masses."""
+    move).  The summary carries ``payload_mass`` (B,), the drawn masses.
+    plant_payload_spread, payload_known: the arm itself carries a payload, and
+    the controller may or may not know it.  plant_payload_spread = (m_lo, m_hi)
+    in kg, checked as payload_spread is (host and device path alike: both step
+    a BatchedPlant): instance b's plant integrates with the nominal arm plus a
+    point payload at the EE offset on link 7
+    (BatchedPlant(link_models=...) / DeviceFleetLoop(plant_link_models=...)),
+    of mass m_lo + (m_hi - m_lo) u, u uniform in [0, 1] from
+    default_rng([seed_b, 8]) (sweep_plant_payload_masses; the other draws do
+    not move).  payload_known = True (needs plant_payload_spread, ValueError
+    otherwise; with device_loop only, NotImplementedError otherwise; not
+    together with payload_spread, ValueError) gives each instance's controller
+    the same model (DeviceFleetLoop(link_models=...)).  A plant step that
+    fails under a payload is a result (``plant_fail``), as under plant_spread.
+    The summary carries ``plant_payload_mass`` (B,), the drawn masses, and
+    ``payload_known``."""
     variant = str(variant).strip().lower()
     if variant not in ("classical", "ff"):
         raise ValueError(f"run_sweep: unknown variant {variant!r}")
@@ -846,6 +880,24 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
         if not device_loop:
             raise NotImplementedError("run_sweep: limit_spread needs device_loop=True "
                                       "(the host fleets solve within the configuration's limits)")
+    if not isinstance(payload_known, (bool, np.bool_)) and payload_known not in (0, 1):
+        raise ValueError(f"run_sweep: payload_known must be a flag, not {payload_known!r}")
+    payload_known = bool(payload_known)
+    if plant_payload_spread is not None:
+        try:
+            plant_payload_spread = check_payload_spread(plant_payload_spread)
+        except ValueError:
+            raise ValueError("run_sweep: plant_payload_spread is (m_lo, m_hi), 0 <= m_lo <= m_hi, "
+                             f"not {plant_payload_spread!r}") from None
+    if payload_known:
+        if plant_payload_spread is None:
+            raise ValueError("run_sweep: payload_known needs plant_payload_spread")
+        if payload_spread is not None:
+            raise ValueError("run_sweep: payload_known gives the controllers the plants' payloads; "
+                             "not together with payload_spread")
+        if not device_loop:
+            raise NotImplementedError("run_sweep: payload_known needs device_loop=True "
+                                      "(the host fleets plan with the nominal model)")
     if payload_spread is not None:
         payload_spread = check_payload_spread(payload_spread)
         if not device_loop:
@@ -896,6 +948,7 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     q0 = np.stack([R.Q_NEUTRAL + np.random.default_rng(int(s)).normal(0.0, q_sigma, 7) for s in seed])
     dt_ctrl = 0.001 * 5  # BatchedPlant.dt
     physics = sweep_plant_physics(seed, plant_spread) if plant_spread is not None else None
+    plant_payload = sweep_plant_payload_masses(seed, plant_payload_spread) if plant_payload_spread else None
     sweep_cfgs = [sweep_uncertainty_config(str(names[b]), int(seed[b]), dt_ctrl, uncertainty_spread) for b in range(B)]
     if device_loop:
         ucfgs = None
@@ -923,14 +976,17 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
         out = _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, (R_site_from_pin_ee, p_off), total_time,
                                 neg_step_rule, device, t_cp, verbose, ucfgs, device_noise, solve_period,
                                 command_filter, tasks, device_summary, keep_logs, physics,
-                                allow_plant_fail=plant_spread is not None or uncertainty_spread is not None,
+                                allow_plant_fail=(plant_spread is not None or uncertainty_spread is not None
+                                                  or plant_payload is not None),
                                 force_profiles=profiles,
                                 weights=sweep_cost_weights(seed, weight_spread) if weight_spread else None,
                                 limit_scale=sweep_limit_scales(seed, limit_spread) if limit_spread else None,
-                                payload_mass=sweep_payload_masses(seed, payload_spread) if payload_spread else None)
+                                payload_mass=sweep_payload_masses(seed, payload_spread) if payload_spread else None,
+                                plant_payload_mass=plant_payload, payload_known=payload_known)
         out.update(names=names, seed=seed, shard=(lo, hi), n_all=n_all)
         return out
-    plant = BatchedPlant(B, timestep=0.001, n_substeps=5, device=device, physics=physics)
+    plant = BatchedPlant(B, timestep=0.001, n_substeps=5, device=device, physics=physics,
+                         link_models=None if plant_payload is None else payload_models(plant_payload))
     plant.q = q0.copy()
     plant.v = np.zeros((B, 7))
     plant.set_tilt(0.0)
@@ -1042,6 +1098,8 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     inject_delay, inject_sigma = _inject_profile(sweep_cfgs, dt_ctrl)
     out.update(plant_rows=plant_rows(physics if physics is not None else [PlantPhysics()] * B),
                inject_delay=inject_delay, inject_sigma=inject_sigma)
+    if plant_payload is not None:
+        out.update(plant_payload_mass=plant_payload, payload_known=False)
     if rec_idx:
         out["record"] = dict(index=np.array(rec_idx), t=rec_t, obs=rec_obs, tau=rec_tau, q0=q0[rec_idx], traj=traj,
                              config=cfg, dt=plant.dt, calibration_obs=obs0)
@@ -1069,7 +1127,8 @@ DEVICE_MEMORY: dict = {}  # the last device-loop sweep's memory figures (tools/s
 def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, total_time, neg_step_rule, device, t_cp,
                       verbose, ucfgs=None, noise=None, solve_period=1, command_filter=False, tasks=None,
                       device_summary=False, keep_logs=True, plant_physics=None, allow_plant_fail=False,
-                      force_profiles=None, weights=None, limit_scale=None, payload_mass=None) -> dict:
+                      force_profiles=None, weights=None, limit_scale=None, payload_mass=None,
+                      plant_payload_mass=None, payload_known=False) -> dict:
     """run_sweep's loop on the device (fleet_loop.DeviceFleetLoop) and the
     host path's summary from the downloaded logs.  tasks: per-instance
     FleetTasks in place of traj; the summary's reference position and its
@@ -1083,7 +1142,10 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
     over the configuration's.  limit_scale: (B,) scales (sweep_limit_scales) of
     the configuration's tau_limits, each instance's own torque limits.
     payload_mass: (B,) masses (sweep_payload_masses) of a point payload at the
-    EE offset in each instance's controller model."""
+    EE offset in each instance's controller model.  plant_payload_mass: (B,)
+    masses (sweep_plant_payload_masses) of the same on each instance's plant;
+    payload_known: its controller plans with that model too (payload_mass is
+    then None)."""
     import torch
 
     from .fleet_loop import DeviceFleetLoop
@@ -1105,8 +1167,10 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
                            cost_weights=None if weights is None else
                            [{name: float(v[b]) for name, v in weights.items()} for b in range(B)],
                            torque_limits=None if limit_scale is None else np.asarray(limit_scale, float),
-                           link_models=None if payload_mass is None else
-                           [R.LinkModel().with_payload(float(m), R.EE_P) for m in payload_mass])
+                           link_models=payload_models(payload_mass) if payload_mass is not None else
+                           payload_models(plant_payload_mass) if payload_known else None,
+                           plant_link_models=None if plant_payload_mass is None else
+                           payload_models(plant_payload_mass))
     wall0 = time.perf_counter()
     loop.run(steps)
     torch.cuda.synchronize(loop.dev)
@@ -1140,6 +1204,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
             out.update(limit_scale=np.asarray(limit_scale, float), tau_limits=loop.tau_limits)
         if payload_mass is not None:
             out.update(payload_mass=np.asarray(payload_mass, float))
+        if plant_payload_mass is not None:
+            out.update(plant_payload_mass=np.asarray(plant_payload_mass, float), payload_known=bool(payload_known))
         if tasks is not None and keep_logs:
             out.update(solved=r["solved"], surface=r["surface"] != 0)
         return out
@@ -1184,6 +1250,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
         out.update(limit_scale=np.asarray(limit_scale, float), tau_limits=loop.tau_limits)
     if payload_mass is not None:
         out.update(payload_mass=np.asarray(payload_mass, float))
+    if plant_payload_mass is not None:
+        out.update(plant_payload_mass=np.asarray(plant_payload_mass, float), payload_known=bool(payload_known))
     if tasks is not None:
         out.update(solved=r["solved"], surface=r["surface"] != 0)  # (ticks, B): the per-tick solve share
     return out

@@ -104,6 +104,15 @@ there is no launch more per tick and ``state`` / ``load_state`` carry nothing
 for them.  The plant is not touched.  Without the argument the loop enqueues
 exactly the calls it did.
 
+With ``plant_link_models`` every instance's plant integrates with its own link
+inertial parameters (ffddp_plant_set_instance_links): one robot.LinkModel per
+instance (None: the nominal one), the arm the instance really has, whatever
+its controller believes (``link_models``).  The rows are handed to the loop's
+BatchedPlant once, before the start sequence; there is no launch more per tick
+and ``state`` / ``load_state`` carry nothing for them.  It combines with
+``plant_physics``, ``link_models`` and every other per-instance option.
+Without the argument the loop enqueues exactly the calls it did.
+
 Not on the device, and so not supported here: ``run_sweep``'s ``record`` and
 any per-tick host callback; ``tick()`` lets a caller look between ticks at the price of its own
 synchronisation.
@@ -282,6 +291,9 @@ class DeviceFleetLoop:
     link_models: None, or one robot.LinkModel (or None, the nominal model) per
     instance, the model its controller plans with; ``link_rows`` (B, LINK_W)
     keeps the rows as uploaded.
+    plant_link_models: None, or one robot.LinkModel (or None, the nominal
+    model) per instance, the link inertial parameters its plant integrates
+    with; ``plant.link_rows`` (B, LINK_W) keeps the rows as set.
 
     ``S``: the controller state, ``T``: the solve's arrays, ``P``: the plant's
     (q, v, obs, tau_app, tau_filt, plane), ``J``: the injector's (row, a, b,
@@ -298,7 +310,7 @@ class DeviceFleetLoop:
                  tasks: Optional[Sequence[FleetTask]] = None, metrics: bool = False, logs: bool = True,
                  t_contact_phase=None, plant_physics=None,
                  force_profiles: Optional[Sequence[Optional[ForceProfile]]] = None, cost_weights=None,
-                 torque_limits=None, link_models=None):
+                 torque_limits=None, link_models=None, plant_link_models=None):
         variant = str(variant).strip().lower()
         if variant not in ("classical", "ff"):
             raise ValueError(f"DeviceFleetLoop: unknown variant {variant!r}")
@@ -309,6 +321,11 @@ class DeviceFleetLoop:
             link_models = list(link_models)
             if len(link_models) != int(B) or not all(m is None or isinstance(m, R.LinkModel) for m in link_models):
                 raise ValueError("DeviceFleetLoop: link_models takes one robot.LinkModel (or None) per instance")
+        if plant_link_models is not None:
+            plant_link_models = list(plant_link_models)
+            if len(plant_link_models) != int(B) or not all(m is None or isinstance(m, R.LinkModel)
+                                                           for m in plant_link_models):
+                raise ValueError("DeviceFleetLoop: plant_link_models takes one robot.LinkModel (or None) per instance")
         metrics, logs = bool(metrics), bool(logs)
         if not logs and not metrics:
             raise ValueError("DeviceFleetLoop: logs=False needs metrics=True (a run without either reports nothing)")
@@ -365,7 +382,7 @@ class DeviceFleetLoop:
                 raise ValueError("DeviceFleetLoop: plant_physics takes one PlantPhysics per instance, or one for all")
             plant_physics = plant_rows(phys)
         self.plant = BatchedPlant(self.B, timestep=timestep, n_substeps=n_substeps, device=device,
-                                  physics=plant_physics)
+                                  physics=plant_physics, link_models=plant_link_models)
         self.plant_rows = plant_rows([PlantPhysics()] * self.B) if plant_physics is None else plant_physics.copy()
         self._has_physics = plant_physics is not None
         self.dt = self.plant.dt

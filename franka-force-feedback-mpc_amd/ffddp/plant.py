@@ -169,6 +169,29 @@ def plant_rows(seq) -> np.ndarray:
     return check_plant_rows(np.stack([p.row() for p in seq]))
 
 
+def plant_link_rows(models) -> np.ndarray:
+    """(n, LINK_W) float64 link-model rows for ffddp_plant_set_instance_links:
+    a sequence of robot.LinkModel | None (None: the nominal model), packed by
+    config.link_model_rows, or an (n, LINK_W) array of such rows.  Refused
+    (ValueError) where the library refuses them: a mass that is not finite and
+    > 0, a com or inertia entry that is not finite; the padding entries
+    (16j + 13..15, 112..127) are not looked at."""
+    from .config import link_model_rows
+
+    if isinstance(models, np.ndarray):
+        rows = np.ascontiguousarray(models, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != _abi.LINK_W or rows.shape[0] < 1:
+            raise ValueError(f"plant link rows: expected (n, {_abi.LINK_W}) with n >= 1, got {rows.shape}")
+        used = rows[:, :112].reshape(-1, 7, 16)[:, :, :13]
+        if not (np.all(np.isfinite(used)) and np.all(used[:, :, 0] > 0.0)):
+            raise ValueError("plant link rows: a mass must be finite and > 0, com and inertia finite")
+        return rows
+    models = list(models)
+    if not models or not all(m is None or isinstance(m, R.LinkModel) for m in models):
+        raise ValueError("plant link rows: a non-empty sequence of robot.LinkModel or None")
+    return link_model_rows(models)
+
+
 def observation_from_record(rec, tau_cmd=None, tilt_deg: float = 0.0) -> Observation:
     """Observation of one FFDDP_PLANT_OBS record (no torque filters: the
     tau_meas* fields hold the unfiltered tau_total)."""
@@ -194,16 +217,22 @@ class BatchedPlant:
     """B plant instances on one device; host-array stepping (one launch per
     control step).  ``obs`` rows follow FFDDP_PLANT_OBS (ffddp_plant.hpp).
     physics: None (every instance integrates with ``params``), or what
-    ``set_physics`` takes."""
+    ``set_physics`` takes.  robot: a robot.LinkModel, the handle's own link
+    inertial parameters (None: the nominal Panda).  link_models: None (every
+    instance integrates with the handle's robot), or what ``set_link_models``
+    takes."""
 
     def __init__(self, B: int, timestep: float = DEFAULT_TIMESTEP, n_substeps: int = 1, device: int = 0,
-                 physics=None):
+                 physics=None, robot=None, link_models=None):
         self.lib = _abi.load()
         self.B = int(B)
         self.params = plant_params(timestep, n_substeps)
+        if robot is not None and not isinstance(robot, R.LinkModel):
+            raise ValueError("BatchedPlant: robot is a robot.LinkModel or None")
+        self.robot = robot
         h = C.c_void_p()
-        rc = self.lib.ffddp_plant_create(C.byref(_abi.robot_struct()), C.byref(self.params), int(device), self.B,
-                                         C.byref(h))
+        rb = _abi.robot_struct() if robot is None else _abi.make_robot(robot)
+        rc = self.lib.ffddp_plant_create(C.byref(rb), C.byref(self.params), int(device), self.B, C.byref(h))
         if rc:
             raise RuntimeError(f"ffddp_plant_create failed ({rc}); a HIP device is required")
         self._h = h
@@ -212,8 +241,11 @@ class BatchedPlant:
         self.plane = np.tile(np.concatenate(table_plane(0.0)), (self.B, 1))
         self.obs = np.zeros((self.B, _abi.PLANT_OBS))
         self.physics = None  # the (B, PLANT_ROW_W) rows in force, or None: the handle's struct
+        self.link_rows = None  # the (B, LINK_W) link-model rows in force, or None: the handle's robot
         if physics is not None:
             self.set_physics(physics)
+        if link_models is not None:
+            self.set_link_models(link_models)
 
     def set_physics(self, rows):
         """Per-instance physics (ffddp_plant_set_instance_params): a sequence
@@ -236,6 +268,29 @@ class BatchedPlant:
         if rc:
             raise RuntimeError(f"ffddp_plant_set_instance_params failed ({rc})")
         self.physics = rows.copy()
+
+    def set_link_models(self, models):
+        """Per-instance link inertial parameters
+        (ffddp_plant_set_instance_links): a sequence of B robot.LinkModel |
+        None (None: the nominal model) or a (B, LINK_W) array of link-model
+        rows (config.link_model_rows), instance b integrating with the masses,
+        centres of mass and inertias of row b from the next step on (``step``
+        and ``step_dev`` alike); None: back to the handle's robot for all.
+        Independent of ``set_physics``.  Invalid input is a ValueError and
+        leaves what was in force."""
+        if models is None:
+            rc = self.lib.ffddp_plant_set_instance_links(self._h, 0, None)
+            if rc:
+                raise RuntimeError(f"ffddp_plant_set_instance_links failed ({rc})")
+            self.link_rows = None
+            return
+        rows = plant_link_rows(models)
+        if rows.shape[0] != self.B:
+            raise ValueError(f"BatchedPlant.set_link_models: {rows.shape[0]} rows for {self.B} instances")
+        rc = self.lib.ffddp_plant_set_instance_links(self._h, self.B, _abi.dptr(rows))
+        if rc:
+            raise RuntimeError(f"ffddp_plant_set_instance_links failed ({rc})")
+        self.link_rows = rows.copy()
 
     @property
     def dt(self) -> float:

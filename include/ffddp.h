@@ -1094,6 +1094,25 @@ int ffddp_plant_step_dev(ffddp_plant* h, int B, double* q, double* v, const doub
 #define FFDDP_PLANT_ROW_SOLIMP 18  /* [5] d0, dmax, width, mid, power */
 int ffddp_plant_set_instance_params(ffddp_plant* h, int n, const double* rows);
 
+/* Per-instance link inertial parameters: one link-model row per instance, the
+ * row format of ffddp_solve_batch_mdl_dev (FFDDP_LINK_W: entry 16j mass[j],
+ * 16j + 1..3 com[j], 16j + 4..12 inertia[j]), as ffddp_link_model_rows writes
+ * them, so one set of rows can serve the controller and the plant.
+ * link_rows: host memory, [n][FFDDP_LINK_W]; the handle keeps its own device
+ * copy (field-major over the 91 used entries).  From the next
+ * ffddp_plant_step / ffddp_plant_step_dev on, with B <= n, instance b
+ * integrates with the masses, centres of mass and inertias of row b; B > n is
+ * FFDDP_E_INVALID.  Kinematics, gravity, timestep, n_substeps and site_R stay
+ * the handle's.  link_rows == NULL (n is ignored): back to the handle's
+ * ffddp_robot for all.  The call waits for the device's work before it
+ * replaces the copy.  Link rows and physics rows
+ * (ffddp_plant_set_instance_params) are set and cleared independently.
+ * FFDDP_E_INVALID with nothing changed for a null handle, n < 1 or n >
+ * max_batch, or any row ffddp_link_model_rows would refuse: a mass that is
+ * not finite and > 0, a com or inertia entry that is not finite.  The padding
+ * entries (16j + 13..15, 112..127) are neither read nor checked. */
+int ffddp_plant_set_instance_links(ffddp_plant* h, int n, const double* link_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -112,6 +112,11 @@ def build_parser():
     ap.add_argument("--payload-spread", type=float, nargs=2, default=None, metavar=("M_LO", "M_HI"),
                     help="with --device-loop 1: per-instance controller models, the nominal arm with a point payload "
                          "of M_LO..M_HI kg (uniform) at the EE offset; the plant is unchanged")
+    ap.add_argument("--plant-payload-spread", type=float, nargs=2, default=None, metavar=("M_LO", "M_HI"),
+                    help="per-instance plants: the arm carries a point payload of M_LO..M_HI kg (uniform) at the EE "
+                         "offset; the controllers plan with the nominal model unless --payload-known 1")
+    ap.add_argument("--payload-known", type=int, choices=(0, 1), default=0,
+                    help="with --plant-payload-spread and --device-loop 1: 1 gives each controller its plant's model")
     ap.add_argument("--scenarios", nargs="+", default=list(ALL_SCENARIOS), help="scenarios to sweep (default: all 5)")
     return ap
 
@@ -146,7 +151,8 @@ def main():
                            device_summary=bool(a.device_summary), keep_logs=bool(a.keep_logs),
                            plant_spread=a.plant_spread, uncertainty_spread=uspread,
                            force_spread=a.force_spread, force_ramp=a.force_ramp, weight_spread=wspread,
-                           limit_spread=a.limit_spread, payload_spread=a.payload_spread)
+                           limit_spread=a.limit_spread, payload_spread=a.payload_spread,
+                           plant_payload_spread=a.plant_payload_spread, payload_known=bool(a.payload_known))
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -223,6 +229,20 @@ def main():
             edges = np.linspace(a.payload_spread[0], a.payload_spread[1], 5)
             which = np.clip(np.digitize(pm, edges) - 1, 0, 3)
             line.update(payload_spread=a.payload_spread, rank0_payload_bins=[
+                {"mass_lo": float(edges[i]), "mass_hi": float(edges[i + 1]), "instances": int(np.sum(which == i)),
+                 "mass_mean": float(np.mean(pm[which == i])),
+                 "fn_mean_contact_phase": float(np.nanmean(pi["fn_mean_contact_phase"][which == i])),
+                 "avg_abs_force_err": float(np.nanmean(pi["avg_abs_force_err"][which == i])),
+                 "rms_tangential_error_contact_phase":
+                     float(np.nanmean(pi["rms_tangential_error_contact_phase"][which == i])),
+                 "contact_loss_contact_phase_pct": float(np.nanmean(pi["contact_loss_contact_phase_pct"][which == i]))}
+                for i in range(4) if np.any(which == i)])
+        if "plant_payload_mass" in res:  # this rank's shard by the plant's payload mass, four linear bins
+            pi, pm = res["per_instance"], res["plant_payload_mass"]
+            edges = np.linspace(a.plant_payload_spread[0], a.plant_payload_spread[1], 5)
+            which = np.clip(np.digitize(pm, edges) - 1, 0, 3)
+            line.update(plant_payload_spread=a.plant_payload_spread, payload_known=int(a.payload_known),
+                        rank0_plant_payload_bins=[
                 {"mass_lo": float(edges[i]), "mass_hi": float(edges[i + 1]), "instances": int(np.sum(which == i)),
                  "mass_mean": float(np.mean(pm[which == i])),
                  "fn_mean_contact_phase": float(np.nanmean(pi["fn_mean_contact_phase"][which == i])),
