@@ -63,6 +63,15 @@ inline void torque_limit_row(const double* tau_limits, double margin, double* ro
 // mass[j], 16j + 1..3 com[j], 16j + 4..12 inertia[j] row-major as the struct
 // holds it, the rest zero padding.  Plain copies, so a row of the handle's
 // robot is the handle's constants by construction.
+// One instance's mount row (ffddp.h FFDDP_MOUNT_W): entries 0..8 base_R =
+// joint_R[0] row-major, 9..11 base_p = joint_p[0], 12..14 gravity, 15 zero
+// padding.  Plain copies likewise.
+inline void mount_row(const ffddp_robot& rb, double* row) {
+  for (int e = 0; e < 9; ++e) row[e] = rb.joint_R[0][e];
+  for (int e = 0; e < 3; ++e) row[9 + e] = rb.joint_p[0][e];
+  for (int e = 0; e < 3; ++e) row[12 + e] = rb.gravity[e];
+  row[15] = 0.0;
+}
 inline void link_model_row(const ffddp_robot& rb, double* row) {
   for (int e = 0; e < FFDDP_LINK_W; ++e) row[e] = 0.0;
   for (int j = 0; j < 7; ++j) {

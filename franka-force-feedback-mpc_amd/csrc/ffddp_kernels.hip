@@ -123,6 +123,8 @@ struct Dev {
                        //          BoxQP bounds; null: C's limits
   const double* md;    // [B][FFDDP_LINK_W] link-model rows (ffddp_solve_batch_mdl_dev), read by the MD
                        //          instantiations of k_node / k_forward_g8 only; null: C.rb's inertial parameters
+  const double* mt;    // [B][FFDDP_MOUNT_W] mount rows (ffddp_solve_batch_mnt_dev): base placement and gravity, read by
+                       //          the MT instantiations of k_node / k_forward_g8 / k_finalize; null: C.rb's
 };
 
 // Active-instance compaction.  Iteration it reads list (it & 1): the
@@ -283,7 +285,9 @@ struct NodeShared {
 // instance's row d.ul[b] (ffddp.h FFDDP_TAU_LIM_W), read where C's were.
 // MD: the links' mass, centre of mass and rotational inertia come from the
 // instance's row d.md[b] (ffddp.h FFDDP_LINK_W), read where C.rb's were.
-template <int NC, bool FF, bool FR, bool CW, bool UL, bool MD>
+// MT: the base placement (joint 0's) and the gravity vector come from the
+// instance's row d.mt[b] (ffddp.h FFDDP_MOUNT_W), read where C.rb's were.
+template <int NC, bool FF, bool FR, bool CW, bool UL, bool MD, bool MT>
 __device__ __forceinline__ void primal_group(const DevConsts& C, const Dev& d, const double* __restrict__ x0,
                                              const double* __restrict__ node_ref, const double* __restrict__ inst_ref,
                                              const uint8_t* __restrict__ surface, int b, int t, Primal* P,
@@ -324,8 +328,10 @@ __device__ __forceinline__ void primal_group(const DevConsts& C, const Dev& d, c
   const double* cw = CW ? d.cw + (long)b * FFDDP_COST_W : nullptr;
   const double* ul = UL ? d.ul + (long)b * FFDDP_TAU_LIM_W : nullptr;
   const double* md = MD ? d.md + (long)b * FFDDP_LINK_W : nullptr;
-  const double pc = node_primal_g8<NC, FR, CW, UL, MD>(C, mode, surf, q, v, u, xreg[ji], xreg[7 + ji], xreg[14 + ji], ref, P,
-                                                       lk, lam, FR ? d.fref + ((long)b * (N + 1) + t) : nullptr, cw, ul, md);
+  const double* mt = MT ? d.mt + (long)b * FFDDP_MOUNT_W : nullptr;
+  const double pc = node_primal_g8<NC, FR, CW, UL, MD, MT>(C, mode, surf, q, v, u, xreg[ji], xreg[7 + ji], xreg[14 + ji], ref, P,
+                                                           lk, lam, FR ? d.fref + ((long)b * (N + 1) + t) : nullptr, cw, ul, md,
+                                                           mt);
   double* rec = d.rec_buf + ((long)b * (N + 1) + t) * d.rec;
   // node cost (IAM scaling, FF augmentation terms): per-lane shares summed over the group
   double c = FF ? C.dt * pc : (terminal ? pc : C.dt * pc);
@@ -415,7 +421,11 @@ __device__ __forceinline__ double fquad(const double* a, const double* Dd, const
 // MD: the calc's link inertial parameters are those of the instance's row
 // d.md[b] (a solve with link_rows), read where C.rb's were; the tangents read
 // only what the calc wrote.  MD = false is the kernel as it was.
-template <int NC, bool FF, bool FR = false, bool CW = false, bool UL = false, bool MD = false>
+// MT: the calc's base placement and gravity vector are those of the instance's
+// row d.mt[b] (a solve with mount_rows), read where C.rb's were; the state
+// tangent's one read of the gravity vector takes the row's too.  MT = false is
+// the kernel as it was.
+template <int NC, bool FF, bool FR = false, bool CW = false, bool UL = false, bool MD = false, bool MT = false>
 __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE_WAVES))) void k_node(const DevConsts* __restrict__ Cg, Dev d,
                                                       const double* __restrict__ x0,
                                                       const double* __restrict__ node_ref,
@@ -454,7 +464,7 @@ __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE
   const double* ref = node_ref + ((long)b * (N + 1) + t) * 6;
   NodeGroupShared& G = S.g[grp];
   Primal& P = G.P;
-  if (active && lane < G8) primal_group<NC, FF, FR, CW, UL, MD>(C, d, x0, node_ref, inst_ref, surface, b, t, &P, G.lk, xsrc, usrc);
+  if (active && lane < G8) primal_group<NC, FF, FR, CW, UL, MD, MT>(C, d, x0, node_ref, inst_ref, surface, b, t, &P, G.lk, xsrc, usrc);
   __syncthreads();
   const bool need_u = mode != MODE_TERMINAL_X;
   // control directions first, their results stored at once (neither touches
@@ -468,7 +478,12 @@ __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE
     for (int r = 0; r < nc; ++r) G.colu[lane][r] = (surf ? dlamu[r] : 0.0);
   }
   double da[NQ], dlam[3], col[NDENSE_MAX], r1[NQ], dh[3];
-  if (active && lane < 14) node_tangent_state_links<NC>(C, mode, surf, G.lk, P, lane, r1, dh, col);
+  if constexpr (MT) {
+    if (active && lane < 14)
+      node_tangent_state_links<NC, true>(C, mode, surf, G.lk, P, lane, r1, dh, col, d.mt + (long)b * FFDDP_MOUNT_W + 12);
+  } else {
+    if (active && lane < 14) node_tangent_state_links<NC>(C, mode, surf, G.lk, P, lane, r1, dh, col);
+  }
   __syncthreads();  // every lane's reads of lk are done before col overwrites it
   // the column's rows 0..11 go to LDS before the contact solves (which read
   // only P), so they are not live across them: no scratch spill at 2 waves/SIMD
@@ -2060,7 +2075,12 @@ __device__ __forceinline__ int ls_row_bcast0(int v) {  // lane 0 of the row into
 // and L in place of LaneK's for the same reason (the kernel runs one wave per
 // SIMD, so the registers are there: DESIGN.md §21).  The EE lane and the ROW
 // layout's phantom lanes hold zeros, as LaneK gives them.
-template <int NC, bool FF, bool ROW, bool FR = false, bool CW = false, bool UL = false, bool MD = false>
+// MT: the base placement and the gravity vector are those of the instance's
+// row d.mt[b], held in registers next to M for the same reason (LsT: lane 0 of
+// the real and of the phantom group takes base_R / base_p, finite in both, the
+// other lanes copy LaneK's placement once; every lane takes the gravity).
+template <int NC, bool FF, bool ROW, bool FR = false, bool CW = false, bool UL = false, bool MD = false,
+          bool MT = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW_WPE))) void k_forward_g8(const DevConsts* __restrict__ Cg, Dev d,
                                                    const double* __restrict__ x0,
                                                    const double* __restrict__ node_ref,
@@ -2167,6 +2187,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
 #pragma unroll
     for (int k = 0; k < 9; ++k) M.I[k] = lnk ? mdr[4 + k] : 0.0;
   }
+  LsT Tm;
+  if constexpr (MT) {
+    const double* mtr = d.mt + (long)b * FFDDP_MOUNT_W;
+    const bool base = li == 0;  // the real group's joint 0 and (ROW) the phantom group's
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Tm.R[k] = base ? mtr[k] : K.R[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Tm.p[k] = base ? mtr[9 + k] : K.p[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Tm.g[k] = mtr[12 + k];
+  }
   // FF augmentation weights (joint lanes) at their use: a term the handle does not build keeps C's zero
   auto w_y = [&]() { return (CW && C.w_y > 0.0) ? W.w[FFDDP_CW_Y - FFDDP_CW_JOINT0] : C.w_y; };
   auto w_w = [&]() { return (CW && C.w_w > 0.0) ? W.w[FFDDP_CW_W - FFDDP_CW_JOINT0] : C.w_w; };
@@ -2235,7 +2266,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
       double qn, vn, cp, lam[3];
       const double uin = FF ? xt_t : u;
       PP(8);
-      ls_node_calc<NC, ROW, FR, CW, UL, MD>(C, fl, K, W, L, M, MODE_RUNNING, surf, xq_t, xv_t, uin, xq, xv, tref, ref, fnr, qn, vn, cp, lam
+      ls_node_calc<NC, ROW, FR, CW, UL, MD, MT>(C, fl, K, W, L, M, Tm, MODE_RUNNING, surf, xq_t, xv_t, uin, xq, xv, tref, ref, fnr, qn, vn, cp, lam
 #ifdef FFDDP_PHASE_PROF
                             , pp_acc, pp_last
 #endif
@@ -2268,7 +2299,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ROW ? 1 : FW
       double qn, vn, cp, lam[3];
       const int mode = FF ? MODE_TERMINAL_U : MODE_TERMINAL_X;
       PP(8);
-      ls_node_calc<NC, ROW, FR, CW, UL, MD>(C, fl, K, W, L, M, mode, surf, xq_t, xv_t, FF ? xt_t : 0.0, xq, xv, tref, ref, fnr, qn, vn, cp, lam
+      ls_node_calc<NC, ROW, FR, CW, UL, MD, MT>(C, fl, K, W, L, M, Tm, mode, surf, xq_t, xv_t, FF ? xt_t : 0.0, xq, xv, tref, ref, fnr, qn, vn, cp, lam
 #ifdef FFDDP_PHASE_PROF
                             , pp_acc, pp_last
 #endif
@@ -2450,7 +2481,9 @@ __global__ __launch_bounds__(64) void k_commit(const DevConsts* __restrict__ Cg,
 // solution read-back helpers: iter/ok, contact force at knots 0 and 1
 // MD: the predicted contact force is computed under the instance's own link model, its row d.md[b] (a solve with
 // link_rows), which rb_pass reads in place of C.rb's inertial parameters; MD = false is the kernel as it was.
-template <int NC, bool FF, bool MD = false>
+// MT: and under its own base placement and gravity, its row d.mt[b] (a solve with mount_rows), which rb_pass reads
+// likewise; instantiated with MD only.
+template <int NC, bool FF, bool MD = false, bool MT = false>
 __global__ __launch_bounds__(64) void k_finalize(const DevConsts* __restrict__ Cg, Dev d, int maxiter, const double* __restrict__ x0,
                            const double* __restrict__ node_ref, const double* __restrict__ inst_ref,
                            const uint8_t* __restrict__ surface, double* cost, int32_t* iters, uint8_t* ok,
@@ -2492,7 +2525,10 @@ __global__ __launch_bounds__(64) void k_finalize(const DevConsts* __restrict__ C
   const double* xreg = inst_ref + (long)b * 21;
   Primal P;
   double yn[21], c;
-  if constexpr (MD) {
+  if constexpr (MT) {
+    node_calc<NC, FF, true>(C, false, true, y, u, ref, xreg, xreg + 14, x0 + (long)b * nx, P, yn, c, nullptr,
+                      d.md + (long)b * FFDDP_LINK_W, d.mt + (long)b * FFDDP_MOUNT_W);
+  } else if constexpr (MD) {
     node_calc<NC, FF>(C, false, true, y, u, ref, xreg, xreg + 14, x0 + (long)b * nx, P, yn, c, nullptr,
                       d.md + (long)b * FFDDP_LINK_W);
   } else {
@@ -2601,6 +2637,67 @@ __global__ __launch_bounds__(64) void k_gravity_mdl(const ffddp_robot* __restric
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   gravity_torque(*rb, q + (long)b * NQ, tau + (long)b * NQ, link + (long)b * FFDDP_LINK_W);
+}
+
+// ffddp_gravity_torque_mnt_dev: k_gravity with each instance's own mount row and, unless null, link-model row
+__global__ __launch_bounds__(64) void k_gravity_mnt(const ffddp_robot* __restrict__ rb, int B, const double* __restrict__ q,
+                                                    const double* __restrict__ link, const double* __restrict__ mount,
+                                                    double* __restrict__ tau) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  gravity_torque<true>(*rb, q + (long)b * NQ, tau + (long)b * NQ, link ? link + (long)b * FFDDP_LINK_W : nullptr,
+                       mount + (long)b * FFDDP_MOUNT_W);
+}
+
+// ffddp_fleet_obs_frame_dev: one lane per instance re-expresses its plant record (ffddp_plant.hpp PO_*) in the
+// instance's planning frame (R, p in the MuJoCo world, frame row [FFDDP_FRAME_W]: R row-major, then p).  All PO_WORDS
+// words are copied; positions become R^T (x - p), free vectors R^T x, the EE rotation and the site Jacobian R^T X
+// column by column.  Each entry is (R[0][i] x0 + R[1][i] x1) + R[2][i] x2, evaluated left to right without
+// contraction, so a restatement in numpy gives the same bits.  sel[b] == 0: the record is copied verbatim.
+__global__ __launch_bounds__(64) void k_fleet_obs_frame(int B, const double* __restrict__ obs, long ld_obs,
+                                                        const double* __restrict__ frame,
+                                                        const uint8_t* __restrict__ sel, double* __restrict__ out,
+                                                        long ld_out) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const double* in = obs + (long)b * ld_obs;
+  double* o = out + (long)b * ld_out;
+  if (sel && !sel[b]) {
+    for (int i = 0; i < PO_WORDS; ++i) o[i] = in[i];
+    return;
+  }
+  double R[9], p[3];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R[k] = frame[(long)b * FFDDP_FRAME_W + k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) p[k] = frame[(long)b * FFDDP_FRAME_W + 9 + k];
+  auto rt = [&](double x0, double x1, double x2, int i) { return (R[i] * x0 + R[3 + i] * x1) + R[6 + i] * x2; };
+  for (int i = 0; i < PO_EE_P; ++i) o[i] = in[i];
+  {
+    const double d0 = in[PO_EE_P] - p[0], d1 = in[PO_EE_P + 1] - p[1], d2 = in[PO_EE_P + 2] - p[2];
+    const double v0 = in[PO_EE_V], v1 = in[PO_EE_V + 1], v2 = in[PO_EE_V + 2];
+    const double f0 = in[PO_FW], f1 = in[PO_FW + 1], f2 = in[PO_FW + 2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      o[PO_EE_P + i] = rt(d0, d1, d2, i);
+      o[PO_EE_V + i] = rt(v0, v1, v2, i);
+      o[PO_FW + i] = rt(f0, f1, f2, i);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const double x0 = in[PO_EE_R + j], x1 = in[PO_EE_R + 3 + j], x2 = in[PO_EE_R + 6 + j];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[PO_EE_R + 3 * i + j] = rt(x0, x1, x2, i);
+  }
+  o[PO_FN] = in[PO_FN];
+  o[PO_NCON] = in[PO_NCON];
+  for (int j = 0; j < NQ; ++j) {
+    const double x0 = in[PO_J + j], x1 = in[PO_J + NQ + j], x2 = in[PO_J + 2 * NQ + j];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[PO_J + NQ * i + j] = rt(x0, x1, x2, i);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -2798,6 +2895,8 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_keep(
 //
 // link (ffddp_fleet_pre_mdl_dev): the gravity torque reference is computed with
 // the instance's own mass / com / inertia, its link-model row; null: *rb's.
+// mount (ffddp_fleet_pre_mnt_dev): and under the instance's own base placement
+// and gravity, its mount row; null: *rb's.
 template <bool SCHED, bool TASK>
 __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_pre(
     const ffddp_robot* __restrict__ rb, int N, int nx, ffddp_fleet_params P, ffddp_fleet_state S, ffddp_fleet_sched Q,
@@ -2806,7 +2905,7 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_pre(
     const double* __restrict__ tau_hat, long ld_th, const double* __restrict__ q_nom, const double* __restrict__ node1, int hint1,
     double* __restrict__ x0, uint8_t* __restrict__ surface, double* __restrict__ inst_ref,
     double* __restrict__ node_ref, double* __restrict__ xs_init, double* __restrict__ us_init, ffddp_fleet_tasks T,
-    double dt_ocp, const double* __restrict__ link) {
+    double dt_ocp, const double* __restrict__ link, const double* __restrict__ mount) {
   const long b = blockIdx.x;
   const int tid = threadIdx.x;
   const bool ff = nx == 21;
@@ -2857,7 +2956,9 @@ __global__ __launch_bounds__(FLEET_BLOCK) void k_fleet_pre(
   } else if (tid == 64) {  // wave 1, so wave 0's lanes go on with the copies
     double qq[NQ], g[NQ];
     for (int i = 0; i < NQ; ++i) qq[i] = P.torque_mode == 1 ? qn[i] : qb[i];
-    if (link) {
+    if (mount) {
+      gravity_torque<true>(*rb, qq, g, link ? link + b * FFDDP_LINK_W : nullptr, mount + b * FFDDP_MOUNT_W);
+    } else if (link) {
       gravity_torque(*rb, qq, g, link + b * FFDDP_LINK_W);
     } else {
       gravity_torque(*rb, qq, g);
@@ -3143,6 +3244,9 @@ struct ffddp_handle {
   // [max_batch][FFDDP_TAU_LIM_W] rows of the configuration's limits: the torque limits of a solve with link
   // rows and no tau_lim of its own (first such solve)
   double* ul_const = nullptr;
+  // [max_batch][FFDDP_LINK_W] rows of the handle's robot: the link model of a solve with mount rows and no
+  // link_rows of its own (first such solve)
+  double* md_const = nullptr;
   // sub-batch streams: the batch is split into nstreams slices solved on their
   // own HIP streams, so latency-bound phases of one slice overlap with the
   // throughput-bound phases of another (FFDDP_STREAMS, default 4: three
@@ -3227,6 +3331,7 @@ void free_all(ffddp_handle* h) {
   if (h->fref_const) (void)hipFree(h->fref_const);
   if (h->cw_const) (void)hipFree(h->cw_const);
   if (h->ul_const) (void)hipFree(h->ul_const);
+  if (h->md_const) (void)hipFree(h->md_const);
   if (h->stage) (void)hipHostFree(h->stage);
 }
 
@@ -3281,6 +3386,7 @@ Dev dev_slice(const Dev& d0, int b0, int Bk, int k) {
   if (d.cw) d.cw += (long)b0 * FFDDP_COST_W;
   if (d.ul) d.ul += (long)b0 * FFDDP_TAU_LIM_W;
   if (d.md) d.md += (long)b0 * FFDDP_LINK_W;
+  if (d.mt) d.mt += (long)b0 * FFDDP_MOUNT_W;
   return d;
 }
 
@@ -3298,10 +3404,10 @@ struct SolveArgs {
   double* fn_pred;
   int32_t* stats;
   const uint8_t* active;
-  const double *fref, *cw, *ul, *md;
+  const double *fref, *cw, *ul, *md, *mt;
 };
 
-template <int NC, bool FF, bool FR, bool CW, bool UL, bool MD>
+template <int NC, bool FF, bool FR, bool CW, bool UL, bool MD, bool MT>
 int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* io) {
   const int B = a.B, maxiter = a.maxiter;
   const int N = h->hc.N, nx = h->hc.nx;
@@ -3340,6 +3446,7 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
   dbase.cw = CW ? a.cw : nullptr;
   dbase.ul = UL ? a.ul : nullptr;
   dbase.md = MD ? a.md : nullptr;
+  dbase.mt = MT ? a.mt : nullptr;
   if (!io) {
     dbase.xs = a.xs;
     dbase.us = a.us;
@@ -3403,7 +3510,7 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
     if (it == 0 && stagger == 2 && k + 1 < S) HIPCHK(h, hipEventRecord(h->stg[k], ss));
     {
       ProfScope p(h, ss, KC_NODE);
-      hipLaunchKernelGGL((k_node<NC, FF, FR, CW, UL, MD>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, ss,
+      hipLaunchKernelGGL((k_node<NC, FF, FR, CW, UL, MD, MT>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, ss,
                          h->dc, d, x0k, nrefk, irefk, surfk, 0, it & 1);
     }
     if (it == 0 && stagger == 1 && k + 1 < S) HIPCHK(h, hipEventRecord(h->stg[k], ss));
@@ -3474,13 +3581,13 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
         const long groups = more ? (long)Bk * ntr : g1;
         if (!row_only) {
           const dim3 grid((unsigned)((groups * G8 + 63) / 64));
-          hipLaunchKernelGGL((k_forward_g8<NC, FF, false, FR, CW, UL, MD>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
+          hipLaunchKernelGGL((k_forward_g8<NC, FF, false, FR, CW, UL, MD, MT>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
                              surfk, tr0, ntr, more, it & 1, wide, row_max);
         }
         if (row_max > 0) {
           const long rg = std::min(groups, (long)row_max);  // the row layout runs only when they fit
           const dim3 grid((unsigned)((rg * 16 + 63) / 64));
-          hipLaunchKernelGGL((k_forward_g8<NC, FF, true, FR, CW, UL, MD>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
+          hipLaunchKernelGGL((k_forward_g8<NC, FF, true, FR, CW, UL, MD, MT>), grid, dim3(64), 0, ss, h->dc, d, x0k, nrefk, irefk,
                              surfk, tr0, ntr, more, it & 1, wide, row_max);
         }
       };
@@ -3516,7 +3623,7 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
     }
     {
       ProfScope p(h, ss, KC_FINALIZE);
-      hipLaunchKernelGGL((k_finalize<NC, FF, MD>), dim3((2 * Bk + 63) / 64), dim3(64), 0, ss, h->dc, d, maxiter,
+      hipLaunchKernelGGL((k_finalize<NC, FF, MD, MT>), dim3((2 * Bk + 63) / 64), dim3(64), 0, ss, h->dc, d, maxiter,
                          a.x0 + b0 * nxl, a.nref + b0 * N1 * 6, a.iref + b0 * 21, a.surf + b0, a.cost + b0, a.iters + b0,
                          a.ok + b0, a.fn_pred ? a.fn_pred + 2 * b0 : nullptr,
                          a.stats ? a.stats + b0 * FFDDP_NSTATS : nullptr, a.active ? a.active + b0 : nullptr);
@@ -3579,35 +3686,39 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
 // The CW kernels exist with FR only (the caller supplies a force reference of fn_des where the user gave none: the
 // same bits), so the build does not double.  ul: there are torque-limit rows; the UL kernels exist with FR and CW
 // only (the caller supplies rows of the configuration's weights likewise).  md: there are link-model rows; the MD
-// kernels exist with FR, CW and UL only (the caller supplies rows of the configuration's limits likewise).
-template <class F> int dispatch_variant(ffddp_handle* h, bool fr, bool cw, bool ul, bool md, F&& f) {
+// kernels exist with FR, CW and UL only (the caller supplies rows of the configuration's limits likewise).  mt: there
+// are mount rows; the MT kernels exist with FR, CW, UL and MD only (the caller supplies rows of the handle's robot
+// likewise).
+template <class F> int dispatch_variant(ffddp_handle* h, bool fr, bool cw, bool ul, bool md, bool mt, F&& f) {
   if (cw && !fr) return fail(h, FFDDP_E_INVALID, "cost weights without a force reference");
   if (ul && !cw) return fail(h, FFDDP_E_INVALID, "torque limits without cost weights");
   if (md && !ul) return fail(h, FFDDP_E_INVALID, "link model without torque limits");
+  if (mt && !md) return fail(h, FFDDP_E_INVALID, "mount without a link model");
   using NC1 = std::integral_constant<int, 1>;
   using NC3 = std::integral_constant<int, 3>;
   const bool ff = h->hc.variant == FFDDP_FORCE_FEEDBACK;
-  auto nc_ff = [&](auto FR, auto CW, auto UL, auto MD) -> int {
+  auto nc_ff = [&](auto FR, auto CW, auto UL, auto MD, auto MT) -> int {
     if (h->hc.nc == 1)
-      return ff ? f(NC1{}, std::true_type{}, FR, CW, UL, MD) : f(NC1{}, std::false_type{}, FR, CW, UL, MD);
-    return ff ? f(NC3{}, std::true_type{}, FR, CW, UL, MD) : f(NC3{}, std::false_type{}, FR, CW, UL, MD);
+      return ff ? f(NC1{}, std::true_type{}, FR, CW, UL, MD, MT) : f(NC1{}, std::false_type{}, FR, CW, UL, MD, MT);
+    return ff ? f(NC3{}, std::true_type{}, FR, CW, UL, MD, MT) : f(NC3{}, std::false_type{}, FR, CW, UL, MD, MT);
   };
   const std::true_type T{};
   const std::false_type F_{};
-  if (md) return nc_ff(T, T, T, T);
-  if (ul) return nc_ff(T, T, T, F_);
-  if (cw) return nc_ff(T, T, F_, F_);
-  if (fr) return nc_ff(T, F_, F_, F_);
-  return nc_ff(F_, F_, F_, F_);
+  if (mt) return nc_ff(T, T, T, T, T);
+  if (md) return nc_ff(T, T, T, T, F_);
+  if (ul) return nc_ff(T, T, T, F_, F_);
+  if (cw) return nc_ff(T, T, F_, F_, F_);
+  if (fr) return nc_ff(T, F_, F_, F_, F_);
+  return nc_ff(F_, F_, F_, F_, F_);
 }
 
 // io: the host entry point's copies (nullptr: the device entry points and the plan capture)
 int launch_solve(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* io) {
-  return dispatch_variant(h, a.fref != nullptr, a.cw != nullptr, a.ul != nullptr, a.md != nullptr,
-                          [&](auto NC, auto FF, auto FR, auto CW, auto UL, auto MD) {
+  return dispatch_variant(h, a.fref != nullptr, a.cw != nullptr, a.ul != nullptr, a.md != nullptr, a.mt != nullptr,
+                          [&](auto NC, auto FF, auto FR, auto CW, auto UL, auto MD, auto MT) {
                             return launch_solve_t<decltype(NC)::value, decltype(FF)::value, decltype(FR)::value,
-                                                  decltype(CW)::value, decltype(UL)::value, decltype(MD)::value>(h, a, s,
-                                                                                                                  io);
+                                                  decltype(CW)::value, decltype(UL)::value, decltype(MD)::value,
+                                                  decltype(MT)::value>(h, a, s, io);
                           });
 }
 
@@ -3951,6 +4062,33 @@ int ffddp_link_model_rows(const ffddp_robot* robots, int B, double* rows) {
   return 0;
 }
 
+// the handle's constant link-model rows (the handle's robot in every row, link_model_row's plain copies), made on
+// first use: the MT kernels are instantiated with MD only, and rows of the handle's robot reproduce its bits
+static int const_link_rows(ffddp_handle* h) {
+  if (h->md_const) return 0;
+  double row[FFDDP_LINK_W];
+  link_model_row(h->hc.rb, row);
+  const size_t n = (size_t)h->max_batch * FFDDP_LINK_W;
+  std::vector<double> v(n);
+  for (size_t i = 0; i < n; ++i) v[i] = row[i % FFDDP_LINK_W];
+  if (int rc = dalloc(h, &h->md_const, n)) return rc;
+  HIPCHK(h, hipMemcpy(h->md_const, v.data(), n * 8, hipMemcpyHostToDevice));
+  return 0;
+}
+
+int ffddp_mount_rows(const ffddp_robot* robots, int B, double* rows) {
+  if (B < 0 || (B > 0 && (!robots || !rows))) return FFDDP_E_INVALID;
+  for (long b = 0; b < B; ++b) {
+    const ffddp_robot& r = robots[b];
+    for (int e = 0; e < 9; ++e)
+      if (!std::isfinite(r.joint_R[0][e])) return FFDDP_E_INVALID;
+    for (int e = 0; e < 3; ++e)
+      if (!std::isfinite(r.joint_p[0][e]) || !std::isfinite(r.gravity[e])) return FFDDP_E_INVALID;
+  }
+  for (long b = 0; b < B; ++b) mount_row(robots[b], rows + b * FFDDP_MOUNT_W);
+  return 0;
+}
+
 int ffddp_solve_batch_wts_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
                               const double* inst_ref, const uint8_t* surface, const double* xs_init,
                               const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
@@ -3977,15 +4115,30 @@ int ffddp_solve_batch_mdl_dev(ffddp_handle* h, int B, const double* x0, const do
                               double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
                               const uint8_t* active, const double* force_ref, const double* cost_w,
                               const double* tau_lim, const double* link_rows, void* stream) {
+  return ffddp_solve_batch_mnt_dev(h, B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs,
+                                   us, K, cost, iters, ok, fn_pred, stats, active, force_ref, cost_w, tau_lim, link_rows,
+                                   nullptr, stream);
+}
+
+int ffddp_solve_batch_mnt_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                              const double* inst_ref, const uint8_t* surface, const double* xs_init,
+                              const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
+                              double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
+                              const uint8_t* active, const double* force_ref, const double* cost_w,
+                              const double* tau_lim, const double* link_rows, const double* mount_rows, void* stream) {
   SolveArgs a{B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs, us, K, cost, iters, ok,
-              fn_pred, stats, active, force_ref, cost_w, tau_lim, link_rows};
+              fn_pred, stats, active, force_ref, cost_w, tau_lim, link_rows, mount_rows};
   if (int rc = solve_args_check(h, a)) return rc;
   if (B == 0) return 0;
   HIPCHK(h, hipSetDevice(h->device));
   // the handle's workspace is shared by every solve: a solve enqueued on
   // another (possibly non-blocking) stream must finish before this one starts
   if (h->last_done_set) HIPCHK(h, hipStreamWaitEvent((hipStream_t)stream, h->last_done, 0));
-  if (link_rows && !tau_lim) {
+  if (mount_rows && !link_rows) {
+    if (int rc = const_link_rows(h)) return rc;
+    a.md = h->md_const;
+  }
+  if (a.md && !tau_lim) {
     if (int rc = const_limit_rows(h)) return rc;
     a.ul = h->ul_const;
   }
@@ -4041,9 +4194,9 @@ int ffddp_solve_batch(ffddp_handle* h, int B, const double* x0, const double* no
                       const uint8_t* surface, const double* xs_init, const double* us_init, int maxiter,
                       int is_feasible, double* xs, double* us, double* K, double* cost, int32_t* iters, uint8_t* ok,
                       double* fn_pred, int32_t* stats) {
-  // the caller's host arrays; no active mask, force reference, cost weights, torque limits or link model on this path
+  // the caller's host arrays; no active mask, force reference, cost weights, torque limits, link model or mount on this path
   const SolveArgs user{B, x0, node_ref, inst_ref, surface, xs_init, us_init, maxiter, is_feasible, xs, us, K, cost,
-                       iters, ok, fn_pred, stats, nullptr, nullptr, nullptr, nullptr, nullptr};
+                       iters, ok, fn_pred, stats, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (int rc = solve_args_check(h, user)) return rc;
   if (B == 0) return 0;
   HIPCHK(h, hipSetDevice(h->device));
@@ -4134,7 +4287,7 @@ int ffddp_solve_batch(ffddp_handle* h, int B, const double* x0, const double* no
   // the solve itself works on the handle's device buffers; xs / us / K: where launch_solve_t copies them down to
   const SolveArgs a{B, h->in_x0, h->in_nref, h->in_iref, h->in_surf, h->in_xs, h->in_us, maxiter, is_feasible,
                     (double*)hout[0], (double*)hout[1], (double*)hout[2], h->out_cost, h->out_iters, h->out_ok,
-                    h->out_fn, h->out_stats, nullptr, nullptr, nullptr, nullptr, nullptr};
+                    h->out_fn, h->out_stats, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (int rc = launch_solve(h, a, cs, &io)) return drain_host_solve(h, rc);
   const double t2 = tm ? now() : 0.0;
   // while the device solves: the first touch of the caller's pageable output
@@ -4294,7 +4447,7 @@ int ffddp_plan_create(ffddp_handle* h, int B, int maxiter, int is_feasible, ffdd
                     (const uint8_t*)(di + L.surf), (const double*)(di + L.xs_init), (const double*)(di + L.us_init),
                     maxiter, is_feasible, (double*)(dq + L.xs), (double*)(dq + L.us), (double*)(dq + L.K),
                     (double*)(dq + L.cost), (int32_t*)(dq + L.iters), (uint8_t*)(dq + L.ok), (double*)(dq + L.fn),
-                    (int32_t*)(dq + L.stats), nullptr, nullptr, nullptr, nullptr, nullptr};
+                    (int32_t*)(dq + L.stats), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int rc = 0;
   hipError_t e = hipStreamBeginCapture(p->s, hipStreamCaptureModeThreadLocal);
   if (e == hipSuccess) {
@@ -4503,6 +4656,15 @@ int ffddp_calc_diff_mdl(ffddp_handle* h, int B, const double* x0, const double* 
                         const double* cost_w, const double* tau_lim, const double* link_rows, double* Fx, double* Fu,
                         double* Lx, double* Lu, double* Lxx, double* Lxu, double* Luu, double* cost, double* xnext,
                         double* lam) {
+  return ffddp_calc_diff_mnt(h, B, x0, node_ref, inst_ref, surface, xs, us, force_ref, cost_w, tau_lim, link_rows, nullptr,
+                             Fx, Fu, Lx, Lu, Lxx, Lxu, Luu, cost, xnext, lam);
+}
+
+int ffddp_calc_diff_mnt(ffddp_handle* h, int B, const double* x0, const double* node_ref, const double* inst_ref,
+                        const uint8_t* surface, const double* xs, const double* us, const double* force_ref,
+                        const double* cost_w, const double* tau_lim, const double* link_rows, const double* mount_rows,
+                        double* Fx, double* Fu, double* Lx, double* Lu, double* Lxx, double* Lxu, double* Luu,
+                        double* cost, double* xnext, double* lam) {
   if (!h) return FFDDP_E_INVALID;
   if (B < 1 || B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "bad B");
   if (force_ref && !(h->hc.w_fn > 0.0))
@@ -4514,8 +4676,9 @@ int ffddp_calc_diff_mdl(ffddp_handle* h, int B, const double* x0, const double* 
     ~Tmp() {
       if (p) (void)hipFree(p);
     }
-  } fref, cw, ul, md;
-  const bool with_ul = tau_lim || link_rows;
+  } fref, cw, ul, md, mt;
+  const bool with_md = link_rows || mount_rows;
+  const bool with_ul = tau_lim || with_md;
   const bool with_cw = cost_w || with_ul;
   if (force_ref) {
     HIPCHK(h, hipMalloc((void**)&fref.p, (size_t)B * (h->hc.N + 1) * 8));
@@ -4528,8 +4691,14 @@ int ffddp_calc_diff_mdl(ffddp_handle* h, int B, const double* x0, const double* 
   if (tau_lim) {
     HIPCHK(h, hipMalloc((void**)&ul.p, (size_t)B * FFDDP_TAU_LIM_W * 8));
     HIPCHK(h, hipMemcpy(ul.p, tau_lim, (size_t)B * FFDDP_TAU_LIM_W * 8, hipMemcpyHostToDevice));
-  } else if (link_rows) {
+  } else if (with_md) {
     if (int rc = const_limit_rows(h)) return rc;
+  }
+  if (mount_rows) {
+    if (!link_rows)
+      if (int rc = const_link_rows(h)) return rc;
+    HIPCHK(h, hipMalloc((void**)&mt.p, (size_t)B * FFDDP_MOUNT_W * 8));
+    HIPCHK(h, hipMemcpy(mt.p, mount_rows, (size_t)B * FFDDP_MOUNT_W * 8, hipMemcpyHostToDevice));
   }
   if (link_rows) {
     HIPCHK(h, hipMalloc((void**)&md.p, (size_t)B * FFDDP_LINK_W * 8));
@@ -4545,8 +4714,9 @@ int ffddp_calc_diff_mdl(ffddp_handle* h, int B, const double* x0, const double* 
   d.B = B;
   d.fref = fref.p ? fref.p : (with_cw ? h->fref_const : nullptr);
   d.cw = cw.p ? cw.p : (with_ul ? h->cw_const : nullptr);
-  d.ul = ul.p ? ul.p : (link_rows ? h->ul_const : nullptr);
-  d.md = md.p;
+  d.ul = ul.p ? ul.p : (with_md ? h->ul_const : nullptr);
+  d.md = md.p ? md.p : (mount_rows ? h->md_const : nullptr);
+  d.mt = mt.p;
   HIPCHK(h, hipMemcpy(h->in_x0, x0, (size_t)B * nx * 8, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->in_nref, node_ref, (size_t)B * (N + 1) * 6 * 8, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->in_iref, inst_ref, (size_t)B * 21 * 8, hipMemcpyHostToDevice));
@@ -4555,11 +4725,11 @@ int ffddp_calc_diff_mdl(ffddp_handle* h, int B, const double* x0, const double* 
   HIPCHK(h, hipMemcpy(h->in_us, us, (size_t)B * N * NU * 8, hipMemcpyHostToDevice));
   // node kernel reads (xs, us) from the solver state: initialise it from the inputs
   hipLaunchKernelGGL(k_init<false>, dim3(1024), dim3(INIT_BLOCK), 0, nullptr, h->dc, d, h->in_xs, h->in_us, 0, nullptr);
-  const int rc = dispatch_variant(h, d.fref != nullptr, d.cw != nullptr, d.ul != nullptr, d.md != nullptr,
-                                  [&](auto NC, auto FF, auto FR, auto CW, auto UL, auto MD) {
+  const int rc = dispatch_variant(h, d.fref != nullptr, d.cw != nullptr, d.ul != nullptr, d.md != nullptr, d.mt != nullptr,
+                                  [&](auto NC, auto FF, auto FR, auto CW, auto UL, auto MD, auto MT) {
     const long nodes = (long)B * (N + 1);
     hipLaunchKernelGGL((k_node<decltype(NC)::value, decltype(FF)::value, decltype(FR)::value, decltype(CW)::value,
-                               decltype(UL)::value, decltype(MD)::value>),
+                               decltype(UL)::value, decltype(MD)::value, decltype(MT)::value>),
                        dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, nullptr, h->dc, d, h->in_x0,
                        h->in_nref, h->in_iref, h->in_surf, 1, 0);
     return 0;
@@ -4650,6 +4820,19 @@ int ffddp_gravity_torque_mdl_dev(ffddp_handle* h, int B, const double* q, const 
   return 0;
 }
 
+int ffddp_gravity_torque_mnt_dev(ffddp_handle* h, int B, const double* q, const double* link_rows,
+                                 const double* mount_rows, double* tau, void* stream) {
+  if (!h || B < 0) return FFDDP_E_INVALID;
+  if (B > 0 && (!q || !tau)) return fail(h, FFDDP_E_INVALID, "ffddp_gravity_torque_mnt_dev: null pointer");
+  if (!mount_rows) return ffddp_gravity_torque_mdl_dev(h, B, q, link_rows, tau, stream);
+  if (B == 0) return 0;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_gravity_mnt, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->drb, B, q, link_rows,
+                     mount_rows, tau);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 int ffddp_build_problem_dev(ffddp_handle* h, int B, const ffddp_task* task, const double* t0, const double* x0,
                             double* node_ref, double* inst_ref, uint8_t* surface, void* stream) {
   if (!h || !task || B < 0) return FFDDP_E_INVALID;
@@ -4730,14 +4913,15 @@ static int fleet_sched_check(ffddp_handle* h, const ffddp_fleet_sched& c, const 
 
 // The body of ffddp_fleet_pre_dev, _pre_sched_dev, _pre_task_dev and _pre_mdl_dev; `name`: the entry point called,
 // for the messages.  sched: the scheduled tick (the SCHED instantiations).  tasks: per-instance tasks (the TASK
-// instantiations) in place of node_ref1 / contact_hint.  link: per-instance link-model rows or null.
+// instantiations) in place of node_ref1 / contact_hint.  link: per-instance link-model rows or null.  mount:
+// per-instance mount rows or null.
 static int fleet_pre(ffddp_handle* h, const char* name, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
                      const double* q, const double* v, const double* fn_meas, const double* contact,
                      const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
                      const double* q_nom, const double* node_ref1, int contact_hint, double* x0, uint8_t* surface,
                      double* inst_ref, double* node_ref, double* xs_init, double* us_init,
                      const ffddp_fleet_sched* sched, const ffddp_fleet_tasks* tasks, const double* link,
-                     void* stream) {
+                     const double* mount, void* stream) {
   if (!h) return FFDDP_E_INVALID;
   const std::string who(name);
   if (B <= 0) return fail(h, FFDDP_E_INVALID, who + ": B must be positive");
@@ -4757,7 +4941,7 @@ static int fleet_pre(ffddp_handle* h, const char* name, int B, const ffddp_fleet
   hipLaunchKernelGGL(kern, dim3(B), dim3(FLEET_BLOCK), 0, (hipStream_t)stream, h->drb, h->hc.N, h->hc.nx, *p, *s,
                      sched ? *sched : ffddp_fleet_sched{}, q, v, fn_meas, contact, ee_z, (long)ld_qv, (long)ld_scalar,
                      tau_hat, (long)ld_tau_hat, q_nom, node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init,
-                     us_init, tasks ? *tasks : ffddp_fleet_tasks{}, tasks ? h->hc.dt : 0.0, link);
+                     us_init, tasks ? *tasks : ffddp_fleet_tasks{}, tasks ? h->hc.dt : 0.0, link, mount);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -4770,7 +4954,7 @@ int ffddp_fleet_pre_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, con
                         double* node_ref, double* xs_init, double* us_init, void* stream) {
   return fleet_pre(h, "ffddp_fleet_pre_dev", B, p, s, q, v, fn_meas, contact, ee_z, ld_qv, ld_scalar, tau_hat, ld_tau_hat,
                    q_nom, node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init, nullptr, nullptr,
-                   nullptr, stream);
+                   nullptr, nullptr, stream);
 }
 
 int ffddp_fleet_pre_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
@@ -4781,7 +4965,7 @@ int ffddp_fleet_pre_sched_dev(ffddp_handle* h, int B, const ffddp_fleet_params* 
                               ffddp_fleet_sched sched, void* stream) {
   return fleet_pre(h, "ffddp_fleet_pre_sched_dev", B, p, s, q, v, fn_meas, contact, ee_z, ld_qv, ld_scalar, tau_hat,
                    ld_tau_hat, q_nom, node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init, &sched,
-                   nullptr, nullptr, stream);
+                   nullptr, nullptr, nullptr, stream);
 }
 
 // The body of ffddp_fleet_post_dev, _post_sched_dev and _post_lim_dev (sched: the scheduled tick, the SCHED
@@ -4887,7 +5071,7 @@ int ffddp_fleet_pre_task_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p
                              const ffddp_fleet_sched* sched, void* stream) {
   return fleet_pre(h, "ffddp_fleet_pre_task_dev", B, p, s, q, v, fn_meas, contact, ee_z, ld_qv, ld_scalar, tau_hat,
                    ld_tau_hat, q_nom, nullptr, 0, x0, surface, inst_ref, node_ref, xs_init, us_init, sched, &tasks, nullptr,
-                   stream);
+                   nullptr, stream);
 }
 
 int ffddp_fleet_pre_mdl_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
@@ -4898,7 +5082,34 @@ int ffddp_fleet_pre_mdl_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p,
                             double* us_init, const ffddp_fleet_sched* sched, const double* link_rows, void* stream) {
   return fleet_pre(h, "ffddp_fleet_pre_mdl_dev", B, p, s, q, v, fn_meas, contact, ee_z, ld_qv, ld_scalar, tau_hat,
                    ld_tau_hat, q_nom, node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init, sched,
-                   tasks.rec ? &tasks : nullptr, link_rows, stream);
+                   tasks.rec ? &tasks : nullptr, link_rows, nullptr, stream);
+}
+
+int ffddp_fleet_pre_mnt_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                            const double* q, const double* v, const double* fn_meas, const double* contact,
+                            const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
+                            const double* q_nom, ffddp_fleet_tasks tasks, const double* node_ref1, int contact_hint,
+                            double* x0, uint8_t* surface, double* inst_ref, double* node_ref, double* xs_init,
+                            double* us_init, const ffddp_fleet_sched* sched, const double* link_rows,
+                            const double* mount_rows, void* stream) {
+  return fleet_pre(h, "ffddp_fleet_pre_mnt_dev", B, p, s, q, v, fn_meas, contact, ee_z, ld_qv, ld_scalar, tau_hat,
+                   ld_tau_hat, q_nom, node_ref1, contact_hint, x0, surface, inst_ref, node_ref, xs_init, us_init, sched,
+                   tasks.rec ? &tasks : nullptr, link_rows, mount_rows, stream);
+}
+
+// a plant record per instance re-expressed in the instance's planning frame (k_fleet_obs_frame)
+int ffddp_fleet_obs_frame_dev(ffddp_handle* h, int B, const double* obs, int ld_obs, const double* frame,
+                              const uint8_t* sel, double* obs_out, int ld_out, void* stream) {
+  if (!h) return FFDDP_E_INVALID;
+  if (B <= 0) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_obs_frame_dev: B must be positive");
+  if (B > h->max_batch) return fail(h, FFDDP_E_CAPACITY, "B exceeds max_batch");
+  if (!obs || !frame || !obs_out) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_obs_frame_dev: null pointer");
+  if (ld_obs < PO_WORDS || ld_out < PO_WORDS) return fail(h, FFDDP_E_INVALID, "ffddp_fleet_obs_frame_dev: bad stride");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(k_fleet_obs_frame, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, obs, (long)ld_obs,
+                     frame, sel, obs_out, (long)ld_out);
+  HIPCHK(h, hipGetLastError());
+  return 0;
 }
 
 // the sweep's task metrics (ffddp_metrics.hpp): one record per instance folded into acc [W][ld]

@@ -256,14 +256,17 @@ template <int NC> FFD_HD void force_world(const double* lam, double* fw) {
 
 // x: inner state (14), u: inner control (7, ignored for MODE_TERMINAL_X),
 // ref: p_ref(3), v_ref(3) for this node, xreg (14), tau_ref (7).
-template <int NC>
+template <int NC, bool MOUNT = false>
 FFD_HD void node_primal(const DevConsts& C, int mode, bool surface, const double* x, const double* u,
                         const double* ref, const double* xreg, const double* tauref, Primal& P,
-                        Primal* gout = nullptr, const double* fnr = nullptr, const double* lrow = nullptr) {
+                        Primal* gout = nullptr, const double* fnr = nullptr, const double* lrow = nullptr,
+                        const double* mrow = nullptr) {
   // fnr: this node's normal-force reference (the solve's force_ref entry) in
   // place of C.fn_ref[NC - 1]; null: C's
   // lrow: the instance's link-model row in place of C.rb's inertial parameters
   // (k_finalize's MD instantiations); null: C.rb's
+  // MOUNT: mrow, the instance's mount row, in place of C.rb's base placement
+  // and gravity (k_finalize's MT instantiations); otherwise not read
   // gout: each block of fields is stored as soon as it is final, so the
   // registers holding it can be reused (a whole-struct copy at the end would
   // keep all ~225 words live to the last instruction).
@@ -276,9 +279,9 @@ FFD_HD void node_primal(const DevConsts& C, int mode, bool surface, const double
   RBOut<double> K;
   double M[28];
   if (with_dyn) {
-    rb_pass<double, true, true>(C.rb, q, v, zero, nullptr, K, M, lrow);
+    rb_pass<double, true, true, MOUNT>(C.rb, q, v, zero, nullptr, K, M, lrow, mrow);
   } else {
-    rb_pass<double, false, false>(C.rb, q, v, zero, nullptr, K, nullptr, lrow);
+    rb_pass<double, false, false, MOUNT>(C.rb, q, v, zero, nullptr, K, nullptr, lrow, mrow);
   }
   #pragma unroll
   for (int i = 0; i < NQ; ++i) {
@@ -665,9 +668,11 @@ FFD_HD void sp_imul(double m, const double* h, const double* IO, const double* x
 //   node_tangent_state_links    link-record part: the column (force rows 0),
 //                               d tau (r1) and dh; reads LK and P
 //   node_tangent_state_contact  contact solves: da, dlam, force rows; reads P only
-template <int NC>
+// MOUNT: grav, the instance's gravity vector (its mount row's entries 12..14,
+// k_node's MT instantiations), in place of C.rb.gravity; otherwise not read
+template <int NC, bool MOUNT = false>
 FFD_HD void node_tangent_state_links(const DevConsts& C, int mode, bool surface, const double* LK, const Primal& P,
-                                     int dir, double* r1, double* dh, double* col) {
+                                     int dir, double* r1, double* dh, double* col, const double* grav = nullptr) {
   constexpr int nc = NC;
   const bool with_dyn = mode != MODE_TERMINAL_X;
   const bool isq = dir < NQ;
@@ -683,7 +688,7 @@ FFD_HD void node_tangent_state_links(const DevConsts& C, int mode, bool surface,
     oj[k] = Lj[LK_O + k];
     Vpv[k] = pz * Lp[LK_VO + k];
     Vpw[k] = pz * Lp[LK_W + k];
-    Apv[k] = pz * Lp[LK_AO + k] - C.rb.gravity[k];  // A_{j-1} - G
+    Apv[k] = pz * Lp[LK_AO + k] - (MOUNT ? grav[k] : C.rb.gravity[k]);  // A_{j-1} - G
     Apw[k] = pz * Lp[LK_AL + k];
   }
   const double* E = LK + LK_EE;
@@ -954,12 +959,13 @@ FFD_HD void node_tangent_control(const DevConsts& C, bool surface, const Primal&
 
 // Full node calc for the forward pass (variant-aware): y (nx), w (7) ->
 // ynext (nx), cost.  Terminal: w ignored.  Returns lambda in P.lam.
-template <int NC, bool FF>
+template <int NC, bool FF, bool MOUNT = false>
 FFD_HD void node_calc(const DevConsts& C, bool terminal, bool surface, const double* y, const double* w,
                       const double* ref, const double* xreg, const double* tauref, const double* yref, Primal& P,
-                      double* ynext, double& cost, const double* fnr = nullptr, const double* lrow = nullptr) {
+                      double* ynext, double& cost, const double* fnr = nullptr, const double* lrow = nullptr,
+                      const double* mrow = nullptr) {
   if (!FF) {
-    node_primal<NC>(C, terminal ? MODE_TERMINAL_X : MODE_RUNNING, surface, y, w, ref, xreg, tauref, P, nullptr, fnr, lrow);
+    node_primal<NC, MOUNT>(C, terminal ? MODE_TERMINAL_X : MODE_RUNNING, surface, y, w, ref, xreg, tauref, P, nullptr, fnr, lrow, mrow);
     for (int i = 0; i < 14; ++i) ynext[i] = P.xnext[i];
     cost = terminal ? P.cost : C.dt * P.cost;
     return;
@@ -967,7 +973,7 @@ FFD_HD void node_calc(const DevConsts& C, bool terminal, bool surface, const dou
   const double* tau = y + 14;
   double wz[7] = {0, 0, 0, 0, 0, 0, 0};
   const double* ww = terminal ? wz : w;
-  node_primal<NC>(C, terminal ? MODE_TERMINAL_U : MODE_RUNNING, surface, y, tau, ref, xreg, tauref, P, nullptr, fnr, lrow);
+  node_primal<NC, MOUNT>(C, terminal ? MODE_TERMINAL_U : MODE_RUNNING, surface, y, tau, ref, xreg, tauref, P, nullptr, fnr, lrow, mrow);
   for (int i = 0; i < 14; ++i) ynext[i] = P.xnext[i];
   for (int i = 0; i < 7; ++i) ynext[14 + i] = C.alpha * tau[i] + C.beta * ww[i];
   double c = C.dt * P.cost;

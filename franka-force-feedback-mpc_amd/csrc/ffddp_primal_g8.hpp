@@ -84,14 +84,19 @@ __device__ __forceinline__ double friction_cone_w(const DevConsts& C, const doub
 // values of its block mdr[16 j ..] of the instance's link-model row (ffddp.h
 // FFDDP_LINK_W) instead of C.rb's, read where the link inertia is formed, for
 // the same reason; the expressions are the same.
-template <int NC, bool FR = false, bool CW = false, bool UL = false, bool MD = false>
+// MT: joint lane 0's placement is base_R / base_p of the instance's mount row
+// mtr (ffddp.h FFDDP_MOUNT_W: 0 base_R, 9 base_p, 12 gravity) instead of
+// C.rb.joint_R[0] / joint_p[0], and every lane's gravity vector is the row's
+// instead of C.rb.gravity, each read at its use, for the same reason.
+template <int NC, bool FR = false, bool CW = false, bool UL = false, bool MD = false, bool MT = false>
 __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, bool surface, double q, double v, double u,
                                                  double xq, double xv, double tr, const double* ref,
                                                  Primal* __restrict__ gp, double* __restrict__ lk, double (&lam)[3],
                                                  const double* __restrict__ fnp = nullptr,
                                                  const double* __restrict__ cwr = nullptr,
                                                  const double* __restrict__ ulr = nullptr,
-                                                 const double* __restrict__ mdr = nullptr) {
+                                                 const double* __restrict__ mdr = nullptr,
+                                                 const double* __restrict__ mtr = nullptr) {
   const ffddp_robot& rb = C.rb;
   const int li = g8_lane();
   const bool J = li < NQ;
@@ -105,7 +110,7 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
   if (J) {
     double s, c;
     sincos_(q, s, c);
-    const double* Jr = rb.joint_R[ji];
+    const double* Jr = (MT && ji == 0) ? mtr : rb.joint_R[ji];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
       R[3 * r + 0] = c * Jr[3 * r + 0] + s * Jr[3 * r + 1];
@@ -113,7 +118,7 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
       R[3 * r + 2] = Jr[3 * r + 2];
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) o[k] = rb.joint_p[ji][k];
+    for (int k = 0; k < 3; ++k) o[k] = (MT && ji == 0) ? mtr[9 + k] : rb.joint_p[ji][k];
   } else {
 #pragma unroll
     for (int k = 0; k < 9; ++k) R[k] = rb.ee_R[k];
@@ -275,7 +280,8 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
     // ---- RNEA at qdd = 0 (bias torques) and CRBA tuples: suffix sums ----
     double fl[3], fa[3];
     {
-      const double g0[3] = {rb.gravity[0], rb.gravity[1], rb.gravity[2]};
+      const double* gv = MT ? mtr + 12 : rb.gravity;
+      const double g0[3] = {gv[0], gv[1], gv[2]};
       double ag[3], t1[3], f1[3], n1[3], Ial[3], c1[3], c2[3], c3[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) ag[k] = aO[k] - g0[k];
@@ -479,7 +485,8 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
     }
     if (J) {
       double* L = lk + li * LK_STRIDE;
-      const double g0[3] = {rb.gravity[0], rb.gravity[1], rb.gravity[2]};
+      const double* gv = MT ? mtr + 12 : rb.gravity;
+      const double g0[3] = {gv[0], gv[1], gv[2]};
       double ag[3], t1[3], f1[3], n1[3], Ial[3], c1[3], c2[3], c3[3], f[3], n[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) ag[k] = aOa[k] - g0[k];

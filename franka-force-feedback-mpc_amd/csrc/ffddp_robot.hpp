@@ -32,10 +32,13 @@ template <class T> struct RBOut {
 // contact force on the robot at the EE origin (or nullptr);  M: 28 packed
 // lower-triangular entries (only when WITH_M).  lrow: an instance's link-model
 // row (ffddp.h FFDDP_LINK_W: 16 i mass, 16 i + 1 com, 16 i + 4 inertia), read in
-// place of rb.mass / com / inertia; null: rb's.
-template <class T, bool WITH_TAU, bool WITH_M>
+// place of rb.mass / com / inertia; null: rb's.  mrow: an instance's mount row
+// (ffddp.h FFDDP_MOUNT_W: 0 base_R, 9 base_p, 12 gravity), read in place of
+// rb.joint_R[0] / joint_p[0] / gravity when MOUNT (a compile-time choice, so
+// that without it the code is what it was); otherwise not read.
+template <class T, bool WITH_TAU, bool WITH_M, bool MOUNT = false>
 FFD_HD void rb_pass(const ffddp_robot& rb, const T* q, const T* v, const double* a, const double* lam_w,
-                    RBOut<T>& out, double* M, const double* lrow = nullptr) {
+                    RBOut<T>& out, double* M, const double* lrow = nullptr, const double* mrow = nullptr) {
   M3<T> Rprev = m3eye<T>();
   V3<T> oprev = v3zero<T>();
   V3<T> vO = v3zero<T>(), w = v3zero<T>(), aO = v3zero<T>(), al = v3zero<T>();
@@ -45,11 +48,11 @@ FFD_HD void rb_pass(const ffddp_robot& rb, const T* q, const T* v, const double*
   V3<T> Sv_[FFDDP_NQ];
   // composite-inertia tuples (m, h = m c, I_O) for CRBA (double only)
   double cm[FFDDP_NQ], ch[FFDDP_NQ][3], cI[FFDDP_NQ][6];
-  const V3<T> g = v3c<T>(rb.gravity);
+  const V3<T> g = v3c<T>(MOUNT ? mrow + 12 : rb.gravity);
 #pragma unroll
   for (int i = 0; i < FFDDP_NQ; ++i) {
-    const V3<T> o = oprev + mulc_v(Rprev, rb.joint_p[i]);
-    const M3<T> Rp = mulc(Rprev, rb.joint_R[i]);
+    const V3<T> o = oprev + mulc_v(Rprev, (MOUNT && i == 0) ? mrow + 9 : rb.joint_p[i]);
+    const M3<T> Rp = mulc(Rprev, (MOUNT && i == 0) ? mrow : rb.joint_R[i]);
     T s, c;
     sincos_(q[i], s, c);
     M3<T> R;
@@ -271,10 +274,13 @@ FFD_HD void rb_links(const ffddp_robot& rb, const double* q, const double* v, co
 
 // gravity torque rnea(q, 0, 0) (crocoddyl_classical.py:447-451)
 // lrow: the instance's link-model row in place of rb's inertial parameters; null: rb's
-FFD_HD void gravity_torque(const ffddp_robot& rb, const double* q, double* tau, const double* lrow = nullptr) {
+// MOUNT: mrow, the instance's mount row, in place of rb's base placement and gravity
+template <bool MOUNT = false>
+FFD_HD void gravity_torque(const ffddp_robot& rb, const double* q, double* tau, const double* lrow = nullptr,
+                           const double* mrow = nullptr) {
   double zero[FFDDP_NQ] = {0, 0, 0, 0, 0, 0, 0};
   RBOut<double> o;
-  rb_pass<double, true, false>(rb, q, zero, zero, nullptr, o, nullptr, lrow);
+  rb_pass<double, true, false, MOUNT>(rb, q, zero, zero, nullptr, o, nullptr, lrow, mrow);
   for (int i = 0; i < FFDDP_NQ; ++i) tau[i] = o.tau[i];
 }
 

@@ -176,6 +176,15 @@ struct LsL {
 struct LsM {
   double m, com[3], I[9];
 };
+// A lane's share of its instance's mount row (ffddp.h FFDDP_MOUNT_W), loaded
+// once before the node loop for the same reason.  R / p: the lane's joint
+// placement, which is base_R / base_p on joint lane 0 (and, ROW, on the
+// phantom group's lane 0, which needs finite kinematics) and LaneK's own R / p
+// on every other lane, so the node calc reads one source without a select.
+// g: the gravity vector in place of C.rb.gravity, on every lane.
+struct LsT {
+  double R[9], p[3], g[3];
+};
 
 // friction-cone cost (ffddp_node.hpp friction_cone, value only); CW: the weight is W's entry
 template <bool CW>
@@ -275,8 +284,11 @@ template <bool ROW> __device__ __forceinline__ double ls_bwd(const double (&Lt)[
 // torque-limit row) instead of K's; L is unused otherwise.
 // MD: the link's mass, centre of mass and rotational inertia are M's (the
 // instance's link-model row) instead of K's; M is unused otherwise.
-template <int NC, bool ROW, bool FR = false, bool CW = false, bool UL = false, bool MD = false>
-__device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, const LaneK& K, const LsW& W, const LsL& L, const LsM& M, int mode, bool surface, double q,
+// MT: the lane's joint placement and the gravity vector are T's (lane 0's and
+// the gravity from the instance's mount row) instead of K's and C.rb's; T is
+// unused otherwise.
+template <int NC, bool ROW, bool FR = false, bool CW = false, bool UL = false, bool MD = false, bool MT = false>
+__device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, const LaneK& K, const LsW& W, const LsL& L, const LsM& M, const LsT& T, int mode, bool surface, double q,
                                              double v, double u, double xq, double xv, double tr, const double* ref,
                                              double fnr, double& qn, double& vn, double& cpart, double (&lam)[3]
 #ifdef FFDDP_PHASE_PROF
@@ -294,7 +306,7 @@ __device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, co
   if (J) {
     double s, c;
     ls_sincos(q, s, c);
-    const double* Jr = K.R;
+    const double* Jr = MT ? T.R : K.R;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
       R[3 * r + 0] = fma(s, Jr[3 * r + 1], c * Jr[3 * r + 0]);
@@ -303,10 +315,10 @@ __device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, co
     }
   } else {
 #pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = K.R[k];
+    for (int k = 0; k < 9; ++k) R[k] = MT ? T.R[k] : K.R[k];
   }
 #pragma unroll
-  for (int k = 0; k < 3; ++k) o[k] = K.p[k];
+  for (int k = 0; k < 3; ++k) o[k] = MT ? T.p[k] : K.p[k];
 #pragma unroll
   for (int d = 1; d < G8; d <<= 1) {
     double Rp[9], op[3];
@@ -484,7 +496,7 @@ __device__ __forceinline__ void ls_node_calc(const DevConsts& C, unsigned fl, co
       for (int k = 0; k < 3; ++k) ha[k] = t1[k] + Iww[k];
       ls_cross(cw, al, t1);
 #pragma unroll
-      for (int k = 0; k < 3; ++k) f1[k] = m * ((aO[k] - C.rb.gravity[k]) - t1[k]);
+      for (int k = 0; k < 3; ++k) f1[k] = m * ((aO[k] - (MT ? T.g[k] : C.rb.gravity[k])) - t1[k]);
       ls_cross(cw, f1, t1);
 #pragma unroll
       for (int k = 0; k < 3; ++k) n1[k] = t1[k] + Ial[k];

@@ -78,6 +78,12 @@ SYMBOLS = (
     "ffddp_gravity_torque_mdl_dev",
     "ffddp_fleet_pre_mdl_dev",
     "ffddp_plant_set_instance_links",
+    "ffddp_solve_batch_mnt_dev",
+    "ffddp_calc_diff_mnt",
+    "ffddp_mount_rows",
+    "ffddp_gravity_torque_mnt_dev",
+    "ffddp_fleet_pre_mnt_dev",
+    "ffddp_fleet_obs_frame_dev",
 )
 PLANT_OBS = 69
 # FFDDP_PLANT_ROW_*: one instance's physics row (ffddp_plant_set_instance_params)
@@ -191,6 +197,12 @@ TAU_LIM_W = 32
 # FFDDP_LINK_W: one instance's link-model row (ffddp_solve_batch_mdl_dev), joint-major: entry 16j mass[j],
 # 16j + 1..3 com[j], 16j + 4..12 inertia[j] row-major, the rest padding (config.link_model_rows builds rows)
 LINK_W = 128
+
+# FFDDP_MOUNT_W: one instance's mount row (ffddp_solve_batch_mnt_dev): entries 0..8 base_R row-major, 9..11 base_p,
+# 12..14 gravity, 15 padding (config.mount_rows builds rows)
+MOUNT_W = 16
+# FFDDP_FRAME_W: one instance's planning frame in the MuJoCo world (ffddp_fleet_obs_frame_dev): R row-major, then p
+FRAME_W = 12
 
 FLEET_FORCE_W = 4  # FFDDP_FLEET_FORCE_W: doubles per force record, f0, f1, t_on, t_ramp (trajectory.force_records)
 
@@ -412,18 +424,24 @@ def _fill(arr, values):
         buf[i] = float(v)
 
 
-def make_robot(model=None) -> Robot:
+def make_robot(model=None, mount=None) -> Robot:
     """The Panda's ffddp_robot; model (robot.LinkModel): its inertial
-    parameters in place of the nominal ones, the kinematics unchanged."""
+    parameters in place of the nominal ones, the kinematics unchanged; mount
+    (robot.Mount): its base placement (joint 1's) and gravity vector in place
+    of the nominal ones, everything else unchanged."""
     rb = Robot()
-    _fill(rb.joint_R, R.JOINT_R)
-    _fill(rb.joint_p, R.JOINT_P)
+    joint_R, joint_p = R.JOINT_R, R.JOINT_P
+    if mount is not None:
+        joint_R, joint_p = joint_R.copy(), joint_p.copy()
+        joint_R[0], joint_p[0] = mount.base_R, mount.base_p
+    _fill(rb.joint_R, joint_R)
+    _fill(rb.joint_p, joint_p)
     _fill(rb.mass, R.MASS if model is None else model.mass)
     _fill(rb.com, R.COM if model is None else model.com)
     _fill(rb.inertia, R.INERTIA if model is None else model.inertia)
     _fill(rb.ee_R, R.EE_R)
     _fill(rb.ee_p, R.EE_P)
-    _fill(rb.gravity, R.GRAVITY)
+    _fill(rb.gravity, R.GRAVITY if mount is None else mount.gravity)
     return rb
 
 
@@ -490,6 +508,13 @@ def load() -> C.CDLL:
     lib.ffddp_calc_diff_mdl.restype = C.c_int
     lib.ffddp_link_model_rows.argtypes = [C.POINTER(Robot), C.c_int, dp]
     lib.ffddp_link_model_rows.restype = C.c_int
+    # ..., stats, active, force_ref, cost_w, tau_lim, link_rows, mount_rows, stream
+    lib.ffddp_solve_batch_mnt_dev.argtypes = dev_args[:-1] + [vp, vp, vp, vp, vp, vp, vp]
+    lib.ffddp_solve_batch_mnt_dev.restype = C.c_int
+    lib.ffddp_calc_diff_mnt.argtypes = [C.c_void_p, C.c_int, dp, dp, dp, up, dp, dp, dp, dp, dp, dp, dp] + [dp] * 10
+    lib.ffddp_calc_diff_mnt.restype = C.c_int
+    lib.ffddp_mount_rows.argtypes = [C.POINTER(Robot), C.c_int, dp]
+    lib.ffddp_mount_rows.restype = C.c_int
     lib.ffddp_frame_placement.argtypes = [C.POINTER(Robot), dp, dp, dp]
     lib.ffddp_frame_placement.restype = C.c_int
     lib.ffddp_gravity_torque.argtypes = [C.POINTER(Robot), C.c_int, dp, dp]
@@ -498,6 +523,8 @@ def load() -> C.CDLL:
     lib.ffddp_gravity_torque_dev.restype = C.c_int
     lib.ffddp_gravity_torque_mdl_dev.argtypes = [C.c_void_p, C.c_int, vp, vp, vp, vp]
     lib.ffddp_gravity_torque_mdl_dev.restype = C.c_int
+    lib.ffddp_gravity_torque_mnt_dev.argtypes = [C.c_void_p, C.c_int, vp, vp, vp, vp, vp]
+    lib.ffddp_gravity_torque_mnt_dev.restype = C.c_int
     lib.ffddp_build_problem_dev.argtypes = [C.c_void_p, C.c_int, C.POINTER(Task)] + [vp] * 6
     lib.ffddp_build_problem_dev.restype = C.c_int
     lib.ffddp_profile_enable.argtypes = [C.c_void_p, C.c_int]
@@ -581,6 +608,13 @@ def load() -> C.CDLL:
     lib.ffddp_fleet_pre_mdl_dev.argtypes = (fl + [vp] * 5 + [C.c_int, C.c_int, vp, C.c_int, vp, FleetTasks, vp, C.c_int]
                                             + [vp] * 6 + [C.POINTER(FleetSched), vp, vp])
     lib.ffddp_fleet_pre_mdl_dev.restype = C.c_int
+    # ..., link_rows, mount_rows, stream
+    lib.ffddp_fleet_pre_mnt_dev.argtypes = (fl + [vp] * 5 + [C.c_int, C.c_int, vp, C.c_int, vp, FleetTasks, vp, C.c_int]
+                                            + [vp] * 6 + [C.POINTER(FleetSched), vp, vp, vp])
+    lib.ffddp_fleet_pre_mnt_dev.restype = C.c_int
+    # B, obs, ld_obs, frame, sel, obs_out, ld_out, stream
+    lib.ffddp_fleet_obs_frame_dev.argtypes = [C.c_void_p, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp]
+    lib.ffddp_fleet_obs_frame_dev.restype = C.c_int
     # the task metrics: B, ld, obs, ld_obs, tasks, rows, dt, p_ref, ts, t_phase, fn_des, info, need, plant_fail, acc
     lib.ffddp_fleet_metrics_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, vp, C.c_int, FleetTasks, C.c_int, C.c_double,
                                             vp, C.c_double, vp, C.c_double, vp, vp, vp, vp] + [vp]
@@ -649,13 +683,14 @@ def robot_struct() -> Robot:
     return _ROBOT
 
 
-def frame_placement(q) -> tuple[np.ndarray, np.ndarray]:
-    """EE placement (R, p) on the host via the library's model code."""
+def frame_placement(q, robot: Robot = None) -> tuple[np.ndarray, np.ndarray]:
+    """EE placement (R, p) on the host via the library's model code; robot:
+    another ffddp_robot (make_robot(mount=...)) than the nominal one."""
     lib = load()
     q = np.ascontiguousarray(q, dtype=np.float64).reshape(7)
     Rm = np.zeros(9)
     p = np.zeros(3)
-    rc = lib.ffddp_frame_placement(C.byref(robot_struct()), dptr(q), dptr(Rm), dptr(p))
+    rc = lib.ffddp_frame_placement(C.byref(robot_struct() if robot is None else robot), dptr(q), dptr(Rm), dptr(p))
     if rc:
         raise RuntimeError(f"ffddp_frame_placement failed ({rc})")
     return Rm.reshape(3, 3), p

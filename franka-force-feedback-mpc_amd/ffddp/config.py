@@ -192,6 +192,26 @@ def link_model_rows(models) -> np.ndarray:
     return rows
 
 
+def mount_rows(mounts) -> np.ndarray:
+    """(B, _abi.MOUNT_W) float64: the mount rows of a solve's ``mount``
+    (ffddp_solve_batch_mnt_dev) for B robot.Mount objects (None: the nominal
+    mount), packed by the library's own code (ffddp_mount_rows).  A row of the
+    handle's mount repeats the handle's constants.  A non-finite entry raises
+    ValueError (robot.Mount itself checks that base_R is a rotation)."""
+    from . import robot as R
+
+    mounts = [R.Mount() if m is None else m for m in mounts]
+    B = len(mounts)
+    robots = (_abi.Robot * max(B, 1))()
+    for b, m in enumerate(mounts):
+        robots[b] = _abi.make_robot(mount=m)
+    rows = np.zeros((B, _abi.MOUNT_W))
+    rc = _abi.load().ffddp_mount_rows(robots, B, _abi.dptr(rows))
+    if rc:
+        raise ValueError(f"mount_rows: base_R, base_p and gravity must be finite (ffddp_mount_rows failed, {rc})")
+    return rows
+
+
 def classical_preset(horizon: int = 30, contact_model: str = "normal_1d") -> OcpConfig:
     """run_classical.py:269-315 (benchmark mode).  The reference preset uses N=36; BASELINE uses 30 (R9)."""
     return OcpConfig(variant="classical", horizon=horizon, contact_model=contact_model)

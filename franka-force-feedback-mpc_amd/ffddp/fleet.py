@@ -710,7 +710,8 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
               weight_spread: Optional[dict] = None,
               limit_spread: Optional[Tuple[float, float]] = None,
               payload_spread: Optional[Tuple[float, float]] = None,
-              plant_payload_spread: Optional[Tuple[float, float]] = None, payload_known: bool = False) -> dict:
+              plant_payload_spread: Optional[Tuple[float, float]] = None, payload_known: bool = False,
+              tilt_known: bool = False) -> dict:
     """Closed-loop sweep of len(scenarios) * seeds instances; this rank runs
     its contiguous shard.  Returns per-instance summary arrays (this shard).
     record: shard-local instance indices whose controller inputs (the plant
@@ -827,7 +828,16 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
     the same model (DeviceFleetLoop(link_models=...)).  A plant step that
     fails under a payload is a result (``plant_fail``), as under plant_spread.
     The summary carries ``plant_payload_mass`` (B,), the drawn masses, and
-    ``payload_known``."""
+    ``payload_known``.
+    tilt_known (with device_loop only, NotImplementedError otherwise: the host
+    fleets plan under the nominal mount): the controllers are told the table's
+    tilt, which the scenarios otherwise hide from them.  Instance b plans under
+    robot.Mount.table_tilt(tilt_b) (DeviceFleetLoop(mounts=...); None for tilt
+    0), that is in the table's frame, where the table is level: its circle lies
+    on the table, and its logs and metrics are read in that frame, while a
+    hidden-tilt instance tracks the world-horizontal circle and is scored in
+    the world frame.  The plant is not changed.  It combines with every other
+    spread.  The summary carries ``tilt_known``."""
     variant = str(variant).strip().lower()
     if variant not in ("classical", "ff"):
         raise ValueError(f"run_sweep: unknown variant {variant!r}")
@@ -898,6 +908,12 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
         if not device_loop:
             raise NotImplementedError("run_sweep: payload_known needs device_loop=True "
                                       "(the host fleets plan with the nominal model)")
+    if not isinstance(tilt_known, (bool, np.bool_)) and tilt_known not in (0, 1):
+        raise ValueError(f"run_sweep: tilt_known must be a flag, not {tilt_known!r}")
+    tilt_known = bool(tilt_known)
+    if tilt_known and not device_loop:
+        raise NotImplementedError("run_sweep: tilt_known needs device_loop=True "
+                                  "(the host fleets plan under the nominal mount)")
     if payload_spread is not None:
         payload_spread = check_payload_spread(payload_spread)
         if not device_loop:
@@ -982,7 +998,7 @@ def run_sweep(scenarios: Sequence[str] = ("flat", "tilted_5", "tilted_10", "tilt
                                 weights=sweep_cost_weights(seed, weight_spread) if weight_spread else None,
                                 limit_scale=sweep_limit_scales(seed, limit_spread) if limit_spread else None,
                                 payload_mass=sweep_payload_masses(seed, payload_spread) if payload_spread else None,
-                                plant_payload_mass=plant_payload, payload_known=payload_known)
+                                plant_payload_mass=plant_payload, payload_known=payload_known, tilt_known=tilt_known)
         out.update(names=names, seed=seed, shard=(lo, hi), n_all=n_all)
         return out
     plant = BatchedPlant(B, timestep=0.001, n_substeps=5, device=device, physics=physics,
@@ -1128,7 +1144,7 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
                       verbose, ucfgs=None, noise=None, solve_period=1, command_filter=False, tasks=None,
                       device_summary=False, keep_logs=True, plant_physics=None, allow_plant_fail=False,
                       force_profiles=None, weights=None, limit_scale=None, payload_mass=None,
-                      plant_payload_mass=None, payload_known=False) -> dict:
+                      plant_payload_mass=None, payload_known=False, tilt_known=False) -> dict:
     """run_sweep's loop on the device (fleet_loop.DeviceFleetLoop) and the
     host path's summary from the downloaded logs.  tasks: per-instance
     FleetTasks in place of traj; the summary's reference position and its
@@ -1170,7 +1186,9 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
                            link_models=payload_models(payload_mass) if payload_mass is not None else
                            payload_models(plant_payload_mass) if payload_known else None,
                            plant_link_models=None if plant_payload_mass is None else
-                           payload_models(plant_payload_mass))
+                           payload_models(plant_payload_mass),
+                           mounts=[R.Mount.table_tilt(float(a)) if float(a) != 0.0 else None for a in tilt]
+                           if tilt_known else None)
     wall0 = time.perf_counter()
     loop.run(steps)
     torch.cuda.synchronize(loop.dev)
@@ -1206,6 +1224,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
             out.update(payload_mass=np.asarray(payload_mass, float))
         if plant_payload_mass is not None:
             out.update(plant_payload_mass=np.asarray(plant_payload_mass, float), payload_known=bool(payload_known))
+        if tilt_known:
+            out.update(tilt_known=True)
         if tasks is not None and keep_logs:
             out.update(solved=r["solved"], surface=r["surface"] != 0)
         return out
@@ -1252,6 +1272,8 @@ def _run_sweep_device(variant, q0, tilt, scale, traj, z_contact, calibration, to
         out.update(payload_mass=np.asarray(payload_mass, float))
     if plant_payload_mass is not None:
         out.update(plant_payload_mass=np.asarray(plant_payload_mass, float), payload_known=bool(payload_known))
+    if tilt_known:
+        out.update(tilt_known=True)
     if tasks is not None:
         out.update(solved=r["solved"], surface=r["surface"] != 0)  # (ticks, B): the per-tick solve share
     return out

@@ -113,6 +113,28 @@ and ``state`` / ``load_state`` carry nothing for them.  It combines with
 ``plant_physics``, ``link_models`` and every other per-instance option.
 Without the argument the loop enqueues exactly the calls it did.
 
+With ``mounts`` every instance plans under its own base mounting and gravity
+vector (ffddp_solve_batch_mnt_dev, ffddp_fleet_pre_mnt_dev): one robot.Mount
+per instance (None: the nominal one), each with a ``frame`` -- the unchanged
+arm seen from another planning frame, such as the tilted table's
+(robot.Mount.table_tilt).  The plant stand-in has one mounting, so a
+``remounted`` arm is refused.  The rows (config.mount_rows) and the frames
+(Mount.obs_frame) are uploaded once.  After every plant step, and at the start
+sequence's first observation, one launch (ffddp_fleet_obs_frame_dev) writes the
+plant's records re-expressed in each instance's planning frame; the
+controllers' inputs, the logs and the metrics read those records, the injector
+goes on reading the joint-space q, v of the plant's own.  A mounted instance's
+task record, force profile, logs and metrics are therefore read in its planning
+frame: under a table_tilt mount the circle lies on the table and the tracking
+errors are measured along it.  The site calibration ``p_site_minus_frame`` is
+the shared nominal one: it is the site-minus-frame offset with the tool at the
+orientation the controller holds, and under a table-frame mount the controller
+holds that orientation relative to the table, so the nominal numbers are the
+right ones.  The plant and its tilted plane are unchanged, and ``state`` /
+``load_state`` carry nothing for the mounts: ``load_state`` re-frames the
+plant records it uploaded, with the loop's own frames.  Without the argument, or with
+None for every instance, the loop enqueues exactly the calls it did.
+
 Not on the device, and so not supported here: ``run_sweep``'s ``record`` and
 any per-tick host callback; ``tick()`` lets a caller look between ticks at the price of its own
 synchronisation.
@@ -125,7 +147,7 @@ import numpy as np
 
 from . import _abi
 from . import robot as R
-from .config import cost_weight_row, link_model_rows, torque_limit_rows
+from .config import cost_weight_row, link_model_rows, mount_rows, torque_limit_rows
 from .controller import ff_filter_alpha
 from .fleet import Traj, fleet_ocp_config, node_ref, site_calibration
 from .trajectory import FleetTask, ForceProfile, force_records, task_records
@@ -295,6 +317,11 @@ class DeviceFleetLoop:
     model) per instance, the link inertial parameters its plant integrates
     with; ``plant.link_rows`` (B, LINK_W) keeps the rows as set.
 
+    mounts: None, or one robot.Mount with a ``frame`` (or None, the nominal
+    mount) per instance, the base mounting and gravity its controller plans
+    under; ``mount_rows`` (B, MOUNT_W) and ``frame_rows`` (B, FRAME_W) keep the
+    rows as uploaded, ``obs_frame`` the re-framed records.
+
     ``S``: the controller state, ``T``: the solve's arrays, ``P``: the plant's
     (q, v, obs, tau_app, tau_filt, plane), ``J``: the injector's (row, a, b,
     seed, the rings, the filter, qv_ctrl, tau_hat, tau_ctrl; with
@@ -310,7 +337,7 @@ class DeviceFleetLoop:
                  tasks: Optional[Sequence[FleetTask]] = None, metrics: bool = False, logs: bool = True,
                  t_contact_phase=None, plant_physics=None,
                  force_profiles: Optional[Sequence[Optional[ForceProfile]]] = None, cost_weights=None,
-                 torque_limits=None, link_models=None, plant_link_models=None):
+                 torque_limits=None, link_models=None, plant_link_models=None, mounts=None):
         variant = str(variant).strip().lower()
         if variant not in ("classical", "ff"):
             raise ValueError(f"DeviceFleetLoop: unknown variant {variant!r}")
@@ -326,6 +353,15 @@ class DeviceFleetLoop:
             if len(plant_link_models) != int(B) or not all(m is None or isinstance(m, R.LinkModel)
                                                            for m in plant_link_models):
                 raise ValueError("DeviceFleetLoop: plant_link_models takes one robot.LinkModel (or None) per instance")
+        if mounts is not None:
+            mounts = list(mounts)
+            if len(mounts) != int(B) or not all(m is None or isinstance(m, R.Mount) for m in mounts):
+                raise ValueError("DeviceFleetLoop: mounts takes one robot.Mount (or None) per instance")
+            if any(m is not None and m.frame is None for m in mounts):
+                raise ValueError("DeviceFleetLoop: every mount must carry a frame (Mount.in_frame / table_tilt); "
+                                 "the plant stand-in has one mounting, so a remounted arm cannot run here")
+            if all(m is None for m in mounts):
+                mounts = None  # the nominal mount for all: the plain loop
         metrics, logs = bool(metrics), bool(logs)
         if not logs and not metrics:
             raise ValueError("DeviceFleetLoop: logs=False needs metrics=True (a run without either reports nothing)")
@@ -421,6 +457,17 @@ class DeviceFleetLoop:
         self.P = dict(q=up(q0), v=z(B, 7), obs=z(B, _abi.PLANT_OBS), tau_app=z(B, 7), tau_filt=z(B, 7),
                       plane=up(np.stack([np.concatenate(table_plane(0.0))] * B)))
         obs = self.P["obs"]
+        # per-instance mounts (ffddp_solve_batch_mnt_dev, ffddp_fleet_pre_mnt_dev, ffddp_fleet_obs_frame_dev): the rows
+        # and frames, uploaded once, and the re-framed records the controllers, the logs and the metrics read
+        self.mount_rows = self.frame_rows = self.mt = self.frame = self.frame_sel = self.obs_frame = None
+        self._framed = False  # the start sequence's first plant step is not re-framed (only its bias torque is read)
+        if mounts is not None:
+            self.mount_rows = mount_rows(mounts)
+            self.frame_rows = np.stack([(R.Mount() if m is None else m).obs_frame() for m in mounts])
+            self.mt, self.frame = up(self.mount_rows), up(self.frame_rows)
+            self.frame_sel = torch.from_numpy(np.array([m is not None for m in mounts], dtype=np.uint8)).to(self.dev)
+            self.obs_frame = z(B, _abi.PLANT_OBS)
+        plant_obs, obs = obs, (obs if self.obs_frame is None else self.obs_frame)
         self.T = dict(
             x0=z(B, nx), node_ref=z(B, N + 1, 6), inst_ref=z(B, 21), surface=z(B, dtype=torch.uint8),
             xs_init=z(B, N + 1, nx), us_init=z(B, N, 7), xs=z(B, N + 1, nx), us=z(B, N, 7), K=z(B, N, 7, nx),
@@ -500,7 +547,8 @@ class DeviceFleetLoop:
         # table (run_sweep); then the tilted plant's first observation
         self._plant_step(integrate=False)
         if variant == "classical":
-            self.S["tau_prev"].copy_(obs[:, 14:21])
+            self.S["tau_prev"].copy_(plant_obs[:, 14:21])
+        self._framed = True
         self.P["plane"].copy_(up(np.stack([np.concatenate(table_plane(t)) for t in tilt])))
         self.k = 0
         self._plant_step(integrate=False)
@@ -579,6 +627,10 @@ class DeviceFleetLoop:
         fail = self.log_fail[(self.k if self.logs else 1) if integrate else 0]
         self.plant.step_dev(P["q"], P["v"], P["tau_app"], P["plane"], P["obs"], fail=fail, integrate=integrate,
                             stream=self._stream)
+        rec = P["obs"]
+        if self.obs_frame is not None and self._framed:
+            rec = self.obs_frame
+            self.solver.fleet_obs_frame_dev(P["obs"], self.frame, rec, sel=self.frame_sel, stream=self._stream)
         if self.metrics and integrate and self.m_k < self.k:
             j = self.k - 1
             r = self._row(j)
@@ -591,7 +643,7 @@ class DeviceFleetLoop:
                 kw.update(p_ref=self.p_tab[j], ts=float(self.times[j]) + self.dt)
             if self.frec is not None:
                 kw.update(force=self.frec)
-            self.solver.fleet_metrics_dev(self.acc, P["obs"], self.t_phase, float(self.cfg.fn_des), **kw)
+            self.solver.fleet_metrics_dev(self.acc, rec, self.t_phase, float(self.cfg.fn_des), **kw)
             self.m_k = self.k
 
     def _enqueue_tick(self):
@@ -623,6 +675,9 @@ class DeviceFleetLoop:
         if self.md is not None:
             fkw = dict(fkw, link_model=self.md)
             mkw = dict(link_model=self.md)
+        if self.mt is not None:
+            fkw = dict(fkw, mount=self.mt)
+            mkw = dict(mkw, mount=self.mt)
         if self.sched is None:
             self.solver.fleet_pre_dev(T, self.params, hint, stream=self._stream, tasks=self.ktasks, **mkw)
             if self.frec is not None:
@@ -701,6 +756,11 @@ class DeviceFleetLoop:
                     self.log_need[r].copy_(torch.from_numpy(np.ascontiguousarray(s["metrics_need"])).to(self.dev))
             else:  # a state saved without them: the accumulators go on with the ticks run from here
                 self.m_k = self.k
+        if self.obs_frame is not None:
+            # the re-framed records are derived from the plant's, which were just replaced: a state saved with
+            # `stepped` set is followed by a tick that reads them before any plant step rewrites them
+            self.solver.fleet_obs_frame_dev(self.P["obs"], self.frame, self.obs_frame, sel=self.frame_sel,
+                                            stream=self._stream)
         torch.cuda.synchronize(self.dev)
 
     def results(self) -> dict:
@@ -734,7 +794,7 @@ class DeviceFleetLoop:
             self._plant_step()
             self._stepped = True
         if self.logs:
-            self.log_obs[k].copy_(self.P["obs"][:, [28, 29, 30, 46, 47]])
+            self.log_obs[k].copy_(self.T["obs"][:, [28, 29, 30, 46, 47]])
         torch.cuda.synchronize(self.dev)
         if self.metrics:
             from .runlog import metrics_from_accumulators

@@ -119,6 +119,83 @@ class LinkModel:
         return LinkModel(self.mass * f, self.com, self.inertia * f[:, None, None])
 
 
+def _check_rotation(Rm, who: str) -> np.ndarray:
+    Rm = np.array(Rm, dtype=np.float64)
+    if Rm.shape != (3, 3) or not np.all(np.isfinite(Rm)):
+        raise ValueError(f"{who}: a rotation is a finite (3, 3) array")
+    if np.max(np.abs(Rm.T @ Rm - np.eye(3))) > 1e-9 or abs(np.linalg.det(Rm) - 1.0) > 1e-9:
+        raise ValueError(f"{who}: the matrix is not a rotation (orthonormal to 1e-9, determinant +1)")
+    return Rm
+
+
+def _check_vector(v, who: str) -> np.ndarray:
+    v = np.array(v, dtype=np.float64)
+    if v.shape != (3,) or not np.all(np.isfinite(v)):
+        raise ValueError(f"{who}: a vector is a finite (3,) array")
+    return v
+
+
+class Mount:
+    """Where the arm's base stands in the planning world and which way gravity
+    points there, what a controller believes about its mounting: base_R (3, 3)
+    and base_p (3,), the placement of joint 1 in the planning (Pinocchio)
+    world, and gravity (3,).  The default is the nominal Panda's (JOINT_R[0],
+    JOINT_P[0], GRAVITY).  ``frame``: (R, p) of the planning frame in the
+    nominal Pinocchio world when the mount re-expresses the unchanged physical
+    system (in_frame, table_tilt), None for the nominal mount's identity and
+    for a physically moved base (remounted).  Immutable by convention."""
+
+    def __init__(self, base_R=None, base_p=None, gravity=None):
+        self.base_R = _check_rotation(JOINT_R[0] if base_R is None else base_R, "Mount: base_R")
+        self.base_p = _check_vector(JOINT_P[0] if base_p is None else base_p, "Mount: base_p")
+        self.gravity = _check_vector(GRAVITY if gravity is None else gravity, "Mount: gravity")
+        self.frame = None
+
+    @classmethod
+    def in_frame(cls, R, p) -> "Mount":
+        """The unchanged physical system seen from a frame M with pose
+        x_W = R x_M + p in the Pinocchio world: base_R = R^T JOINT_R[0],
+        base_p = R^T (JOINT_P[0] - p), gravity = R^T GRAVITY.  Keeps (R, p) as
+        ``frame``."""
+        R, p = _check_rotation(R, "Mount.in_frame: R"), _check_vector(p, "Mount.in_frame: p")
+        m = cls(R.T @ JOINT_R[0], R.T @ (JOINT_P[0] - p), R.T @ GRAVITY)
+        m.frame = (R, p)
+        return m
+
+    @classmethod
+    def remounted(cls, R, p) -> "Mount":
+        """A physically moved base (wall, ceiling, pedestal): the base frame has
+        pose (R, p) in the world, base_R = R JOINT_R[0], base_p = R JOINT_P[0]
+        + p; gravity is the world's.  ``frame`` is None."""
+        R, p = _check_rotation(R, "Mount.remounted: R"), _check_vector(p, "Mount.remounted: p")
+        return cls(R @ JOINT_R[0], R @ JOINT_P[0] + p, GRAVITY)
+
+    @classmethod
+    def table_tilt(cls, tilt_deg: float) -> "Mount":
+        """in_frame of the table's frame at tilt_deg: plant.table_plane's
+        rotation about the MuJoCo world's y axis through plant.TABLE_BODY_POS,
+        mapped to the Pinocchio world with R_MJ_FROM_PIN.  In that frame the
+        table is the flat table."""
+        from .plant import TABLE_BODY_POS  # plant imports this module through _abi
+
+        a = np.deg2rad(float(tilt_deg))
+        if not np.isfinite(a):
+            raise ValueError("Mount.table_tilt: the tilt must be finite")
+        Ry = np.array([[np.cos(a), 0.0, np.sin(a)], [0.0, 1.0, 0.0], [-np.sin(a), 0.0, np.cos(a)]])
+        p_mj = TABLE_BODY_POS - Ry @ TABLE_BODY_POS
+        D = R_MJ_FROM_PIN
+        return cls.in_frame(D.T @ Ry @ D, D.T @ p_mj)
+
+    def obs_frame(self) -> np.ndarray:
+        """The (12,) frame row of ffddp_fleet_obs_frame_dev, the planning
+        frame's pose in the MuJoCo world: R_mj = D R D row-major, then
+        p_mj = D p, D = R_MJ_FROM_PIN.  The identity for a mount without a
+        frame."""
+        R, p = (np.eye(3), np.zeros(3)) if self.frame is None else self.frame
+        D = R_MJ_FROM_PIN
+        return np.concatenate([(D @ R @ D.T).reshape(9), D @ p])
+
+
 def vertical_down_rotation_mj() -> np.ndarray:
     """_make_vertical_down_rotation_mj (crocoddyl_classical.py:241-248)."""
     z = np.array([0.0, 0.0, -1.0])

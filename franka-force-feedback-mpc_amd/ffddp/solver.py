@@ -140,9 +140,11 @@ class _RecycledPinned:
 
 class BatchedBoxFDDP:
     def __init__(self, cfg: OcpConfig, max_batch: int, device: int = 0, pinned_outputs: bool = False,
-                 outputs: str | None = None, robot=None):
+                 outputs: str | None = None, robot=None, mount=None):
         """robot: a robot.LinkModel, the inertial parameters this handle plans
         with in place of the nominal Panda's (the kinematics stay).
+        mount: a robot.Mount, the base placement and gravity vector this handle
+        plans with in place of the nominal ones.
         outputs: how solve() returns xs / us / K / cost / ...:
           "recycled" (default): fresh numpy arrays per solve() in page-locked
               memory recycled from earlier solves whose arrays are gone
@@ -156,6 +158,7 @@ class BatchedBoxFDDP:
               382-385)."""
         self.cfg = cfg
         self.robot = robot
+        self.mount = mount
         if outputs is None:
             outputs = "pinned" if pinned_outputs else "recycled"
         if outputs not in ("recycled", "fresh", "pinned"):
@@ -175,7 +178,8 @@ class BatchedBoxFDDP:
         self._cfg_struct = cfg.to_struct()
         h = C.c_void_p()
         rc = self._lib.ffddp_create(
-            C.byref(_abi.robot_struct() if robot is None else _abi.make_robot(robot)), C.byref(self._cfg_struct),
+            C.byref(_abi.robot_struct() if robot is None and mount is None else _abi.make_robot(robot, mount)),
+            C.byref(self._cfg_struct),
             int(device), self.max_batch, C.byref(h)
         )
         if rc != 0:
@@ -330,7 +334,7 @@ class BatchedBoxFDDP:
 
     # -- solve (device-resident torch tensors; bench path) ---------------------------
     def solve_dev(self, t, maxiter: int = 10, is_feasible: bool = False, stream=None, active=None, force_ref=None,
-                  cost_weights=None, torque_limits=None, link_model=None):
+                  cost_weights=None, torque_limits=None, link_model=None, mount=None):
         """t: dict of contiguous torch.cuda tensors with keys x0, node_ref, inst_ref,
         surface (uint8), xs_init, us_init and outputs xs, us, K, cost, iters (int32),
         ok (uint8), fn_pred, stats (int32).  Asynchronous on `stream` (hipStream_t int).
@@ -354,10 +358,16 @@ class BatchedBoxFDDP:
         (ffddp_solve_batch_mdl_dev; config.link_model_rows builds the rows);
         goes with or without the other four.  t["inst_ref"] stays the caller's:
         gravity_torque_dev(link_model=...) gives the torque reference under
-        each instance's model."""
+        each instance's model.
+        mount: optional (B, _abi.MOUNT_W) float64 device tensor, one row of
+        base placement and gravity per instance in place of the handle's
+        robot's (ffddp_solve_batch_mnt_dev; config.mount_rows builds the rows);
+        goes with or without the other five.  The references in t are the
+        caller's, in each instance's planning world; gravity_torque_dev(mount=
+        ...) gives the torque reference under each instance's mount."""
         B = int(t["x0"].shape[0])
         p = lambda k: C.c_void_p(int(t[k].data_ptr()))
-        rc = self._lib.ffddp_solve_batch_mdl_dev(
+        rc = self._lib.ffddp_solve_batch_mnt_dev(
             self._h, B, p("x0"), p("node_ref"), p("inst_ref"), p("surface"), p("xs_init"), p("us_init"),
             int(maxiter), int(bool(is_feasible)), p("xs"), p("us"), p("K"), p("cost"), p("iters"), p("ok"),
             p("fn_pred"), p("stats"),
@@ -370,24 +380,50 @@ class BatchedBoxFDDP:
                          "torque_limits must be a contiguous (B, TAU_LIM_W) float64 device tensor"),
             _opt_dev_ptr(link_model, "float64", (B, _abi.LINK_W),
                          "link_model must be a contiguous (B, LINK_W) float64 device tensor"),
+            _opt_dev_ptr(mount, "float64", (B, _abi.MOUNT_W),
+                         "mount must be a contiguous (B, MOUNT_W) float64 device tensor"),
             C.c_void_p(stream if stream else 0),
         )
-        self._check(rc, "ffddp_solve_batch_mdl_dev")
+        self._check(rc, "ffddp_solve_batch_mnt_dev")
 
-    def gravity_torque_dev(self, q, tau, link_model=None, stream=None):
+    def gravity_torque_dev(self, q, tau, link_model=None, stream=None, mount=None):
         """tau (B, 7) = rnea(q, 0, 0) for q (B, 7), contiguous float64 device
         tensors (ffddp_gravity_torque_dev), under the handle's robot; with
         link_model, (B, _abi.LINK_W) float64 device rows, under each instance's
-        own model (ffddp_gravity_torque_mdl_dev).  Asynchronous on `stream`."""
+        own model, and with mount, (B, _abi.MOUNT_W) float64 device rows, under
+        each instance's own base placement and gravity
+        (ffddp_gravity_torque_mnt_dev).  Asynchronous on `stream`."""
         B = int(q.shape[0])
         assert tuple(q.shape) == (B, 7) and tuple(tau.shape) == (B, 7) and q.is_contiguous() and tau.is_contiguous()
         assert q.is_cuda and tau.is_cuda and str(q.dtype) == str(tau.dtype) == "torch.float64"
-        rc = self._lib.ffddp_gravity_torque_mdl_dev(
+        rc = self._lib.ffddp_gravity_torque_mnt_dev(
             self._h, B, C.c_void_p(int(q.data_ptr())),
             _opt_dev_ptr(link_model, "float64", (B, _abi.LINK_W),
                          "link_model must be a contiguous (B, LINK_W) float64 device tensor"),
+            _opt_dev_ptr(mount, "float64", (B, _abi.MOUNT_W),
+                         "mount must be a contiguous (B, MOUNT_W) float64 device tensor"),
             C.c_void_p(int(tau.data_ptr())), C.c_void_p(stream if stream else 0))
-        self._check(rc, "ffddp_gravity_torque_mdl_dev")
+        self._check(rc, "ffddp_gravity_torque_mnt_dev")
+
+    def fleet_obs_frame_dev(self, obs, frame, obs_out, sel=None, stream=None):
+        """obs_out (B, >= 69) = the plant records obs (B, >= 69) re-expressed in
+        each instance's planning frame, frame (B, _abi.FRAME_W) float64 device
+        rows (robot.Mount.obs_frame: R, p in the MuJoCo world), in one launch
+        (ffddp_fleet_obs_frame_dev).  sel: optional (B,) uint8 device tensor;
+        an instance with sel[b] == 0 is copied verbatim.  Row-contiguous
+        float64 device tensors; obs_out must not overlap obs.  Asynchronous on
+        `stream`."""
+        B = int(obs.shape[0])
+        for a in (obs, obs_out):
+            assert a.is_cuda and str(a.dtype) == "torch.float64" and a.dim() == 2 and a.stride(1) == 1
+        assert int(obs_out.shape[0]) == B
+        rc = self._lib.ffddp_fleet_obs_frame_dev(
+            self._h, B, C.c_void_p(int(obs.data_ptr())), int(obs.stride(0)),
+            _opt_dev_ptr(frame, "float64", (B, _abi.FRAME_W),
+                         "frame must be a contiguous (B, FRAME_W) float64 device tensor"),
+            _opt_dev_ptr(sel, "uint8", (B,), "sel must be a contiguous (B,) uint8 device tensor"),
+            C.c_void_p(int(obs_out.data_ptr())), int(obs_out.stride(0)), C.c_void_p(stream if stream else 0))
+        self._check(rc, "ffddp_fleet_obs_frame_dev")
 
     # -- fleet tick glue (include/ffddp.h: ffddp_fleet_warm_start_dev / ffddp_fleet_keep_dev) --
     def fleet_warm_start_dev(self, t, stream=None):
@@ -521,7 +557,7 @@ class BatchedBoxFDDP:
         self._check(rc, "ffddp_fleet_metrics_fref_dev")
 
     def fleet_pre_dev(self, t, params: _abi.FleetParams, hint: bool = False, stream=None, sched: _abi.FleetSched = None,
-                      tasks: _abi.FleetTasks = None, link_model=None):
+                      tasks: _abi.FleetTasks = None, link_model=None, mount=None):
         """Everything a fleet tick does before the solve, for B instances in one
         launch.  Inputs t["q"], t["v"] (B, 7), t["fn_meas"], t["ee_z"] (B,),
         optionally t["contact"] (B,) and, for force feedback, t["tau_hat"]
@@ -540,7 +576,10 @@ class BatchedBoxFDDP:
         link_model: optional (B, _abi.LINK_W) float64 device tensor, the
         solve's link-model rows: the gravity torque reference is each
         instance's own (ffddp_fleet_pre_mdl_dev), with or without sched and
-        tasks.  Asynchronous on `stream`."""
+        tasks.  mount: optional (B, _abi.MOUNT_W) float64 device tensor, the
+        solve's mount rows: the gravity torque reference is computed under each
+        instance's own mount (ffddp_fleet_pre_mnt_dev), with or without the
+        others.  Asynchronous on `stream`."""
         B = int(t["x0"].shape[0])
         p = lambda k: C.c_void_p(int(t[k].data_ptr()) if t.get(k) is not None else 0)
         assert t["q"].stride(0) == t["v"].stride(0) and t["fn_meas"].stride(0) == t["ee_z"].stride(0)
@@ -551,6 +590,17 @@ class BatchedBoxFDDP:
                 int(t["q"].stride(0)), int(t["fn_meas"].stride(0)), p("tau_hat"),
                 int(th.stride(0)) if th is not None else 0, p("q_nom"))
         tail = (p("x0"), p("surface"), p("inst_ref"), p("node_ref"), p("xs_init"), p("us_init"))
+        if mount is not None:
+            sp = C.byref(self._fleet_sched(t, sched)) if sched is not None else None
+            rc = self._lib.ffddp_fleet_pre_mnt_dev(
+                *head, tasks if tasks is not None else _abi.FleetTasks(), p("node_ref1"), int(bool(hint)), *tail, sp,
+                _opt_dev_ptr(link_model, "float64", (B, _abi.LINK_W),
+                             "link_model must be a contiguous (B, LINK_W) float64 device tensor"),
+                _opt_dev_ptr(mount, "float64", (B, _abi.MOUNT_W),
+                             "mount must be a contiguous (B, MOUNT_W) float64 device tensor"),
+                C.c_void_p(stream if stream else 0))
+            self._check(rc, "ffddp_fleet_pre_mnt_dev")
+            return
         if link_model is not None:
             sp = C.byref(self._fleet_sched(t, sched)) if sched is not None else None
             rc = self._lib.ffddp_fleet_pre_mdl_dev(
@@ -745,14 +795,17 @@ class BatchedBoxFDDP:
         return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(_abi.KERNEL_CLASSES)}
 
     # -- problem.calcDiff(xs, us) -------------------------------------------------------
-    def calc_diff(self, batch, xs, us, force_ref=None, cost_weights=None, torque_limits=None, link_model=None):
+    def calc_diff(self, batch, xs, us, force_ref=None, cost_weights=None, torque_limits=None, link_model=None,
+                  mount=None):
         """force_ref: optional (B, N+1) host array, the desired normal contact
         force per instance and node (ffddp_calc_diff_fref).  cost_weights:
         optional (B, _abi.COST_W) host array, the scalar cost weights per
         instance (ffddp_calc_diff_wts).  torque_limits: optional
         (B, _abi.TAU_LIM_W) host array, the torque-limit rows per instance
         (ffddp_calc_diff_lim).  link_model: optional (B, _abi.LINK_W) host
-        array, the link-model rows per instance (ffddp_calc_diff_mdl)."""
+        array, the link-model rows per instance (ffddp_calc_diff_mdl).  mount:
+        optional (B, _abi.MOUNT_W) host array, the mount rows per instance
+        (ffddp_calc_diff_mnt)."""
         B = int(batch.x0.shape[0])
         N, nx = self.N, self.nx
         f = lambda a, shape: np.ascontiguousarray(np.asarray(a, np.float64).reshape(shape))
@@ -763,7 +816,7 @@ class BatchedBoxFDDP:
             lam=np.zeros((B, N + 1, 3)),
         )
         d = _abi.dptr
-        fr = cw = ul = md = None
+        fr = cw = ul = md = mt = None
         if force_ref is not None:
             fr = np.asarray(force_ref, np.float64)
             if fr.shape != (B, N + 1):
@@ -784,15 +837,21 @@ class BatchedBoxFDDP:
             if md.shape != (B, _abi.LINK_W):
                 raise ValueError("link_model must have shape (B, LINK_W)")
             md = np.ascontiguousarray(md)
-        rc = self._lib.ffddp_calc_diff_mdl(
+        if mount is not None:
+            mt = np.asarray(mount, np.float64)
+            if mt.shape != (B, _abi.MOUNT_W):
+                raise ValueError("mount must have shape (B, MOUNT_W)")
+            mt = np.ascontiguousarray(mt)
+        rc = self._lib.ffddp_calc_diff_mnt(
             self._h, B, d(f(batch.x0, (B, nx))), d(f(batch.node_ref, (B, N + 1, 6))), d(f(batch.inst_ref, (B, 21))),
             _abi.uptr(np.ascontiguousarray(np.asarray(batch.surface, np.uint8))), d(f(xs, (B, N + 1, nx))),
             d(f(us, (B, N, 7))), d(fr) if fr is not None else None, d(cw) if cw is not None else None,
-            d(ul) if ul is not None else None, d(md) if md is not None else None, d(out["Fx"]),
+            d(ul) if ul is not None else None, d(md) if md is not None else None, d(mt) if mt is not None else None,
+            d(out["Fx"]),
             d(out["Fu"]), d(out["Lx"]), d(out["Lu"]), d(out["Lxx"]), d(out["Lxu"]), d(out["Luu"]), d(out["cost"]),
             d(out["xnext"]), d(out["lam"]),
         )
-        self._check(rc, "ffddp_calc_diff_mdl")
+        self._check(rc, "ffddp_calc_diff_mnt")
         return out
 
 

@@ -355,6 +355,52 @@ int ffddp_solve_batch_mdl_dev(ffddp_handle* h, int B, const double* x0, const do
  * finite and > 0, or a com or inertia entry that is not finite. */
 int ffddp_link_model_rows(const ffddp_robot* robots, int B, double* rows);
 
+/* ffddp_solve_batch_mdl_dev with the arm's base mounting and the gravity
+ * vector per instance: mount_rows is [B][FFDDP_MOUNT_W] device doubles, row b
+ * what instance b plans with, in the solve's (Pinocchio) world.  A row is 16
+ * doubles (128 bytes, one cache line):
+ *     0 .. 8     base_R, row-major   in place of ffddp_robot.joint_R[0]
+ *     9 .. 11    base_p              in place of ffddp_robot.joint_p[0]
+ *     12 .. 14   gravity             in place of ffddp_robot.gravity
+ *     15         padding, which the library never reads
+ * ffddp_mount_rows packs ffddp_robot structs into rows, so a row of the
+ * handle's robot gives the bits of the call without mount_rows.  base_R must
+ * be a rotation; the library does not check it.  Joint placements 1..6 and
+ * the EE offset stay the handle's.
+ *
+ * Planning in a frame M with pose x_W = R x_M + p of the unchanged physical
+ * system is the same problem with base_R = R^T joint_R[0], base_p =
+ * R^T (joint_p[0] - p) and gravity = R^T gravity, and with the references in M
+ * (the contact normal, the tangential and plane costs are M-aligned by
+ * construction).  A physically re-mounted arm changes the placement and keeps
+ * the gravity.
+ *
+ * Rows of unselected instances are not read.  `active`, force_ref, cost_w,
+ * tau_lim and link_rows stay optional and combine freely with mount_rows
+ * (without link_rows the solve reads rows of the handle's robot that the
+ * handle keeps, allocated by the first such call; likewise the limits, weights
+ * and fn_des).  mount_rows == NULL is ffddp_solve_batch_mdl_dev: same kernels,
+ * same bits.  Errors are ffddp_solve_batch_mdl_dev's.  The torque reference
+ * inst_ref[14..20] is the caller's: ffddp_gravity_torque_mnt_dev gives it under
+ * each instance's mount.  The host-pointer entry point, solve plans and
+ * ffddp_build_problem_dev take no rows. */
+#define FFDDP_MOUNT_W 16
+int ffddp_solve_batch_mnt_dev(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                              const double* inst_ref, const uint8_t* surface, const double* xs_init,
+                              const double* us_init, int maxiter, int is_feasible, double* xs, double* us, double* K,
+                              double* cost, int32_t* iters, uint8_t* ok, double* fn_pred, int32_t* stats,
+                              const uint8_t* active, const double* force_ref, const double* cost_w,
+                              const double* tau_lim, const double* link_rows, const double* mount_rows, void* stream);
+
+/* Host function: rows [B][FFDDP_MOUNT_W] for ffddp_solve_batch_mnt_dev,
+ * ffddp_calc_diff_mnt, ffddp_gravity_torque_mnt_dev and ffddp_fleet_pre_mnt_dev
+ * from joint_R[0], joint_p[0] and gravity of B robots (the only fields read,
+ * plain copies); padding is zero.  FFDDP_E_INVALID for B < 0, for a null
+ * pointer with B > 0, or for an entry that is not finite; B == 0 reads and
+ * writes nothing and returns 0 whatever the pointers are, as
+ * ffddp_link_model_rows does. */
+int ffddp_mount_rows(const ffddp_robot* robots, int B, double* rows);
+
 /* Solve plan for a receding-horizon loop: one solve of a fixed batch per
  * control tick (crocoddyl_classical.py:367 called every tick at
  * run_classical.py:412).  ffddp_plan_create captures the whole host-array
@@ -439,6 +485,14 @@ int ffddp_calc_diff_mdl(ffddp_handle* h, int B, const double* x0, const double* 
                         const double* link_rows, double* Fx, double* Fu, double* Lx, double* Lu, double* Lxx,
                         double* Lxu, double* Luu, double* cost, double* xnext, double* lam);
 
+/* ffddp_calc_diff_mdl with host mount rows [B][FFDDP_MOUNT_W]
+ * (ffddp_solve_batch_mnt_dev's array; NULL: ffddp_calc_diff_mdl). */
+int ffddp_calc_diff_mnt(ffddp_handle* h, int B, const double* x0, const double* node_ref,
+                        const double* inst_ref, const uint8_t* surface, const double* xs,
+                        const double* us, const double* force_ref, const double* cost_w, const double* tau_lim,
+                        const double* link_rows, const double* mount_rows, double* Fx, double* Fu, double* Lx,
+                        double* Lu, double* Lxx, double* Lxu, double* Luu, double* cost, double* xnext, double* lam);
+
 /* Host-side setup helpers (CPU, same model code): frame placement of the EE
  * (pin.forwardKinematics + updateFramePlacements, crocoddyl_classical.py:199-225)
  * and gravity torque rnea(q, 0, 0) (_gravity_torque, :447-451) for B configurations. */
@@ -521,6 +575,14 @@ int ffddp_gravity_torque_dev(ffddp_handle* h, int B, const double* q, double* ta
  * NULL is that function. */
 int ffddp_gravity_torque_mdl_dev(ffddp_handle* h, int B, const double* q, const double* link_rows, double* tau,
                                  void* stream);
+/* The same under each instance's own mount as well: mount_rows
+ * [B][FFDDP_MOUNT_W] device doubles (ffddp_solve_batch_mnt_dev).  Either array
+ * may be NULL (the handle's robot supplies that part); both NULL is
+ * ffddp_gravity_torque_dev.  Rows of the handle's robot give its bits.
+ * FFDDP_E_INVALID for a null handle, B < 0, or a null q or tau with B > 0
+ * (checked here, before any launch). */
+int ffddp_gravity_torque_mnt_dev(ffddp_handle* h, int B, const double* q, const double* link_rows,
+                                 const double* mount_rows, double* tau, void* stream);
 
 /* Device-side problem builder: what _build_problem (crocoddyl_classical.py:
  * 521-556; FF :776-836) feeds the action models, for B instances at once,
@@ -928,6 +990,43 @@ int ffddp_fleet_pre_mdl_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p,
                             const double* q_nom, ffddp_fleet_tasks tasks, const double* node_ref1, int contact_hint,
                             double* x0, uint8_t* surface, double* inst_ref, double* node_ref, double* xs_init,
                             double* us_init, const ffddp_fleet_sched* sched, const double* link_rows, void* stream);
+/* ffddp_fleet_pre_mdl_dev with each instance's own mount: mount_rows is the
+ * solve's [B][FFDDP_MOUNT_W] rows (ffddp_solve_batch_mnt_dev), under which (and
+ * under link_rows, if given) the gravity torque reference inst_ref[14..20] of
+ * torque modes 0 and 1 is computed (ffddp_gravity_torque_mnt_dev's bits).
+ * Every other output is unchanged; the measurements handed in are expected in
+ * the instance's planning frame (ffddp_fleet_obs_frame_dev).  mount_rows ==
+ * NULL gives ffddp_fleet_pre_mdl_dev's bits.  Errors are its, under this
+ * function's name. */
+int ffddp_fleet_pre_mnt_dev(ffddp_handle* h, int B, const ffddp_fleet_params* p, const ffddp_fleet_state* s,
+                            const double* q, const double* v, const double* fn_meas, const double* contact,
+                            const double* ee_z, int ld_qv, int ld_scalar, const double* tau_hat, int ld_tau_hat,
+                            const double* q_nom, ffddp_fleet_tasks tasks, const double* node_ref1, int contact_hint,
+                            double* x0, uint8_t* surface, double* inst_ref, double* node_ref, double* xs_init,
+                            double* us_init, const ffddp_fleet_sched* sched, const double* link_rows,
+                            const double* mount_rows, void* stream);
+
+/* A plant record per instance (ffddp_plant_step_dev's [B][ld_obs] observation,
+ * FFDDP_PLANT_OBS = 69 words, MuJoCo world) re-expressed in each instance's
+ * planning frame.  frame is [B][FFDDP_FRAME_W] device doubles, the frame's
+ * pose in the MuJoCo world: R (9, row-major) and p (3), x_world = R x_frame +
+ * p.  The 69 words are copied to obs_out [B][ld_out], with these replaced:
+ *     EE position (28..30)           R^T (x - p)
+ *     EE velocity (31..33)           R^T x
+ *     EE rotation (34..42)           R^T X
+ *     world contact force (43..45)   R^T x
+ *     site Jacobian (48..68, 3 x 7)  R^T J
+ * q, dq, bias, constraint torque, the normal force and the contact count are
+ * joint-space or scalar and stay.  Each replaced entry i is
+ * (R[0][i] x0 + R[1][i] x1) + R[2][i] x2 in that order, without contraction
+ * (x - p is formed first), so the same expression in IEEE doubles elsewhere
+ * gives the same bits.  sel is [B] bytes or NULL (all): an instance with
+ * sel[b] == 0 is copied verbatim and its frame row is not read.  obs_out must
+ * not overlap obs.  FFDDP_E_INVALID for a null handle, obs, frame or obs_out,
+ * B <= 0, ld_obs < 69 or ld_out < 69; FFDDP_E_CAPACITY for B > max_batch. */
+#define FFDDP_FRAME_W 12
+int ffddp_fleet_obs_frame_dev(ffddp_handle* h, int B, const double* obs, int ld_obs, const double* frame,
+                              const uint8_t* sel, double* obs_out, int ld_out, void* stream);
 
 /* The sweep's task metrics accumulated on the device: one call folds one plant
  * record per instance -- the observation after a tick's command -- into

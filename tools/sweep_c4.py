@@ -30,6 +30,8 @@ wall time, closed-loop ticks/s).
                                                                # the torque limits per instance, scaled log-uniformly
   python tools/sweep_c4.py --device-loop 1 --device-refs 1 --payload-spread 0 3
                                                                # a payload (kg) in each controller's model, uniform
+  python tools/sweep_c4.py --device-loop 1 --device-refs 1 --device-noise philox --tilt-known 1
+                                                               # the controllers are told the table's tilt
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 tools/sweep_c4.py
 """
 import argparse
@@ -117,6 +119,9 @@ def build_parser():
                          "offset; the controllers plan with the nominal model unless --payload-known 1")
     ap.add_argument("--payload-known", type=int, choices=(0, 1), default=0,
                     help="with --plant-payload-spread and --device-loop 1: 1 gives each controller its plant's model")
+    ap.add_argument("--tilt-known", type=int, choices=(0, 1), default=0,
+                    help="with --device-loop 1: 1 tells each controller its table's tilt (it plans in the table's "
+                         "frame, and is scored there); the plant is unchanged")
     ap.add_argument("--scenarios", nargs="+", default=list(ALL_SCENARIOS), help="scenarios to sweep (default: all 5)")
     return ap
 
@@ -152,7 +157,8 @@ def main():
                            plant_spread=a.plant_spread, uncertainty_spread=uspread,
                            force_spread=a.force_spread, force_ramp=a.force_ramp, weight_spread=wspread,
                            limit_spread=a.limit_spread, payload_spread=a.payload_spread,
-                           plant_payload_spread=a.plant_payload_spread, payload_known=bool(a.payload_known))
+                           plant_payload_spread=a.plant_payload_spread, payload_known=bool(a.payload_known),
+                           tilt_known=bool(a.tilt_known))
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -251,6 +257,7 @@ def main():
                      float(np.nanmean(pi["rms_tangential_error_contact_phase"][which == i])),
                  "contact_loss_contact_phase_pct": float(np.nanmean(pi["contact_loss_contact_phase_pct"][which == i]))}
                 for i in range(4) if np.any(which == i)])
+        line["tilt_known"] = int(bool(res.get("tilt_known", False)))
         # instances that left the nominal regime, per scenario: any tick on the unstable fallback; a non-finite summary
         ui, ri = fleet.SUMMARY_KEYS.index("unstable_ticks"), fleet.SUMMARY_KEYS.index("rms_3d_error")
         line["diverged"] = {str(s): {"unstable_instances": int(np.sum(m[names == s, ui] > 0)),
