@@ -123,6 +123,8 @@ struct Dev {
                        //          BoxQP bounds; null: C's limits
   const double* md;    // [B][FFDDP_LINK_W] link-model rows (ffddp_solve_batch_mdl_dev), read by the MD
                        //          instantiations of k_node / k_forward_g8 only; null: C.rb's inertial parameters
+  uint8_t* uni0;       // [B]  the instance starts from one repeated (x, u) point (k_init; k_node_rep)
+  double* rep;         // [B][REP_W]  node 0's stash for k_node_rep (ffddp_primal_g8.hpp)
   const double* mt;    // [B][FFDDP_MOUNT_W] mount rows (ffddp_solve_batch_mnt_dev): base placement and gravity, read by
                        //          the MT instantiations of k_node / k_forward_g8 / k_finalize; null: C.rb's
 };
@@ -183,9 +185,38 @@ constexpr int INIT_BLOCK = 256;
 template <bool SEL>
 __global__ __launch_bounds__(INIT_BLOCK) void k_init(const DevConsts* __restrict__ Cg, Dev d, const double* xs_init,
                                                      const double* us_init, int is_feasible,
-                                                     const uint8_t* __restrict__ active) {
+                                                     const uint8_t* __restrict__ active,
+                                                     const double* __restrict__ node_ref,
+                                                     const uint8_t* __restrict__ surface, int nc) {
   const DevConsts& C = *Cg;
   const int N = C.N, nx = C.nx;
+  // Uniform start (k_node_rep): the running nodes 0..N-1 of the instance share
+  // one (x, u) bit pattern, and so do the node-reference components that enter
+  // the contact dynamics (a surface instance's target point along the
+  // constrained axes), so their calc differs from node 0's only in the
+  // reference-dependent residuals.  xs_init[N] is the terminal model's and not
+  // part of the test.  One wave per instance; bit patterns, not ==, so -0 and
+  // NaN do not pass as equal.  node_ref null: the replication is off.
+  {
+    const int l = threadIdx.x % 64;
+    const int nw = (int)gridDim.x * (INIT_BLOCK / 64);
+    for (int b = (int)blockIdx.x * (INIT_BLOCK / 64) + threadIdx.x / 64; b < d.B; b += nw) {
+      bool same = node_ref != nullptr && N >= 2 && (!SEL || active[b] != 0);
+      if (same) {
+        const long long* x = reinterpret_cast<const long long*>(xs_init + (long)b * (N + 1) * nx);
+        for (int i = l; i < (N - 1) * nx; i += 64) same = same && x[nx + i] == x[i % nx];
+        const long long* u = reinterpret_cast<const long long*>(us_init + (long)b * N * NU);
+        for (int i = l; i < (N - 1) * NU; i += 64) same = same && u[NU + i] == u[i % NU];
+        if (surface[b] != 0) {
+          const long long* r = reinterpret_cast<const long long*>(node_ref + (long)b * (N + 1) * 6);
+          const int c0 = nc == 1 ? 2 : 0;
+          for (int i = l; i < (N - 1) * nc; i += 64) same = same && r[(1 + i / nc) * 6 + c0 + i % nc] == r[c0 + i % nc];
+        }
+      }
+      const bool all = __all(same) != 0;
+      if (l == 0) d.uni0[b] = all ? 1 : 0;
+    }
+  }
   if constexpr (SEL) {
     __shared__ int red[INIT_BLOCK / 64], wcnt[INIT_BLOCK / 64];
     const int w = threadIdx.x / 64, l = threadIdx.x % 64;
@@ -292,7 +323,7 @@ __device__ __forceinline__ void primal_group(const DevConsts& C, const Dev& d, c
                                              const double* __restrict__ node_ref, const double* __restrict__ inst_ref,
                                              const uint8_t* __restrict__ surface, int b, int t, Primal* P,
                                              double* lk, const double* __restrict__ xsrc,
-                                             const double* __restrict__ usrc) {
+                                             const double* __restrict__ usrc, double* __restrict__ stash) {
   const int N = C.N;
   constexpr int nx = FF ? 21 : 14;
   const int li = g8_lane();
@@ -329,9 +360,11 @@ __device__ __forceinline__ void primal_group(const DevConsts& C, const Dev& d, c
   const double* ul = UL ? d.ul + (long)b * FFDDP_TAU_LIM_W : nullptr;
   const double* md = MD ? d.md + (long)b * FFDDP_LINK_W : nullptr;
   const double* mt = MT ? d.mt + (long)b * FFDDP_MOUNT_W : nullptr;
-  const double pc = node_primal_g8<NC, FR, CW, UL, MD, MT>(C, mode, surf, q, v, u, xreg[ji], xreg[7 + ji], xreg[14 + ji], ref, P,
+  // the kernels k_node_rep completes compute the reference-dependent terms through the functions it shares
+  constexpr bool STRICT = !FF && !FR && !CW && !UL && !MD && !MT;
+  const double pc = node_primal_g8<NC, FR, CW, UL, MD, MT, STRICT>(C, mode, surf, q, v, u, xreg[ji], xreg[7 + ji], xreg[14 + ji], ref, P,
                                                            lk, lam, FR ? d.fref + ((long)b * (N + 1) + t) : nullptr, cw, ul, md,
-                                                           mt);
+                                                           mt, stash);
   double* rec = d.rec_buf + ((long)b * (N + 1) + t) * d.rec;
   // node cost (IAM scaling, FF augmentation terms): per-lane shares summed over the group
   double c = FF ? C.dt * pc : (terminal ? pc : C.dt * pc);
@@ -376,6 +409,10 @@ __device__ __forceinline__ void primal_group(const DevConsts& C, const Dev& d, c
       const double vn = (mode == MODE_TERMINAL_X) ? v : v + a * dt;
       f[li] = feas ? 0.0 : qn - yn[li];
       f[7 + li] = feas ? 0.0 : vn - yn[7 + li];
+      if (stash != nullptr) {
+        stash[REP_XN + li] = qn;
+        stash[REP_XN + 7 + li] = vn;
+      }
       if (FF) f[14 + li] = feas ? 0.0 : (C.alpha * y[14 + li] + C.beta * usrc[(long)t * NU + li]) - yn[14 + li];
     }
     if (t == 0) {
@@ -430,7 +467,8 @@ __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE
                                                       const double* __restrict__ x0,
                                                       const double* __restrict__ node_ref,
                                                       const double* __restrict__ inst_ref,
-                                                      const uint8_t* __restrict__ surface, int force_all, int cur) {
+                                                      const uint8_t* __restrict__ surface, int force_all, int cur,
+                                                      int rep0) {
   const DevConsts& C = *Cg;
   const int N = C.N;
   constexpr int nx = FF ? 21 : 14;
@@ -449,9 +487,21 @@ __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE
     b = active ? al.list[slot] : 0;
     if (active) active = (d.st[b].done == 0) && (d.st[b].recalc != 0);
   }
-  const long node = (long)b * (N + 1) + t;
-  const bool surf = active ? surface[b] != 0 : false;
   const bool terminal = t == N;
+  // rep0 (the first node stage of a solve): of an instance that starts from
+  // one repeated (x, u) point, node 0 and the terminal node run; node 0 also
+  // stashes what k_node_rep, launched next, builds nodes 1..N-1 from.  The
+  // plain classical kernels only: the others have no such branch.
+  bool rep_src = false;
+  if constexpr (!FF && !FR && !CW && !UL && !MD && !MT) {
+    if (rep0 && active && !terminal && d.uni0[b] != 0) {
+      if (t == 0)
+        rep_src = true;
+      else
+        active = false;
+    }
+  }
+  const bool surf = active ? surface[b] != 0 : false;
   constexpr bool ff = FF;
   const int mode = !terminal ? MODE_RUNNING : (ff ? MODE_TERMINAL_U : MODE_TERMINAL_X);
   // current iterate: the trial the last line search accepted (not yet copied
@@ -464,7 +514,8 @@ __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE
   const double* ref = node_ref + ((long)b * (N + 1) + t) * 6;
   NodeGroupShared& G = S.g[grp];
   Primal& P = G.P;
-  if (active && lane < G8) primal_group<NC, FF, FR, CW, UL, MD, MT>(C, d, x0, node_ref, inst_ref, surface, b, t, &P, G.lk, xsrc, usrc);
+  if (active && lane < G8) primal_group<NC, FF, FR, CW, UL, MD, MT>(C, d, x0, node_ref, inst_ref, surface, b, t, &P, G.lk, xsrc, usrc,
+                                                                    rep_src ? d.rep + (long)b * REP_W : nullptr);
   __syncthreads();
   const bool need_u = mode != MODE_TERMINAL_X;
   // control directions first, their results stored at once (neither touches
@@ -537,9 +588,18 @@ __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE
       }
       // Lx_in[j]
       double lx = 0.0;
-      for (int r = 0; r < nd; ++r) lx += col[r] * g[r];
-      lx = (lx + P.gx[j]) * sc;
+      if constexpr (!FF && !FR && !CW && !UL && !MD && !MT) {
+        lx = node_lx_entry<12 + NC>(col, g, P.gx[j], sc);  // shared with k_node_rep
+      } else {
+        for (int r = 0; r < nd; ++r) lx += col[r] * g[r];
+        lx = (lx + P.gx[j]) * sc;
+      }
       if (ff) lx += wy * wy2j * (y[j] - x0[(long)b * nx + j]);
+      if (rep_src) {
+        double* stash = d.rep + (long)b * REP_W;
+        for (int r = 0; r < nd; ++r) stash[REP_COL + j * NDENSE_MAX + r] = col[r];
+        stash[REP_GX + j] = P.gx[j];
+      }
       rec[rec_off_Lx(nx) + j] = lx;
       // Lxu_in row j (force rows only): classical -> Lxu row j; FF -> Lxx_aug[14+k][j]
       if (need_u) {
@@ -616,6 +676,72 @@ __global__ __launch_bounds__(NODE_BLOCK) __attribute__((amdgpu_waves_per_eu(NODE
   }
 }
 
+
+// Nodes 1..N-1 of the instances that start from one repeated (x, u) point
+// (d.uni0, k_init), once per solve after the first k_node, which ran their
+// nodes 0 and N only.  Such a node's calc is node 0's up to the terms the node
+// references enter: the EE residuals' gradients (so Lx) and the cost.  16-lane
+// group per node: the record blocks that do not depend on the references (A,
+// Lxx, Lxu, Luu, Lu, lambda) are copied from node 0's record with 16-byte
+// accesses, Lx and the cost recomputed from node 0's stash (d.rep) through the
+// functions k_node computes them with, and the gap written from node 0's next
+// state.  (The first node stage has no accepted trial to commit into xs / us.)
+template <int NC>
+__global__ __launch_bounds__(NODE_BLOCK) void k_node_rep(const DevConsts* __restrict__ Cg, Dev d,
+                                                         const double* __restrict__ node_ref,
+                                                         const uint8_t* __restrict__ surface) {
+  const DevConsts& C = *Cg;
+  const int N = C.N;
+  constexpr int nx = 14, nd = 12 + NC;
+  const int grp = threadIdx.x / NODE_GROUP, lane = threadIdx.x % NODE_GROUP;
+  const long gnode = (long)blockIdx.x * NODE_GPB + grp;
+  const int b = (int)(gnode / (N - 1)), t = 1 + (int)(gnode % (N - 1));
+  if (b >= d.B || d.uni0[b] == 0) return;
+  const InstState* st = d.st + b;
+  if (st->done != 0) return;
+  const double* src = d.rec_buf + (long)b * (N + 1) * d.rec;
+  double* rec = d.rec_buf + ((long)b * (N + 1) + t) * d.rec;
+  const double* stash = d.rep + (long)b * REP_W;
+  // the reference-independent blocks: words [0, Lx) and lambda
+  {
+    const double2* s2 = reinterpret_cast<const double2*>(src);
+    double2* r2 = reinterpret_cast<double2*>(rec);
+    // classical layout (rec_off_* of ffddp_node.hpp): Lx starts at word 490 and lambda at 512, both even
+    constexpr int o_lx = 147 + nx * nx + nx * 7 + 49, o_lam = o_lx + nx + 7 + 1;
+    static_assert(o_lx % 2 == 0 && o_lam % 2 == 0, "16-byte copy ranges");
+    const int n2 = rec_off_Lx(nx) / 2;
+#pragma unroll 4
+    for (int i = lane; i < n2; i += NODE_GROUP) r2[i] = s2[i];
+    if (lane < 2) r2[rec_off_lam(nx) / 2 + lane] = s2[rec_off_lam(nx) / 2 + lane];
+    if (lane < NU) rec[rec_off_Lu(nx) + lane] = src[rec_off_Lu(nx) + lane];
+  }
+  // the residual terms of this node's references
+  double rr[3], wee[3], pee[3], vp[3], lm[3], Dd[NDENSE_MAX], gd[NDENSE_MAX], Ho[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    rr[k] = stash[REP_RR + k];
+    wee[k] = stash[REP_WEE + k];
+    pee[k] = stash[REP_PEE + k];
+    vp[k] = stash[REP_VP + k];
+    lm[k] = stash[REP_LM + k];
+  }
+  const double* ref = node_ref + ((long)b * (N + 1) + t) * 6;
+  const double cee = ee_contact_costs<NC, false, false>(C, surface[b] != 0, rr, wee, pee, vp, lm, ref, nullptr, nullptr, Dd,
+                                                        gd, Ho);
+  if (lane == 0) rec[rec_off_cost(nx)] = C.dt * (stash[REP_CJ] + cee);
+  if (lane < 14) {
+    double col[nd];
+#pragma unroll
+    for (int r = 0; r < nd; ++r) col[r] = stash[REP_COL + lane * NDENSE_MAX + r];
+    rec[rec_off_Lx(nx) + lane] = node_lx_entry<nd>(col, gd, stash[REP_GX + lane], C.dt);
+  }
+  // the gap to the next node's state: node 0's next state against xs[t + 1]
+  if (lane < 14) {
+    const bool feas = st->is_feasible != 0;
+    const double* yn = d.xs + ((long)b * (N + 1) + t + 1) * nx;
+    d.fs[((long)b * (N + 1) + t + 1) * nx + lane] = feas ? 0.0 : stash[REP_XN + lane] - yn[lane];
+  }
+}
 
 __device__ __forceinline__ bool bad(double v) { return isnan(v) || isinf(v) || v >= 1e30; }
 
@@ -3263,6 +3389,9 @@ struct ffddp_handle {
   // +2.3 %, B=2048 +4 % over 2), else 0 (latency-bound: the stagger only
   // delays the last slice, B=512/1024 +1.2 % over 1)
   int stagger = -1;
+  // FFDDP_NODE_REP=0: the first node stage evaluates every node of a uniform cold start instead of
+  // node 0 and k_node_rep's copies (same results)
+  bool node_rep = true;
   int fw_first = 4;  // trials evaluated before the fallback pass (FFDDP_FW_FIRST)
   // first-pass trial counts of the first iterations (FFDDP_FW_SCHED="2,2,2,2"):
   // while every instance is active the line search is throughput-bound, so a
@@ -3322,7 +3451,7 @@ template <class T> int dalloc(ffddp_handle* h, T** p, size_t n) {
 
 void free_all(ffddp_handle* h) {
   void* ps[] = {h->dc, h->drb, h->d.alist, h->d.acnt, h->d.rec_buf, h->d.fs, h->d.xs, h->d.us, h->d.K, h->d.k, h->d.w, h->d.xs_try,
-                h->d.us_try, h->d.trial, h->d.trial_fail, h->d.st, h->in_x0, h->in_nref, h->in_iref, h->in_xs,
+                h->d.us_try, h->d.trial, h->d.trial_fail, h->d.st, h->d.uni0, h->d.rep, h->in_x0, h->in_nref, h->in_iref, h->in_xs,
                 h->in_us, h->in_surf, h->out_xs, h->out_us, h->out_K, h->out_cost, h->out_fn, h->out_iters,
                 h->out_stats, h->out_ok};
   for (void* p : ps)
@@ -3380,6 +3509,8 @@ Dev dev_slice(const Dev& d0, int b0, int Bk, int k) {
   d.trial_fail += (long)b0 * NTRIALS;
   d.st += b0;
   d.alist += 2L * b0;
+  d.uni0 += b0;
+  d.rep += (long)b0 * REP_W;
   d.acnt += 4 * k;
   if (d.trace) d.trace += (long)b0 * d0.trace_it * FFDDP_TRACE_W;
   if (d.fref) d.fref += (long)b0 * (N + 1);
@@ -3466,6 +3597,9 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
       if (sl[k].s != s) HIPCHK(h, hipStreamWaitEvent(sl[k].s, h->sev[0], 0));
   }
   const long nxl = nx, N1 = N + 1;
+  // the uniform-start replication (k_node_rep): the plain classical kernels only, N >= 2
+  constexpr bool REP = !FF && !FR && !CW && !UL && !MD && !MT;
+  const bool node_rep = REP && h->node_rep && N >= 2;
   if (io) {
     io->ns = S;
     for (int k = 0; k < S; ++k) {
@@ -3486,12 +3620,16 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
   auto enqueue_init = [&](int k) {
     ProfScope p(h, sl[k].s, KC_INIT);
     const long b0 = sl[k].b0;
+    // null: no instance of the slice is flagged as a uniform start
+    auto rep_ref = [&](long b) { return node_rep ? a.nref + b * N1 * 6 : nullptr; };
     if (a.active)
       hipLaunchKernelGGL(k_init<true>, dim3(1024), dim3(INIT_BLOCK), 0, sl[k].s, h->dc, sl[k].d,
-                         a.xs_init + b0 * N1 * nxl, a.us_init + b0 * (long)N * NU, a.is_feasible, a.active + b0);
+                         a.xs_init + b0 * N1 * nxl, a.us_init + b0 * (long)N * NU, a.is_feasible, a.active + b0, rep_ref(b0),
+                         a.surf + b0, NC);
     else
       hipLaunchKernelGGL(k_init<false>, dim3(1024), dim3(INIT_BLOCK), 0, sl[k].s, h->dc, sl[k].d,
-                         a.xs_init + b0 * N1 * nxl, a.us_init + b0 * (long)N * NU, a.is_feasible, nullptr);
+                         a.xs_init + b0 * N1 * nxl, a.us_init + b0 * (long)N * NU, a.is_feasible, nullptr, rep_ref(b0),
+                         a.surf + b0, NC);
   };
   // one FDDP iteration of slice k: node stage, backward pass, line search, step decision
   auto enqueue_iter = [&](int k, int it) -> int {
@@ -3511,7 +3649,12 @@ int launch_solve_t(ffddp_handle* h, const SolveArgs& a, hipStream_t s, HostIO* i
     {
       ProfScope p(h, ss, KC_NODE);
       hipLaunchKernelGGL((k_node<NC, FF, FR, CW, UL, MD, MT>), dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, ss,
-                         h->dc, d, x0k, nrefk, irefk, surfk, 0, it & 1);
+                         h->dc, d, x0k, nrefk, irefk, surfk, 0, it & 1, (it == 0 && node_rep) ? 1 : 0);
+      if constexpr (REP) {
+        if (it == 0 && node_rep)
+          hipLaunchKernelGGL((k_node_rep<NC>), dim3((unsigned)(((long)Bk * (N - 1) + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK),
+                             0, ss, h->dc, d, nrefk, surfk);
+      }
     }
     if (it == 0 && stagger == 1 && k + 1 < S) HIPCHK(h, hipEventRecord(h->stg[k], ss));
     {
@@ -3842,6 +3985,7 @@ int ffddp_create(const ffddp_robot* robot, const ffddp_ocp_config* cfg, int devi
       }
     }
     if (const char* sg = std::getenv("FFDDP_STAGGER")) h->stagger = std::atoi(sg);
+    if (const char* nr = std::getenv("FFDDP_NODE_REP")) h->node_rep = std::atoi(nr) != 0;
     if (const char* cs = std::getenv("FFDDP_CALLER_SLICE")) h->caller_slice = std::atoi(cs) != 0;
     const char* f1 = std::getenv("FFDDP_FW_FIRST");
     if (f1) {
@@ -3873,6 +4017,8 @@ int ffddp_create(const ffddp_robot* robot, const ffddp_ocp_config* cfg, int devi
   rc |= dalloc(h, &d.trial_fail, (size_t)B * NTRIALS);
   rc |= dalloc(h, &d.st, (size_t)B);
   rc |= dalloc(h, &d.alist, (size_t)B * 2);
+  rc |= dalloc(h, &d.uni0, (size_t)B);
+  rc |= dalloc(h, &d.rep, (size_t)B * REP_W);
   rc |= dalloc(h, &d.acnt, (size_t)4 * 8);
   rc |= dalloc(h, &h->in_x0, (size_t)B * nx);
   rc |= dalloc(h, &h->in_nref, (size_t)B * (N + 1) * 6);
@@ -4724,14 +4870,14 @@ int ffddp_calc_diff_mnt(ffddp_handle* h, int B, const double* x0, const double* 
   HIPCHK(h, hipMemcpy(h->in_xs, xs, (size_t)B * (N + 1) * nx * 8, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->in_us, us, (size_t)B * N * NU * 8, hipMemcpyHostToDevice));
   // node kernel reads (xs, us) from the solver state: initialise it from the inputs
-  hipLaunchKernelGGL(k_init<false>, dim3(1024), dim3(INIT_BLOCK), 0, nullptr, h->dc, d, h->in_xs, h->in_us, 0, nullptr);
+  hipLaunchKernelGGL(k_init<false>, dim3(1024), dim3(INIT_BLOCK), 0, nullptr, h->dc, d, h->in_xs, h->in_us, 0, nullptr, nullptr, nullptr, 0);
   const int rc = dispatch_variant(h, d.fref != nullptr, d.cw != nullptr, d.ul != nullptr, d.md != nullptr, d.mt != nullptr,
                                   [&](auto NC, auto FF, auto FR, auto CW, auto UL, auto MD, auto MT) {
     const long nodes = (long)B * (N + 1);
     hipLaunchKernelGGL((k_node<decltype(NC)::value, decltype(FF)::value, decltype(FR)::value, decltype(CW)::value,
                                decltype(UL)::value, decltype(MD)::value, decltype(MT)::value>),
                        dim3((int)((nodes + NODE_GPB - 1) / NODE_GPB)), dim3(NODE_BLOCK), 0, nullptr, h->dc, d, h->in_x0,
-                       h->in_nref, h->in_iref, h->in_surf, 1, 0);
+                       h->in_nref, h->in_iref, h->in_surf, 1, 0, 0);
     return 0;
   });
   if (rc) return rc;

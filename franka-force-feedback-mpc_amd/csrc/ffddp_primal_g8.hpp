@@ -31,9 +31,11 @@ __device__ __forceinline__ double cw_get(const double* __restrict__ cw, int i, d
 
 // friction_cone of ffddp_node.hpp with the weight *wp, loaded after the facet
 // sums, where it is first needed (same operations in the same order:
-// *wp = C.w_fc gives its bits)
-__device__ __forceinline__ double friction_cone_w(const DevConsts& C, const double* __restrict__ wp, const double* lam,
-                                                  double* gl, double* Hd, double* Ho) {
+// *wp = C.w_fc gives its bits).  friction_cone_sums leaves the cost as its
+// factors w and c (the cost is w c), for a caller that adds it by an explicit
+// fma (ee_contact_costs).
+__device__ __forceinline__ void friction_cone_sums(const DevConsts& C, const double* __restrict__ wp, const double* lam,
+                                                   double* gl, double* Hd, double* Ho, double& c_out, double& w_out) {
   double c = 0.0;
   double g0 = 0.0, g1 = 0.0, g2 = 0.0, h00 = 0.0, h11 = 0.0, h22 = 0.0, h10 = 0.0, h20 = 0.0, h21 = 0.0;
 #pragma unroll
@@ -63,7 +65,167 @@ __device__ __forceinline__ double friction_cone_w(const DevConsts& C, const doub
   Ho[0] = w * h10;
   Ho[1] = w * h20;
   Ho[2] = w * h21;
+  c_out = c;
+  w_out = w;
+}
+__device__ __forceinline__ double friction_cone_w(const DevConsts& C, const double* __restrict__ wp, const double* lam,
+                                                  double* gl, double* Hd, double* Ho) {
+  double c, w;
+  friction_cone_sums(C, wp, lam, gl, Hd, Ho, c, w);
   return w * c;
+}
+
+// The per-instance stash of k_node_rep (ffddp_kernels.hip): what node 0 of a
+// uniform cold start leaves for the nodes 1..N-1 that share its (x, u) and
+// the record does not hold.  Layout in doubles:
+constexpr int REP_COL = 0;                         // [14][NDENSE_MAX] residual-Jacobian columns (state directions)
+constexpr int REP_GX = REP_COL + 14 * NDENSE_MAX;  // [14] state-residual gradient
+constexpr int REP_CJ = REP_GX + 14;                // the joint lanes' summed state / control costs
+constexpr int REP_PEE = REP_CJ + 1;                // EE position, velocity, angular velocity,
+constexpr int REP_VP = REP_PEE + 3;                // orientation residual and the contact force the
+constexpr int REP_WEE = REP_VP + 3;                // costs see
+constexpr int REP_RR = REP_WEE + 3;
+constexpr int REP_LM = REP_RR + 3;
+constexpr int REP_XN = REP_LM + 3;                 // [14] the node's next state
+constexpr int REP_W = (REP_XN + 14 + 1) & ~1;
+
+// The EE / contact cost terms of a node with their Gauss-Newton weights: the
+// only part of the calc the node references (ref, *fnp) enter once the
+// dynamics are solved.  k_node (through node_primal_g8) and k_node_rep both
+// call it, so it is written with explicit fma and contraction off: the
+// compiler cannot round the two call sites differently.  Dd / gd: the dense
+// rows' weights and gradients; Ho: the friction cone's off-diagonal weights
+// (zero without one); returns the terms' cost.
+template <int NC, bool FR, bool CW>
+__device__ __forceinline__ double ee_contact_costs(const DevConsts& C, bool surface, const double* rr,
+                                                   const double* wee, const double* pee, const double* vp,
+                                                   const double* lm, const double* __restrict__ ref,
+                                                   const double* __restrict__ fnp, const double* __restrict__ cwr,
+                                                   double* Dd, double* gd, double* Ho) {
+#pragma clang fp contract(off)
+  auto wt = [&](int i, double c) { return cw_get<CW>(cwr, i, c); };
+#pragma unroll
+  for (int k = 0; k < NDENSE_MAX; ++k) Dd[k] = gd[k] = 0.0;
+  Ho[0] = Ho[1] = Ho[2] = 0.0;
+  double cee = 0.0;
+  {
+    const double w = wt(FFDDP_CW_EE_ORI, C.w_ori);
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      s = fma(C.ori_w[i] * rr[i], rr[i], s);
+      Dd[3 + i] = w * C.ori_w[i];
+      gd[3 + i] = w * C.ori_w[i] * rr[i];
+    }
+    cee = fma(w, 0.5 * s, cee);
+  }
+  {
+    const double w = wt(FFDDP_CW_WDAMP, C.w_wd);
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      s = fma(C.wd_w[i] * wee[i], wee[i], s);
+      Dd[9 + i] = w * C.wd_w[i];
+      gd[9 + i] = w * C.wd_w[i] * wee[i];
+    }
+    cee = fma(w, 0.5 * s, cee);
+  }
+  if (!surface) {
+    const double w = wt(FFDDP_CW_EE_POS, C.w_ee_pos);
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const double r = pee[i] - ref[i];
+      s = fma(C.ee_pos_w[i] * r, r, s);
+      Dd[i] = w * C.ee_pos_w[i];
+      gd[i] = w * C.ee_pos_w[i] * r;
+    }
+    cee = fma(w, 0.5 * s, cee);
+  } else {
+    const double pstar2 = ref[2] - C.z_press;
+    {
+      const double w = wt(FFDDP_CW_TANGENT_POS, C.w_tp);
+      const double rx = pee[0] - ref[0], ry = pee[1] - ref[1], rz = pee[2] - ref[2];
+      const double s = fma(0.0 * rz, rz, fma(rx, rx, ry * ry));
+      Dd[0] = w;
+      Dd[1] = w;
+      gd[0] = w * rx;
+      gd[1] = w * ry;
+      cee = fma(w, 0.5 * s, cee);
+    }
+    {
+      const double w = wt(FFDDP_CW_TANGENT_VEL, C.w_tv);
+      const double rx = vp[0] - ref[3], ry = vp[1] - ref[4];
+      Dd[6] = w;
+      Dd[7] = w;
+      gd[6] = w * rx;
+      gd[7] = w * ry;
+      cee = fma(w, 0.5 * fma(rx, rx, ry * ry), cee);
+    }
+    if (C.has_pz) {
+      const double w = wt(FFDDP_CW_PLANE_Z, C.w_pz);
+      const double rz = pee[2] - pstar2;
+      Dd[2] = w;
+      gd[2] = w * rz;
+      cee = fma(w, 0.5 * rz * rz, cee);
+    }
+    if (C.has_vz) {
+      const double w = wt(FFDDP_CW_VZ, C.w_vz);
+      Dd[8] = w;
+      gd[8] = w * vp[2];
+      cee = fma(w, 0.5 * vp[2] * vp[2], cee);
+    }
+    if (NC == 3 && C.has_fc) {
+      double gl[3], Hd[3], cfc, wfc;
+      friction_cone_sums(C, CW ? cwr + FFDDP_CW_FRICTION_CONE : &C.w_fc, lm, gl, Hd, Ho, cfc, wfc);
+      cee = fma(wfc, cfc, cee);
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        Dd[12 + r] = Hd[r];
+        gd[12 + r] = gl[r];
+      }
+    }
+    if (C.has_uni) {
+      const double w = wt(FFDDP_CW_UNILATERAL, C.w_uni);
+      double s = 0.0;
+#pragma unroll
+      for (int r = 0; r < NC; ++r) {
+        double ai, Ar, Arr;
+        barrier(lm[r], C.uni_lb[r], C.uni_ub[r], ai, Ar, Arr);
+        s = s + ai;
+        Dd[12 + r] = fma(w, Arr, Dd[12 + r]);
+        gd[12 + r] = fma(w, Ar, gd[12 + r]);
+      }
+      cee = fma(w, s, cee);
+    }
+    if (C.has_fn) {
+      const double w = wt(FFDDP_CW_FN, C.w_fn);
+      double s = 0.0;
+      double fnr = 0.0;
+      if constexpr (FR) fnr = *fnp;
+#pragma unroll
+      for (int r = 0; r < NC; ++r) {
+        const double e = lm[r] - ((FR && r == NC - 1) ? fnr : C.fn_ref[r]);
+        s = fma(C.fn_w[r] * e, e, s);
+        Dd[12 + r] = fma(w, C.fn_w[r], Dd[12 + r]);
+        gd[12 + r] = fma(w * C.fn_w[r], e, gd[12 + r]);
+      }
+      cee = fma(w, 0.5 * s, cee);
+    }
+  }
+  return cee;
+}
+
+// Lx entry j of a node: its residual-Jacobian column against the dense rows'
+// gradients plus the state-residual gradient, scaled; the other function
+// k_node and k_node_rep share (explicit fma, contraction off)
+template <int ND>
+__device__ __forceinline__ double node_lx_entry(const double* col, const double* g, double gxj, double sc) {
+#pragma clang fp contract(off)
+  double lx = 0.0;
+#pragma unroll
+  for (int r = 0; r < ND; ++r) lx = fma(col[r], g[r], lx);
+  return (lx + gxj) * sc;
 }
 
 // gp: this node's Primal in global memory; lk: its link record (LK_* layout).
@@ -88,7 +250,7 @@ __device__ __forceinline__ double friction_cone_w(const DevConsts& C, const doub
 // mtr (ffddp.h FFDDP_MOUNT_W: 0 base_R, 9 base_p, 12 gravity) instead of
 // C.rb.joint_R[0] / joint_p[0], and every lane's gravity vector is the row's
 // instead of C.rb.gravity, each read at its use, for the same reason.
-template <int NC, bool FR = false, bool CW = false, bool UL = false, bool MD = false, bool MT = false>
+template <int NC, bool FR = false, bool CW = false, bool UL = false, bool MD = false, bool MT = false, bool STRICT = false>
 __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, bool surface, double q, double v, double u,
                                                  double xq, double xv, double tr, const double* ref,
                                                  Primal* __restrict__ gp, double* __restrict__ lk, double (&lam)[3],
@@ -96,7 +258,8 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
                                                  const double* __restrict__ cwr = nullptr,
                                                  const double* __restrict__ ulr = nullptr,
                                                  const double* __restrict__ mdr = nullptr,
-                                                 const double* __restrict__ mtr = nullptr) {
+                                                 const double* __restrict__ mtr = nullptr,
+                                                 double* __restrict__ stash = nullptr) {
   const ffddp_robot& rb = C.rb;
   const int li = g8_lane();
   const bool J = li < NQ;
@@ -595,14 +758,15 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
     }
   }
   // EE / contact residuals: every lane computes them (group-uniform operands);
-  // lane k < NDENSE_MAX stores dense row k's weights
+  // lane k < NDENSE_MAX stores dense row k's weights.  STRICT (the kernels
+  // k_node_rep completes): through ee_contact_costs, which k_node_rep calls
+  // too; the others keep the terms written out here, as the compiler has
+  // contracted them so far.
   double Dd[NDENSE_MAX], gd[NDENSE_MAX];
-#pragma unroll
-  for (int k = 0; k < NDENSE_MAX; ++k) Dd[k] = gd[k] = 0.0;
   double cee = 0.0;
   double rr[3], th;
-  {
-    double Rrel[9];
+  if constexpr (STRICT) {
+    double Rrel[9], Ho[3];
 #pragma unroll
     for (int a_ = 0; a_ < 3; ++a_)
 #pragma unroll
@@ -610,112 +774,145 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
         Rrel[3 * a_ + b_] = C.Rdes[0 * 3 + a_] * Ree[0 * 3 + b_] + C.Rdes[1 * 3 + a_] * Ree[1 * 3 + b_] +
                             C.Rdes[2 * 3 + a_] * Ree[2 * 3 + b_];
     log3(Rrel, rr, th);
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      s += C.ori_w[i] * rr[i] * rr[i];
-      Dd[3 + i] += wt(FFDDP_CW_EE_ORI, C.w_ori) * C.ori_w[i];
-      gd[3 + i] += wt(FFDDP_CW_EE_ORI, C.w_ori) * C.ori_w[i] * rr[i];
-    }
-    cee += wt(FFDDP_CW_EE_ORI, C.w_ori) * (0.5 * s);
-  }
-  {
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      s += C.wd_w[i] * wee[i] * wee[i];
-      Dd[9 + i] += wt(FFDDP_CW_WDAMP, C.w_wd) * C.wd_w[i];
-      gd[9 + i] += wt(FFDDP_CW_WDAMP, C.w_wd) * C.wd_w[i] * wee[i];
-    }
-    cee += wt(FFDDP_CW_WDAMP, C.w_wd) * (0.5 * s);
-  }
-  if (!surface) {
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const double r = pee[i] - ref[i];
-      s += C.ee_pos_w[i] * r * r;
-      Dd[i] += wt(FFDDP_CW_EE_POS, C.w_ee_pos) * C.ee_pos_w[i];
-      gd[i] += wt(FFDDP_CW_EE_POS, C.w_ee_pos) * C.ee_pos_w[i] * r;
-    }
-    cee += wt(FFDDP_CW_EE_POS, C.w_ee_pos) * (0.5 * s);
-  } else {
-    const double pstar2 = ref[2] - C.z_press;
-    {
-      const double rx = pee[0] - ref[0], ry = pee[1] - ref[1], rz = pee[2] - ref[2];
-      const double s = rx * rx + ry * ry + 0.0 * rz * rz;
-      Dd[0] += wt(FFDDP_CW_TANGENT_POS, C.w_tp);
-      Dd[1] += wt(FFDDP_CW_TANGENT_POS, C.w_tp);
-      gd[0] += wt(FFDDP_CW_TANGENT_POS, C.w_tp) * rx;
-      gd[1] += wt(FFDDP_CW_TANGENT_POS, C.w_tp) * ry;
-      cee += wt(FFDDP_CW_TANGENT_POS, C.w_tp) * (0.5 * s);
-    }
-    {
-      const double rx = vp[0] - ref[3], ry = vp[1] - ref[4];
-      Dd[6] += wt(FFDDP_CW_TANGENT_VEL, C.w_tv);
-      Dd[7] += wt(FFDDP_CW_TANGENT_VEL, C.w_tv);
-      gd[6] += wt(FFDDP_CW_TANGENT_VEL, C.w_tv) * rx;
-      gd[7] += wt(FFDDP_CW_TANGENT_VEL, C.w_tv) * ry;
-      cee += wt(FFDDP_CW_TANGENT_VEL, C.w_tv) * (0.5 * (rx * rx + ry * ry));
-    }
-    if (C.has_pz) {
-      const double rz = pee[2] - pstar2;
-      Dd[2] += wt(FFDDP_CW_PLANE_Z, C.w_pz);
-      gd[2] += wt(FFDDP_CW_PLANE_Z, C.w_pz) * rz;
-      cee += wt(FFDDP_CW_PLANE_Z, C.w_pz) * (0.5 * rz * rz);
-    }
-    if (C.has_vz) {
-      Dd[8] += wt(FFDDP_CW_VZ, C.w_vz);
-      gd[8] += wt(FFDDP_CW_VZ, C.w_vz) * vp[2];
-      cee += wt(FFDDP_CW_VZ, C.w_vz) * (0.5 * vp[2] * vp[2]);
-    }
     double lm[3] = {0, 0, 0};
     if (mode != MODE_TERMINAL_X)
 #pragma unroll
       for (int r = 0; r < NC; ++r) lm[r] = lam[r];
-    if (NC == 3 && C.has_fc) {
-      double gl[3], Hd[3], Ho[3];
-      if constexpr (CW)
-        cee += friction_cone_w(C, cwr + FFDDP_CW_FRICTION_CONE, lm, gl, Hd, Ho);
-      else
-        cee += friction_cone(C, lm, gl, Hd, Ho);
+    cee = ee_contact_costs<NC, FR, CW>(C, surface, rr, wee, pee, vp, lm, ref, fnp, cwr, Dd, gd, Ho);
+    if (surface && li == 0) {
 #pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        Dd[12 + r] += Hd[r];
-        gd[12 + r] += gl[r];
-      }
-      if (li == 0) {
-#pragma unroll
-        for (int r = 0; r < 3; ++r) gp->Dfo[r] = Ho[r];
-      }
-    } else if (li == 0) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r) gp->Dfo[r] = 0.0;
+      for (int r = 0; r < 3; ++r) gp->Dfo[r] = Ho[r];
     }
-    if (C.has_uni) {
+    if (stash != nullptr && li == 0) {
+      // what k_node_rep recomputes the replicated nodes' residual terms from
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        stash[REP_PEE + k] = pee[k];
+        stash[REP_VP + k] = vp[k];
+        stash[REP_WEE + k] = wee[k];
+        stash[REP_RR + k] = rr[k];
+        stash[REP_LM + k] = lm[k];
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < NDENSE_MAX; ++k) Dd[k] = gd[k] = 0.0;
+    {
+      double Rrel[9];
+#pragma unroll
+      for (int a_ = 0; a_ < 3; ++a_)
+#pragma unroll
+        for (int b_ = 0; b_ < 3; ++b_)
+          Rrel[3 * a_ + b_] = C.Rdes[0 * 3 + a_] * Ree[0 * 3 + b_] + C.Rdes[1 * 3 + a_] * Ree[1 * 3 + b_] +
+                              C.Rdes[2 * 3 + a_] * Ree[2 * 3 + b_];
+      log3(Rrel, rr, th);
       double s = 0.0;
 #pragma unroll
-      for (int r = 0; r < NC; ++r) {
-        double ai, Ar, Arr;
-        barrier(lm[r], C.uni_lb[r], C.uni_ub[r], ai, Ar, Arr);
-        s += ai;
-        Dd[12 + r] += wt(FFDDP_CW_UNILATERAL, C.w_uni) * Arr;
-        gd[12 + r] += wt(FFDDP_CW_UNILATERAL, C.w_uni) * Ar;
+      for (int i = 0; i < 3; ++i) {
+        s += C.ori_w[i] * rr[i] * rr[i];
+        Dd[3 + i] += wt(FFDDP_CW_EE_ORI, C.w_ori) * C.ori_w[i];
+        gd[3 + i] += wt(FFDDP_CW_EE_ORI, C.w_ori) * C.ori_w[i] * rr[i];
       }
-      cee += wt(FFDDP_CW_UNILATERAL, C.w_uni) * s;
+      cee += wt(FFDDP_CW_EE_ORI, C.w_ori) * (0.5 * s);
     }
-    if (C.has_fn) {
+    {
       double s = 0.0;
-      double fnr = 0.0;
-      if constexpr (FR) fnr = *fnp;
 #pragma unroll
-      for (int r = 0; r < NC; ++r) {
-        const double e = lm[r] - ((FR && r == NC - 1) ? fnr : C.fn_ref[r]);
-        s += C.fn_w[r] * e * e;
-        Dd[12 + r] += wt(FFDDP_CW_FN, C.w_fn) * C.fn_w[r];
-        gd[12 + r] += wt(FFDDP_CW_FN, C.w_fn) * C.fn_w[r] * e;
+      for (int i = 0; i < 3; ++i) {
+        s += C.wd_w[i] * wee[i] * wee[i];
+        Dd[9 + i] += wt(FFDDP_CW_WDAMP, C.w_wd) * C.wd_w[i];
+        gd[9 + i] += wt(FFDDP_CW_WDAMP, C.w_wd) * C.wd_w[i] * wee[i];
       }
-      cee += wt(FFDDP_CW_FN, C.w_fn) * (0.5 * s);
+      cee += wt(FFDDP_CW_WDAMP, C.w_wd) * (0.5 * s);
+    }
+    if (!surface) {
+      double s = 0.0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double r = pee[i] - ref[i];
+        s += C.ee_pos_w[i] * r * r;
+        Dd[i] += wt(FFDDP_CW_EE_POS, C.w_ee_pos) * C.ee_pos_w[i];
+        gd[i] += wt(FFDDP_CW_EE_POS, C.w_ee_pos) * C.ee_pos_w[i] * r;
+      }
+      cee += wt(FFDDP_CW_EE_POS, C.w_ee_pos) * (0.5 * s);
+    } else {
+      const double pstar2 = ref[2] - C.z_press;
+      {
+        const double rx = pee[0] - ref[0], ry = pee[1] - ref[1], rz = pee[2] - ref[2];
+        const double s = rx * rx + ry * ry + 0.0 * rz * rz;
+        Dd[0] += wt(FFDDP_CW_TANGENT_POS, C.w_tp);
+        Dd[1] += wt(FFDDP_CW_TANGENT_POS, C.w_tp);
+        gd[0] += wt(FFDDP_CW_TANGENT_POS, C.w_tp) * rx;
+        gd[1] += wt(FFDDP_CW_TANGENT_POS, C.w_tp) * ry;
+        cee += wt(FFDDP_CW_TANGENT_POS, C.w_tp) * (0.5 * s);
+      }
+      {
+        const double rx = vp[0] - ref[3], ry = vp[1] - ref[4];
+        Dd[6] += wt(FFDDP_CW_TANGENT_VEL, C.w_tv);
+        Dd[7] += wt(FFDDP_CW_TANGENT_VEL, C.w_tv);
+        gd[6] += wt(FFDDP_CW_TANGENT_VEL, C.w_tv) * rx;
+        gd[7] += wt(FFDDP_CW_TANGENT_VEL, C.w_tv) * ry;
+        cee += wt(FFDDP_CW_TANGENT_VEL, C.w_tv) * (0.5 * (rx * rx + ry * ry));
+      }
+      if (C.has_pz) {
+        const double rz = pee[2] - pstar2;
+        Dd[2] += wt(FFDDP_CW_PLANE_Z, C.w_pz);
+        gd[2] += wt(FFDDP_CW_PLANE_Z, C.w_pz) * rz;
+        cee += wt(FFDDP_CW_PLANE_Z, C.w_pz) * (0.5 * rz * rz);
+      }
+      if (C.has_vz) {
+        Dd[8] += wt(FFDDP_CW_VZ, C.w_vz);
+        gd[8] += wt(FFDDP_CW_VZ, C.w_vz) * vp[2];
+        cee += wt(FFDDP_CW_VZ, C.w_vz) * (0.5 * vp[2] * vp[2]);
+      }
+      double lm[3] = {0, 0, 0};
+      if (mode != MODE_TERMINAL_X)
+#pragma unroll
+        for (int r = 0; r < NC; ++r) lm[r] = lam[r];
+      if (NC == 3 && C.has_fc) {
+        double gl[3], Hd[3], Ho[3];
+        if constexpr (CW)
+          cee += friction_cone_w(C, cwr + FFDDP_CW_FRICTION_CONE, lm, gl, Hd, Ho);
+        else
+          cee += friction_cone(C, lm, gl, Hd, Ho);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          Dd[12 + r] += Hd[r];
+          gd[12 + r] += gl[r];
+        }
+        if (li == 0) {
+#pragma unroll
+          for (int r = 0; r < 3; ++r) gp->Dfo[r] = Ho[r];
+        }
+      } else if (li == 0) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) gp->Dfo[r] = 0.0;
+      }
+      if (C.has_uni) {
+        double s = 0.0;
+#pragma unroll
+        for (int r = 0; r < NC; ++r) {
+          double ai, Ar, Arr;
+          barrier(lm[r], C.uni_lb[r], C.uni_ub[r], ai, Ar, Arr);
+          s += ai;
+          Dd[12 + r] += wt(FFDDP_CW_UNILATERAL, C.w_uni) * Arr;
+          gd[12 + r] += wt(FFDDP_CW_UNILATERAL, C.w_uni) * Ar;
+        }
+        cee += wt(FFDDP_CW_UNILATERAL, C.w_uni) * s;
+      }
+      if (C.has_fn) {
+        double s = 0.0;
+        double fnr = 0.0;
+        if constexpr (FR) fnr = *fnp;
+#pragma unroll
+        for (int r = 0; r < NC; ++r) {
+          const double e = lm[r] - ((FR && r == NC - 1) ? fnr : C.fn_ref[r]);
+          s += C.fn_w[r] * e * e;
+          Dd[12 + r] += wt(FFDDP_CW_FN, C.w_fn) * C.fn_w[r];
+          gd[12 + r] += wt(FFDDP_CW_FN, C.w_fn) * C.fn_w[r] * e;
+        }
+        cee += wt(FFDDP_CW_FN, C.w_fn) * (0.5 * s);
+      }
     }
   }
   if (li == 0) {
@@ -734,8 +931,10 @@ __device__ __forceinline__ double node_primal_g8(const DevConsts& C, int mode, b
       gp->D[k] = Dd[k];
       gp->g[k] = gd[k];
     }
-  const double cost = g8_sum(J ? cj : 0.0) + cee;
+  const double cjs = g8_sum(J ? cj : 0.0);
+  const double cost = cjs + cee;
   if (li == 0) gp->cost = cost;
+  if (STRICT && stash != nullptr && li == 0) stash[REP_CJ] = cjs;
   // ---- Euler step ----
   if (J) {
     if (with_dyn) {
